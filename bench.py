@@ -1,7 +1,7 @@
 """bench.py — the north-star measurement (BASELINE.json): pack -> reduce over 65 536 variable-length
 sequences, hidden 512, bf16, per GPU; M elements/s whole-job + % of the HBM roofline.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One step = one pass of the hot path over one batch already resident in HBM:
@@ -11,9 +11,17 @@ One step = one pass of the hot path over one batch already resident in HBM:
     (N > 1: one RCCL all-gather of `out`; sequences are sharded, payload never crosses xGMI)
 Nothing is cached between steps: every step uploads the lengths again, re-sorts, re-scans, re-moves.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (the pack row mover:
-algorithmic bytes 2*N*H*e + 8*(3B+T)), timed with HIP events on the launch stream
-inside the timed region.  `cpu_baseline` times the oracle port on the host cores on a bounded sample.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the steps and prints the headline
+(`value`, `ms_per_step` and the configuration).  `--full` adds everything else, measured as before: per-rank
+and per-kernel figures, `roofline` for the dominant kernel (the pack row mover: algorithmic bytes
+2*N*H*e + 8*(3B+T)) timed with HIP events on the launch stream inside the timed region, the
+device-lengths, fused, copy-ceiling and forward + backward legs, `parity`, and `cpu_baseline`, which times the
+oracle port on the host cores on a bounded sample.
+
+`--dump-outputs DIR` writes what the last timed step returned as float32 / float64 .npy files (rank 0):
+the [B*world, H] sums (`sums`), the PackedSequence's `pack_data`, `batch_sizes`, `sorted_indices` and
+`unsorted_indices`.  An array larger than its share of the 64 MB budget is written as a fixed, seeded
+sample of its rows, the same rows in every run with the same arguments.
 """
 import argparse
 import json
@@ -41,7 +49,39 @@ def parse():
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--trace-host', action='store_true', help='print per-step host enqueue time to stderr')
     ap.add_argument('--cpu-sample', type=int, default=16384, help='sequences in the CPU-baseline sample (16 384 = a quarter of the batch: ~10 s of host work for the two CPU legs)')
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true', help='also measure the per-kernel, roofline, side-leg, parity and '
+                                                        'CPU-baseline figures (a plain run reports the headline only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
+
+
+# bytes of .npy payload per dumped array (58 MB in all): larger arrays are written as a seeded sample of their rows
+DUMP_BUDGET = {'sums': 20_000_000, 'pack_data': 32_000_000, 'batch_sizes': 2_000_000, 'sorted_indices': 2_000_000,
+               'unsorted_indices': 2_000_000}
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each tensor as <out_dir>/<name>.npy: floating point as float32, integers as float64 (exact below 2^53).
+    Rows beyond the array's budget are thinned to a sorted sample drawn from a generator seeded by the name, so two
+    runs with the same arguments write the same rows."""
+    import zlib
+
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        dtype = torch.float32 if t.is_floating_point() else torch.float64
+        rows = t.size(0)
+        row_bytes = (t.numel() // max(1, rows)) * (4 if dtype == torch.float32 else 8)
+        keep = max(1, DUMP_BUDGET[name] // max(1, row_bytes))
+        if rows > keep:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            pick = torch.randperm(rows, generator=g)[:keep].sort().values
+            t = t[pick.to(t.device)]
+        np.save(os.path.join(out_dir, f'{name}.npy'), t.detach().to(dtype).cpu().numpy())
 
 
 def make_inputs(args, rank, dev):
@@ -294,7 +334,8 @@ def main():
     e = data.element_size()
 
     timer = KernelTimer(['to_pack', 'reduce', 'pack_reduce'])
-    _ops.set_kernel_hook(timer)
+    if args.full or args.trace_host:        # the per-kernel figures: a plain run records no events
+        _ops.set_kernel_hook(timer)
 
     def step(host_mirror=True):
         if host_mirror:
@@ -355,9 +396,12 @@ def main():
     # sanity inside the bench: the last step's output is a real PackedSequence and a [B, H] sum
     assert p.data.shape == data.shape and p.batch_sizes.numel() == T and out.shape[-1] == H
     assert out.shape[0] == B * world
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'sums': out, 'pack_data': p.data, 'batch_sizes': p.batch_sizes,
+                                         'sorted_indices': p.sorted_indices, 'unsorted_indices': p.unsorted_indices})
 
     extra = {}
-    if world == 1:                     # the same pipeline with device-only lengths (blocking D2H per pack)
+    if world == 1 and args.full:       # the same pipeline with device-only lengths (blocking D2H per pack)
         sync()
         k = max(5, args.steps // 2)
         step(host_mirror=False)
@@ -464,12 +508,14 @@ def main():
     # the host sort of this rank's lengths, all ranks sorting at the same moment (per-rank host time
     # must stay under the per-rank kernel time when eight ranks share one host)
     from torchrua_amd import _meta
-    if use_dist:
-        dist.barrier()
-    ts = time.perf_counter()
-    for _ in range(20):
-        _meta.host_sort_desc(lens_host)
-    sort_ms = (time.perf_counter() - ts) / 20 * 1e3
+    sort_ms = 0.0
+    if args.full:
+        if use_dist:
+            dist.barrier()
+        ts = time.perf_counter()
+        for _ in range(20):
+            _meta.host_sort_desc(lens_host)
+        sort_ms = (time.perf_counter() - ts) / 20 * 1e3
     host_enqueue_ms = sum(host_ms) / max(1, len(host_ms))
     cpu_sets = [list(my_cpus)]
 
@@ -494,22 +540,6 @@ def main():
     if rank == 0:
         ms_step = dt / args.steps * 1e3
         value = n_total * H / (dt / args.steps) / 1e6
-        move_ms, red_ms = timer.mean_ms('to_pack'), timer.mean_ms('reduce')
-        pack_bytes = 2.0 * N * H * e + 8.0 * (3 * B + T)
-        reduce_bytes = 1.0 * N * H * e + 1.0 * B * H * e + 8.0 * B
-        achieved = pack_bytes / (move_ms * 1e-3) / 1e9
-        # HBM bytes per launch from the PMC counters are NOT measured by this run (rocprofv3 --pmc needs its own
-        # passes): the figure is carried from the committed profile of this same command and shape, with its source
-        # named beside it, and is null for any other shape
-        traffic, traffic_source = None, None
-        import glob
-        tpaths = sorted(glob.glob(os.path.join(ROOT, 'profiles', 'r[0-9][0-9]_traffic.json')))      # the latest round's
-        if tpaths and (B, H, args.lo, args.hi) == (65536, 512, 8, 512):
-            with open(tpaths[-1]) as f:
-                tj = json.load(f)
-            traffic = tj.get('to_pack_hbm_bytes_per_launch')
-            traffic_source = (f"profiles/{os.path.basename(tpaths[-1])} "
-                              f"({tj.get('collected', 'rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes')})")
         line = {
             'metric': f'pack->reduce throughput, {B} seqs/GPU h={H} bf16 (M elements/s) + % HBM roofline',
             'value': round(value, 1), 'unit': 'M elements/s', 'n_gpus': world, 'steps': args.steps,
@@ -526,30 +556,49 @@ def main():
                        'host_sort_threads_rank0': _meta.host_sort_threads(),
                        'host_sort_native': _meta.host_sort_is_native(),      # False: the self-test kept torch.sort
                        'backend': (os.environ.get('RUA_BENCH_BACKEND', 'nccl') + (' (RCCL)' if os.environ.get('RUA_BENCH_BACKEND', 'nccl') == 'nccl' else '')) if use_dist else None},
-            'per_rank': [{'rank': r, 'rows': int(row[0]), 'ms_per_step': round(row[1] / args.steps * 1e3, 4),
-                          'pack_kernel_GBps': round((2.0 * row[0] * H * e + 8.0 * (3 * B + T)) / (row[2] * 1e-3) / 1e9, 1) if row[2] else None,
-                          'reduce_kernel_GBps': round((row[0] * H * e + 1.0 * B * H * e + 8.0 * B) / (row[3] * 1e-3) / 1e9, 1) if row[3] else None,
-                          'kernel_ms': round(row[2] + row[3], 4), 'host_enqueue_ms': round(row[4], 4),
-                          'host_sort_ms': round(row[5], 4), 'torch_threads': int(row[6]),
-                          'cpus': _ranges(cpu_sets[r]) if r < len(cpu_sets) and cpu_sets[r] is not None else None}
-                         for r, row in enumerate(per_rank)],
-            'roofline': {'bound': 'hbm', 'kernel': 'move_rows_kernel<16,false,NT,1,16,256,4> (C->P pack, 16-row tiles)',
-                         'achieved': round(achieved, 1), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                         'frac': round(achieved / HBM_PEAK_GBS, 4), 'traffic': traffic, 'traffic_source': traffic_source,
-                         'algorithmic_bytes': pack_bytes, 'avg_ms': round(move_ms, 4)},
-            'reduce_kernel': {'kernel': 'seg_reduce_kernel<bf16,8,SUM,NT> (over P)', 'avg_ms': round(red_ms, 4),
-                              'achieved': round(reduce_bytes / (red_ms * 1e-3) / 1e9, 1), 'unit': 'GB/s',
-                              'frac': round(reduce_bytes / (red_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)},
-            'pipeline': {'algorithmic_bytes': pack_bytes + reduce_bytes,
-                         'kernel_ms': round(move_ms + red_ms, 4),
-                         'frac_of_hbm_peak_kernels': round((pack_bytes + reduce_bytes) / ((move_ms + red_ms) * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                         'frac_of_hbm_peak_wall': round((pack_bytes + reduce_bytes) * world / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS / world, 4)},
         }
+        if args.full:
+            move_ms, red_ms = timer.mean_ms('to_pack'), timer.mean_ms('reduce')
+            pack_bytes = 2.0 * N * H * e + 8.0 * (3 * B + T)
+            reduce_bytes = 1.0 * N * H * e + 1.0 * B * H * e + 8.0 * B
+            achieved = pack_bytes / (move_ms * 1e-3) / 1e9
+            # HBM bytes per launch from the PMC counters are NOT measured by this run (rocprofv3 --pmc needs its own
+            # passes): the figure is carried from the committed profile of this same command and shape, with its source
+            # named beside it, and is null for any other shape
+            traffic, traffic_source = None, None
+            import glob
+            tpaths = sorted(glob.glob(os.path.join(ROOT, 'profiles', 'r[0-9][0-9]_traffic.json')))      # the latest round's
+            if tpaths and (B, H, args.lo, args.hi) == (65536, 512, 8, 512):
+                with open(tpaths[-1]) as f:
+                    tj = json.load(f)
+                traffic = tj.get('to_pack_hbm_bytes_per_launch')
+                traffic_source = (f"profiles/{os.path.basename(tpaths[-1])} "
+                                  f"({tj.get('collected', 'rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes')})")
+            line.update({
+                'per_rank': [{'rank': r, 'rows': int(row[0]), 'ms_per_step': round(row[1] / args.steps * 1e3, 4),
+                              'pack_kernel_GBps': round((2.0 * row[0] * H * e + 8.0 * (3 * B + T)) / (row[2] * 1e-3) / 1e9, 1) if row[2] else None,
+                              'reduce_kernel_GBps': round((row[0] * H * e + 1.0 * B * H * e + 8.0 * B) / (row[3] * 1e-3) / 1e9, 1) if row[3] else None,
+                              'kernel_ms': round(row[2] + row[3], 4), 'host_enqueue_ms': round(row[4], 4),
+                              'host_sort_ms': round(row[5], 4), 'torch_threads': int(row[6]),
+                              'cpus': _ranges(cpu_sets[r]) if r < len(cpu_sets) and cpu_sets[r] is not None else None}
+                             for r, row in enumerate(per_rank)],
+                'roofline': {'bound': 'hbm', 'kernel': 'move_rows_kernel<16,false,NT,1,16,256,4> (C->P pack, 16-row tiles)',
+                             'achieved': round(achieved, 1), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+                             'frac': round(achieved / HBM_PEAK_GBS, 4), 'traffic': traffic, 'traffic_source': traffic_source,
+                             'algorithmic_bytes': pack_bytes, 'avg_ms': round(move_ms, 4)},
+                'reduce_kernel': {'kernel': 'seg_reduce_kernel<bf16,8,SUM,NT> (over P)', 'avg_ms': round(red_ms, 4),
+                                  'achieved': round(reduce_bytes / (red_ms * 1e-3) / 1e9, 1), 'unit': 'GB/s',
+                                  'frac': round(reduce_bytes / (red_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)},
+                'pipeline': {'algorithmic_bytes': pack_bytes + reduce_bytes,
+                             'kernel_ms': round(move_ms + red_ms, 4),
+                             'frac_of_hbm_peak_kernels': round((pack_bytes + reduce_bytes) / ((move_ms + red_ms) * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                             'frac_of_hbm_peak_wall': round((pack_bytes + reduce_bytes) * world / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS / world, 4)},
+            })
         line.update(extra)
         if 'copy_ceiling' in extra:
             line['roofline']['frac_of_copy_ceiling'] = round(achieved / extra['copy_ceiling']['GBps'], 4)
             line['roofline']['copy_ceiling_GBps'] = extra['copy_ceiling']['GBps']
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line['parity'] = parity_leg(ta, data, lens_host, out_graded)
             line['cpu_baseline'] = cpu_baseline(args)
             line['cpu_baseline_torch'] = cpu_baseline_torch(args)

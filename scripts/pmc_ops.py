@@ -2,9 +2,9 @@
 over-fetch of narrow rows and pads).
 
     # on the GPU box, one pass per counter (the pool refuses --pmc together with trace domains):
-    rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmcops_fetch -o run -- python3 scripts/pmc_ops.py run
-    rocprofv3 --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmcops_write -o run -- python3 scripts/pmc_ops.py run
-    python3 scripts/pmc_ops.py run --time > gpurun_out/pmcops_time.json          # HIP-event times, no profiler
+    rocprofv3 --pmc FETCH_SIZE --output-format csv -d prof_out/pmcops_fetch -o run -- python3 scripts/pmc_ops.py run
+    rocprofv3 --pmc WRITE_SIZE --output-format csv -d prof_out/pmcops_write -o run -- python3 scripts/pmc_ops.py run
+    python3 scripts/pmc_ops.py run --time > prof_out/pmcops_time.json            # HIP-event times, no profiler
     python3 scripts/pmc_ops.py summarize r04                                     # -> profiles/r04_pmc_ops.json
 
 `run` executes a fixed list of operator groups; every group is one uncounted warm-up and `REPS` counted launches of one
@@ -211,7 +211,7 @@ def cut(rows, order):
 
 
 def summarize(tag, pre='pmcops'):
-    G = os.path.join(ROOT, 'gpurun_out')
+    G = os.path.join(ROOT, os.environ.get('PROF_OUT', 'prof_out'))   # where scripts/profile_round.sh leaves the passes
     meta = json.load(open(os.path.join(G, f'{pre}_time.json')))
     order = meta['order']
     fetch = cut(counter_rows(os.path.join(G, f'{pre}_fetch'), 'FETCH_SIZE'), order)

@@ -1,9 +1,9 @@
-"""Condense rocprofv3 output under gpurun_out/ into the small, tracked files under profiles/.
+"""Condense rocprofv3 output under $PROF_OUT (default prof_out/) into the small, tracked files under profiles/.
 
     python scripts/summarize_prof.py r01          # -> profiles/r01_kernel_stats.csv, r01_pmc.json, r01_traffic.json
 
-Expects gpurun_out/prof_stats (--kernel-trace --stats), prof_fetch (--pmc FETCH_SIZE), prof_write
-(--pmc WRITE_SIZE), each from `bench.py --no-cpu-baseline` at the default (north-star) shape.
+Expects <PROF_OUT>/prof_stats (--kernel-trace --stats), prof_fetch (--pmc FETCH_SIZE), prof_write
+(--pmc WRITE_SIZE), each from `bench.py --full --no-cpu-baseline` at the default (north-star) shape.
 HBM bytes follow MI355X_MICROARCH.md §HBM: bytes = counter * 1024; on gfx950 FETCH_SIZE reports 1/2 of
 a wide coalesced read stream, so the read side is doubled; WRITE_SIZE is exact for 16-B stores."""
 import collections
@@ -15,8 +15,8 @@ import sys
 
 tag = sys.argv[1] if len(sys.argv) > 1 else 'r01'
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-G = os.path.join(ROOT, 'gpurun_out')
-PRE = os.environ.get('PROF_PREFIX', 'prof_')      # gpurun_out/<PRE>stats, <PRE>fetch, <PRE>write
+G = os.path.join(ROOT, os.environ.get('PROF_OUT', 'prof_out'))
+PRE = os.environ.get('PROF_PREFIX', 'prof_')      # <PROF_OUT>/<PRE>stats, <PRE>fetch, <PRE>write
 P = os.path.join(ROOT, 'profiles')
 os.makedirs(P, exist_ok=True)
 
@@ -85,7 +85,7 @@ if move:
     with open(os.path.join(P, f'{tag}_traffic.json'), 'w') as f:
         import datetime
         json.dump({'to_pack_hbm_bytes_per_launch': move[0]['hbm_bytes_per_launch'],
-                   'collected': f'rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes of `bench.py --no-cpu-baseline`, '
+                   'collected': f'rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes of `bench.py --full --no-cpu-baseline`, '
                                 f'gfx950 corrections per MI355X_MICROARCH.md, summarised {datetime.date.today().isoformat()}',
                    'source': f'profiles/{tag}_pmc.json'},
                   f, indent=1)

@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.gpu
 def test_bench_json_line():
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--batch', '512', '--hidden', '64', '--steps', '3',
-                          '--warmup', '1', '--cpu-sample', '64'], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          '--warmup', '1', '--cpu-sample', '64', '--full'], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{')]
     assert len(lines) == 1
@@ -52,7 +52,7 @@ def test_bench_starts_its_own_ranks():
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--batch', '512', '--hidden', '64',
-                          '--steps', '3', '--warmup', '1'], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
+                          '--steps', '3', '--warmup', '1', '--full'], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{')]
     assert len(lines) == 1, out.stdout
@@ -105,7 +105,7 @@ def test_bench_legs_are_sane_at_the_north_star_shape():
     torch.cuda.empty_cache()
     if torch.cuda.mem_get_info()[0] < 80 << 30:
         pytest.skip('needs ~75 GB of free HBM')
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '6', '--warmup', '3', '--cpu-sample', '256'],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '6', '--warmup', '3', '--cpu-sample', '256', '--full'],
                          capture_output=True, text=True, timeout=900, cwd=ROOT,
                          env=dict(os.environ))
     assert out.returncode == 0, out.stderr[-2000:]
@@ -126,3 +126,82 @@ def test_bench_legs_are_sane_at_the_north_star_shape():
     par = d['parity']
     assert par['max_exact'] is True and par['sum_f32_vs_fp64_over_sum_abs'] <= 1e-5
     assert par['logsumexp_f32_vs_reference_max_rel'] <= 1e-5 and par['pipeline_bf16_sum_vs_exact_rounded_to_bf16_max_ulps'] <= 1
+
+
+HEADLINE = ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
+            'vs_baseline', 'dtype', 'data', 'config')
+
+
+@pytest.mark.gpu
+def test_plain_bench_is_the_headline_and_dumps_what_the_timed_path_returned(tmp_path):
+    """A run without --full prints the headline only; --dump-outputs writes the last timed step's PackedSequence and
+    sums, identical from run to run, and the sums are the per-sequence sums of the dumped PackedSequence."""
+    import numpy as np
+    dumps = []
+    for run in range(2):
+        out_dir = tmp_path / f'run{run}'
+        out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--batch', '512', '--hidden', '64', '--lo', '1',
+                              '--hi', '64', '--steps', '3', '--warmup', '1', '--dump-outputs', str(out_dir)],
+                             capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{')]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert set(d) == set(HEADLINE), sorted(set(d) ^ set(HEADLINE))
+        assert d['steps'] == 3 and d['warmup'] == 1 and d['ms_per_step'] > 0 and d['value'] > 0
+        assert d['dtype'] == 'bf16' and d['higher_is_better'] is True and d['unit'] == 'M elements/s'
+        files = {f.name: np.load(f) for f in out_dir.iterdir()}
+        assert set(files) == {'sums.npy', 'pack_data.npy', 'batch_sizes.npy', 'sorted_indices.npy', 'unsorted_indices.npy'}
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+        assert sum(a.nbytes for a in files.values()) <= 64_000_000
+        dumps.append(files)
+    for name, a in dumps[0].items():
+        assert np.array_equal(a, dumps[1][name]), name
+    f = dumps[0]
+    sums, data, bs, srt = f['sums.npy'], f['pack_data.npy'], f['batch_sizes.npy'].astype(np.int64), f['sorted_indices.npy'].astype(np.int64)
+    assert sums.shape == (512, 64) and data.shape[0] == bs.sum() and data.shape[1] == 64    # small enough to be whole
+    assert np.array_equal(f['unsorted_indices.npy'].astype(np.int64), np.argsort(srt))
+    off = np.concatenate([[0], np.cumsum(bs)[:-1]])
+    want = np.zeros((512, 64), np.float64)
+    for t, (o, n) in enumerate(zip(off, bs)):
+        want[srt[:n]] += data[o:o + n]
+    assert np.allclose(sums, want, rtol=2 ** -7, atol=2 ** -4)
+
+
+def test_bench_refuses_zero_steps():
+    """--steps sets the number of timed steps, so there must be at least one (checked before any GPU call)."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '0'], capture_output=True, text=True,
+                         timeout=300, cwd=ROOT)
+    assert out.returncode != 0 and '--steps' in out.stderr
+    assert not [ln for ln in out.stdout.splitlines() if ln.startswith('{')]
+
+
+def test_dump_outputs_keeps_to_its_budget_with_a_fixed_sample(tmp_path):
+    """Arrays larger than their share are thinned to the same seeded rows every time; the total stays under 64 MB;
+    floating point is written as float32 and integers as float64, exactly."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(0)
+    arrays = {'sums': torch.randn((40000, 512), generator=g).to(torch.bfloat16),
+              'pack_data': torch.randn((70000, 512), generator=g).to(torch.bfloat16),
+              'batch_sizes': torch.arange(512, 0, -1), 'sorted_indices': torch.randperm(300000, generator=g),
+              'unsorted_indices': torch.randperm(1000, generator=g)}
+    bench.dump_outputs(str(tmp_path / 'a'), arrays)
+    bench.dump_outputs(str(tmp_path / 'b'), arrays)
+    total = 0
+    for name, t in arrays.items():
+        a, b = np.load(tmp_path / 'a' / f'{name}.npy'), np.load(tmp_path / 'b' / f'{name}.npy')
+        assert np.array_equal(a, b), name
+        assert a.dtype == (np.float32 if t.is_floating_point() else np.float64)
+        total += a.nbytes
+        full = t.to(torch.float32 if t.is_floating_point() else torch.float64).numpy()
+        if a.shape[0] == full.shape[0]:
+            assert np.array_equal(a, full), name
+        else:                                   # a sample: every dumped row is a row of the array, in order
+            assert a.nbytes <= bench.DUMP_BUDGET[name] and a.shape[1:] == full.shape[1:]
+            rows = {r.tobytes(): i for i, r in enumerate(full)}
+            idx = [rows[r.tobytes()] for r in a]
+            assert idx == sorted(idx) and len(set(idx)) == len(idx), name
+    assert total <= 64_000_000 and sum(bench.DUMP_BUDGET.values()) <= 64_000_000

@@ -61,7 +61,7 @@ def test_bench_line_over_rccl(world):
         pytest.skip(f'{torch.cuda.device_count()} GPU(s) on this box; needs {world}')
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'RUA_BENCH_DEVICE', 'RUA_BENCH_BACKEND')}
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(world), '--batch', '4096', '--hidden',
-                          '128', '--steps', '5', '--warmup', '2'], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                          '128', '--steps', '5', '--warmup', '2', '--full'], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith('{')][0])
     assert d['n_gpus'] == world and d['config']['backend'].startswith('nccl') and len(d['per_rank']) == world
