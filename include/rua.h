@@ -346,6 +346,14 @@ int rua_host_pack_scans(const int64_t* lens, int64_t B, const int64_t* batch_siz
                         int64_t* off);
 
 /* Introspection: ABI version and the gfx target the code objects were built for. */
+/* Dispatch trace, for tests: while on, every launch of a segmented-reduce kernel (rua_segment_reduce, rua_pack_reduce,
+ * rua_segment_reduce_backward, rua_fill_empty) appends one record on the host — the kernel template's name as spelled
+ * in rua_reduce_impl.h, then key=value pairs that tell its instantiations apart.  The log is process-global, holds the
+ * newest 512 records and costs one relaxed load per dispatch while off.  rua_debug_trace switches it and returns the
+ * previous state; rua_debug_trace_take copies whole records, one per line, into `buf`, removes them from the log and
+ * returns the bytes written (with buf == NULL: the bytes the whole log needs, nothing removed). */
+int rua_debug_trace(int32_t on);
+int64_t rua_debug_trace_take(char* buf, int64_t cap);
 int rua_abi_version(void);
 const char* rua_build_target(void);
 

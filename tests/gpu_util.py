@@ -1,8 +1,13 @@
-"""GPU-side helpers for the parity tests: golden/oracle containers <-> torchrua_amd containers."""
+"""GPU-side helpers for the parity tests: golden/oracle containers <-> torchrua_amd containers, and the reduce
+dispatch trace."""
+import contextlib
+import ctypes
+
 import numpy as np
 import torch
 
 import torchrua_amd as ta
+from torchrua_amd import _lib as L
 from helpers import orc, to_np, to_torch
 
 DEV = torch.device('cuda:0')
@@ -58,3 +63,46 @@ def host_sort(lens) -> np.ndarray:
     """The reference's host call for sorted_indices (core/view.py:48), on THIS machine."""
     t = torch.as_tensor(np.asarray(lens), dtype=torch.long)
     return torch.sort(t, descending=True)[1].numpy()
+
+
+class _Trace:
+    """What dispatch_trace() recorded: `records` (one line each), `kernels` (the template names, in launch order)."""
+
+    def __init__(self):
+        self.records = []
+
+    @property
+    def kernels(self):
+        return [r.split(' ', 1)[0] for r in self.records]
+
+    def matching(self, want: str):
+        """The records of the kernel `want` names that carry every key=value pair of `want`
+        ('seg_reduce_ranks_kernel EPL=8 glog=2')."""
+        name, *pairs = want.split()
+        return [r for r in self.records if r.split(' ', 1)[0] == name and set(pairs) <= set(r.split()[1:])]
+
+
+def _take_trace(lib) -> list:
+    n = lib.rua_debug_trace_take(None, 0)
+    if n <= 0:
+        return []
+    buf = ctypes.create_string_buffer(int(n) + 1)
+    got = lib.rua_debug_trace_take(buf, n + 1)
+    return buf.raw[:got].decode().splitlines()
+
+
+@contextlib.contextmanager
+def dispatch_trace():
+    """Record which reduce kernel templates the dispatchers launch inside the block (rua_debug_trace): every launch, the
+    backward's included (autograd runs it on its own thread; the log is process-global).  Synchronises on the way out,
+    so a record never belongs to work still queued.  The product never switches the trace on."""
+    lib = L.load()
+    _take_trace(lib)                               # whatever an earlier block left behind
+    t = _Trace()
+    prev = lib.rua_debug_trace(1)
+    try:
+        yield t
+    finally:
+        torch.cuda.synchronize()
+        lib.rua_debug_trace(prev)
+        t.records = _take_trace(lib)

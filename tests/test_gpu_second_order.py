@@ -138,3 +138,60 @@ def test_prod_says_that_it_differentiates_once():
     (g,) = torch.autograd.grad((ta.reduce_prod(ta.with_host_sizes(x, lens)) ** 2).sum(), x, create_graph=True)
     with pytest.raises(RuntimeError, match='differentiate once'):
         torch.autograd.grad((g * w).sum(), x)
+
+
+def _stock_logsumexp(x, lens):
+    parts = torch.split(x, lens.tolist())
+    return torch.stack([p.logsumexp(0) for p in parts])
+
+
+@pytest.mark.parametrize('name', ['logsumexp', 'max'])
+def test_strided_payload_twice(name):
+    """A non-contiguous payload (every other column): the Function must save its own input, or the second derivative
+    loses d/d data (logsumexp's Hessian came out as -pp^T instead of diag(p) - pp^T)."""
+    lens, x0, _ = batch(seed=4, H=6)
+    w = torch.randn(x0.shape, generator=torch.Generator().manual_seed(5), dtype=torch.float64).to(DEV)
+
+    def ours(x):
+        return (getattr(ta, f'segment_{name}')(x[:, ::2], lens.to(DEV)) ** 2).sum()
+
+    def stock(x):
+        v = x[:, ::2]
+        r = _stock_logsumexp(v, lens) if name == 'logsumexp' else torch.stack([p.amax(0) for p in torch.split(v, lens.tolist())])
+        return (r ** 2).sum()
+
+    g1, h1 = second(ours, x0.clone().requires_grad_(True), w)
+    g2, h2 = second(stock, x0.clone().requires_grad_(True), w)
+    torch.testing.assert_close(g1, g2, rtol=1e-9, atol=1e-9)
+    torch.testing.assert_close(h1, h2, rtol=1e-9, atol=1e-9)
+
+
+@pytest.mark.parametrize('pad', [1e9, float('inf'), float('nan')])
+@pytest.mark.parametrize('kind', 'LR')
+def test_logsumexp_twice_over_padding(kind, pad):
+    """Padding rows of L / R holding huge values, inf or NaN: the composed gradient (create_graph) and the Hessian-vector
+    product are exactly zero there and match stock torch on the token rows."""
+    lens, x0, w0 = batch(seed=6)
+    c = ta.with_host_sizes(x0, lens)
+    z = c.left(pad) if kind == 'L' else c.right(pad)
+    T = z.data.size(1)
+    b = torch.repeat_interleave(torch.arange(lens.numel()), lens)
+    t = torch.arange(int(lens.sum())) - torch.repeat_interleave(torch.cumsum(lens, 0) - lens, lens)
+    rows = (b * T + (t if kind == 'L' else (T - lens[b]) + t)).to(DEV)
+    live = torch.zeros(lens.numel() * T, dtype=torch.bool, device=DEV)
+    live[rows] = True
+    w = torch.zeros((lens.numel() * T, x0.size(1)), dtype=torch.float64, device=DEV)
+    w[rows] = w0
+
+    def ours(d):
+        cls = ta.L if kind == 'L' else ta.R
+        return (ta.reduce_logsumexp(cls(d, z.token_sizes)) ** 2).sum()
+
+    d = z.data.clone().requires_grad_(True)
+    (g1,) = torch.autograd.grad(ours(d), d, create_graph=True)
+    (h1,) = torch.autograd.grad((g1 * w.view_as(g1)).sum(), d)
+    g1, h1 = g1.detach().flatten(0, 1), h1.flatten(0, 1)
+    assert bool((g1[~live] == 0).all()) and bool((h1[~live] == 0).all()), 'padding rows carry a gradient'
+    g2, h2 = second(lambda x: (_stock_logsumexp(x, lens) ** 2).sum(), x0.clone().requires_grad_(True), w0)
+    torch.testing.assert_close(g1[rows], g2, rtol=1e-9, atol=1e-9)
+    torch.testing.assert_close(h1[rows], h2, rtol=1e-9, atol=1e-9)

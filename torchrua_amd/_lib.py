@@ -87,6 +87,8 @@ SYMBOLS = {
     'rua_host_sort_heap_segments': (c_int64, []),
     'rua_host_batch_sizes': (c_int, [c_void_p, c_int64, c_int64, c_void_p]),
     'rua_host_pack_scans': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    'rua_debug_trace': (c_int, [c_int32]),
+    'rua_debug_trace_take': (c_int64, [c_char_p, c_int64]),
     'rua_abi_version': (c_int, []),
     'rua_build_target': (c_char_p, []),
 }

@@ -260,7 +260,7 @@ class _Reduce(torch.autograd.Function):
             ties = torch.empty((lay.B,) + tuple(hidden), dtype=acc, device=data.device)
         out = launch_reduce(lay, data, op, hidden=hidden, ties_out=ties)
         ctx.lay, ctx.op, ctx.lens, ctx.ties = lay, op, lens, ties
-        ctx.save_for_backward(data.contiguous(), out)
+        ctx.save_for_backward(data, out)      # (reduce() hands a contiguous payload: the saved tensor IS the input)
         return out
 
     @staticmethod
@@ -282,7 +282,10 @@ def _composed_reduce_grad(grad: Tensor, data: Tensor, out: Tensor, lay: M.Lay, o
         return _ReduceBwd.apply(v.contiguous(), data.detach(), out.detach(), lay, L.SUM, None)
 
     if op == L.LOGSUMEXP:
-        return spread(grad) * (data - spread(out)).exp()
+        # padding rows of a padded layout may hold anything (inf, NaN, 1e9): exp(pad - 0) would turn their zero into
+        # NaN, so the exponent is taken on live rows only (0 elsewhere — its gradient there is then exactly 0 as well)
+        live = spread(torch.ones_like(out.detach())) != 0
+        return spread(grad) * torch.where(live, data - spread(out), torch.zeros_like(data)).exp()
     o = spread(out.detach())
     x = data.detach()
     hit = (x == o) | ((x != x) & (o != o))
@@ -333,7 +336,9 @@ class _ReduceBwd(torch.autograd.Function):
 
 def reduce(data: Tensor, lay: M.Lay, op: int, hidden, lens: Optional[Tensor]) -> Tensor:
     if data.requires_grad and torch.is_grad_enabled():
-        return _Reduce.apply(data, lay, op, tuple(hidden), lens)
+        # contiguous HERE, inside the graph: the Function saves its own input, so a second derivative (create_graph)
+        # reaches d/d data through it — a copy made inside forward() would carry no history
+        return _Reduce.apply(data.contiguous(), lay, op, tuple(hidden), lens)
     return launch_reduce(lay, data.detach() if data.requires_grad else data, op, hidden=tuple(hidden))
 
 

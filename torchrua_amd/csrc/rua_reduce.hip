@@ -1,10 +1,26 @@
 // rua_reduce.hip — extern "C" entry points of the reductions; the kernels live in rua_reduce_impl.h and are
 // instantiated per element type in rua_reduce_{f32,bf16,f16,f64}.hip.
 #include <hip/hip_runtime.h>
+#include <string.h>
+#include <atomic>
+#include <deque>
+#include <mutex>
+#include <string>
 #include "rua.h"
 #include "rua_dev.h"
 
 namespace rua {
+// the dispatch trace (rua_debug_trace): process-global — autograd runs the backward on a thread of its own — and
+// bounded, oldest record dropped first
+std::atomic<int> g_trace_on{0};
+static std::mutex g_trace_mu;
+static std::deque<std::string> g_trace_log;
+constexpr size_t TRACE_CAP = 512;
+void trace_add(const char* rec) {
+  std::lock_guard<std::mutex> lk(g_trace_mu);
+  if (g_trace_log.size() >= TRACE_CAP) g_trace_log.pop_front();
+  g_trace_log.emplace_back(rec);
+}
 constexpr int EXTREME_WORDS_ENTRY = RUA_EXTREME_WORDS;     // 1 024 slots, flags, the reset ticket, one spare
 constexpr int BWD_TIES_POSITIVE = 2;      // bit 1 of the kernels' extra_count (rua_reduce_impl.h)
 __global__ void extreme_init_entry_kernel(unsigned long long* ext, int want_max_of_data) {
@@ -33,6 +49,25 @@ int64_t reduce_int_ws_bytes(int64_t n_rows, int64_t H, int64_t split);
 using namespace rua;
 
 extern "C" {
+
+int rua_debug_trace(int32_t on) { return g_trace_on.exchange(on ? 1 : 0, std::memory_order_relaxed); }
+
+int64_t rua_debug_trace_take(char* buf, int64_t cap) {
+  std::lock_guard<std::mutex> lk(g_trace_mu);
+  int64_t n = 0;
+  if (!buf || cap <= 0) {                   // the size of the whole log, left in place
+    for (const std::string& r : g_trace_log) n += (int64_t)r.size() + 1;
+    return n;
+  }
+  while (!g_trace_log.empty() && n + (int64_t)g_trace_log.front().size() + 1 <= cap) {
+    const std::string& r = g_trace_log.front();
+    memcpy(buf + n, r.data(), r.size());
+    n += (int64_t)r.size();
+    buf[n++] = '\n';
+    g_trace_log.pop_front();
+  }
+  return n;
+}
 
 int rua_reduce_team_waves(int64_t n_rows, int64_t B, int64_t row_bytes) {
   // what dispatch_reduce_main decides for an aligned payload whose rows are a multiple of 16 bytes — or of 8 bytes,

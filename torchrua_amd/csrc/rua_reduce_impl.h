@@ -10,7 +10,10 @@
 // Row addressing per layout (include/rua.h): CAT off[b]+t (contiguous), PACK boff[t]+rank[b]
 // (stride varies with t), LEFT/RIGHT b*T+t(+pad), and CAT+perm for the bucketed scatter_*.
 #pragma once
+#include <stdarg.h>
+#include <stdio.h>
 #include <stdlib.h>
+#include <atomic>
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
 #include "rua_dev.h"
@@ -1498,10 +1501,15 @@ __device__ __forceinline__ void fill_empty_body(const rua_layout& L, T* __restri
     const unsigned long long o = __shfl_xor(best, d, RUA_WAVE);
     best = o > best ? o : best;
   }
+  // no slot written: every wave that read rows still held its start value (fold_flags hands nothing over then), so the
+  // data are all -inf (want_max_of_data) or all +inf — the reference's tensor.max() / tensor.min() — and no slot code
+  // is zero (codes of NaN are never stored)
+  const bool untouched = best == 0ull;
   if (!want_max_of_data) best = ~best;
   const bool poison = (flags & 1ull) != 0ull;
   A val;
-  if (sizeof(A) == 8) val = (A)unordered_f64(best); else val = (A)unordered_f32(best);
+  if (untouched) val = want_max_of_data ? -acc_inf<A>() : acc_inf<A>();
+  else if (sizeof(A) == 8) val = (A)unordered_f64(best); else val = (A)unordered_f32(best);
   if (poison) val = val - val + (A)__builtin_nanf("");
   const T tv = elem<T>::down(val);
 
@@ -1626,6 +1634,52 @@ static SplitWs carve_ws(void* ws, int64_t max_u, int64_t split) {
   return W;
 }
 
+// ---- dispatch trace (rua_debug_trace, include/rua.h): the host records which kernel template a dispatcher committed to,
+// one line per launch, named as in this file.  Off: one relaxed load per dispatch.  The log lives in rua_reduce.hip.
+extern std::atomic<int> g_trace_on;
+void trace_add(const char* rec);
+static inline bool tracing() { return g_trace_on.load(std::memory_order_relaxed) != 0; }
+__attribute__((format(printf, 1, 2))) static void trace_fmt(const char* fmt, ...) {
+  char buf[320];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  trace_add(buf);
+}
+template <typename T> static const char* tname();
+template <> const char* tname<float>() { return "f32"; }
+template <> const char* tname<double>() { return "f64"; }
+template <> const char* tname<__hip_bfloat16>() { return "bf16"; }
+template <> const char* tname<__half>() { return "f16"; }
+// the OP template argument the switch below a dispatcher picks (max / min count their ties when `ties` is given)
+static inline const char* op_name(int op, bool ties) {
+  switch (op) {
+    case RUA_SUM: return "sum";
+    case RUA_MEAN: return "mean";
+    case RUA_MAX: return ties ? "max_t" : "max";
+    case RUA_MIN: return ties ? "min_t" : "min";
+    case RUA_PROD: return "prod";
+    case RUA_LOGSUMEXP: return "logsumexp";
+  }
+  return "?";
+}
+template <typename T>
+static void trace_fwd(const char* kern, int epl, int op, bool ties, bool nt, bool copy, int cpw, int wpb, int team,
+                      int glog, int check, bool split, int no_empty) {
+  trace_fmt("%s T=%s EPL=%d OP=%s NT=%d COPY=%d CPW=%d WPB=%d team=%d glog=%d check=%d split=%d no_empty=%d", kern,
+            tname<T>(), epl, op_name(op, ties), nt ? 1 : 0, copy ? 1 : 0, cpw, wpb, team, glog, check, split ? 1 : 0,
+            no_empty);
+}
+
+template <typename T>
+static void trace_bwd(const char* kern, int epl, int op, bool nt, int tv, bool multi_chunk, bool span, bool split,
+                      bool phased, bool ties_final, bool pad_memset) {
+  trace_fmt("%s T=%s EPL=%d OP=%s NT=%d TV=%d chunks=%d span=%d split=%d phased=%d ties_final=%d pad_memset=%d", kern,
+            tname<T>(), epl, op_name(op, false), nt ? 1 : 0, tv, multi_chunk ? 1 : 0, span ? 1 : 0, split ? 1 : 0,
+            phased ? 1 : 0, ties_final ? 1 : 0, pad_memset ? 1 : 0);
+}
+
 template <typename T, int EPL, bool NT, bool COPY, int CPW>
 static int launch_reduce(int op, unsigned grid, hipStream_t s, const rua_layout& L, const int64_t* perm,
                          const void* data, void* out, int64_t H, int lp_log2, int64_t n_chunks, int include_self,
@@ -1654,7 +1708,16 @@ static int launch_reduce(int op, unsigned grid, hipStream_t s, const rua_layout&
   // Rows of at least 512 bytes only: at 16 / 32-byte rows (a whole short sequence per wave instruction) two waves per
   // workgroup lose 7-10 % (final width sweep of round 4: 2.36 -> 2.20, 4.40 -> 3.95 TB/s).
   const int wpb = (COPY || CPW != 1) ? 1 : ((L.kind != RUA_PACK && H * (int64_t)sizeof(T) >= 512) ? 2 : 1);
-#define RUA_LAUNCH(OP)                                                                                              \
+  if (tracing()) {
+    const bool tk = !COPY && ties;
+    trace_fwd<T>("seg_reduce_kernel", EPL, op, tk, NT, COPY, CPW, do_split ? 1 : wpb, 1, 0, 0, do_split, no_empty);
+    if (do_split) {
+      trace_fwd<T>("seg_reduce_tail_kernel", EPL, op, tk, NT, COPY, CPW, 1, 1, 0, 0, true, no_empty);
+      trace_fwd<T>("seg_reduce_combine_kernel", EPL, op, tk, false, COPY, CPW, COMBINE_WAVES_MAX / CPW, 1, 0, 0, true,
+                   no_empty);
+    }
+  }
+#define RUA_LAUNCH(OP)                                                                                             \
   if (do_split) {                                                                                                   \
     hipLaunchKernelGGL((seg_reduce_kernel<T, EPL, OP, NT, COPY, true, CPW>), g, b, 0, s, L, perm, (const T*)data,   \
                        (T*)out, H, lp_log2, n_chunks, include_self, ev, ext, CD, (T*)copy, W, no_empty);            \
@@ -1782,7 +1845,18 @@ static int dispatch_reduce_main(int op, hipStream_t s, const rua_layout& L, cons
       if (e != hipSuccess) return (int)e;
       W.ties = ties;
     }
-#define RUA_RANKS(EPLV, NTV, OPV)                                                                                  \
+    if (tracing()) {
+      const int ntr = vec_ok && nt;
+      trace_fwd<T>("seg_reduce_ranks_kernel", epl, op, ties != nullptr, ntr, false, 1, 1, 1, glog, ranks_check,
+                   ranks_split, no_empty);
+      if (ranks_split) {
+        trace_fwd<T>("seg_reduce_tail_kernel", epl, op, ties != nullptr, ntr, false, 1, 1, 1, glog, ranks_check, true,
+                     no_empty);
+        trace_fwd<T>("seg_reduce_combine_kernel", epl, op, ties != nullptr, false, false, 1, COMBINE_WAVES_MAX, 1, glog,
+                     ranks_check, true, no_empty);
+      }
+    }
+#define RUA_RANKS(EPLV, NTV, OPV)                                                                                 \
   do { if (ranks_split) {                                                                                               \
     if constexpr (EPLV == FULL) {                                                                                  \
       hipLaunchKernelGGL((seg_reduce_ranks_kernel<T, EPLV, OPV, NTV, true>), gg, bb, 0, s, L, (const T*)data, (T*)out, H, \
@@ -1823,7 +1897,9 @@ static int dispatch_reduce_main(int op, hipStream_t s, const rua_layout& L, cons
       const dim3 gg((unsigned)blocks), bb(RUA_WAVE * team);
       unsigned long long* ext = (unsigned long long*)extreme;
       using A = typename elem<T>::acc;
-#define RUA_TEAM(NTV, OPV)                                                                                           \
+      if (tracing())
+        trace_fwd<T>("seg_reduce_team_kernel", FULL, op, ties != nullptr, nt, false, 1, team, team, 0, 0, false, no_empty);
+#define RUA_TEAM(NTV, OPV)                                                                                          \
   hipLaunchKernelGGL((seg_reduce_team_kernel<T, FULL, OPV, NTV>), gg, bb, 0, s, L, perm, (const T*)data, (T*)out, H, \
                      lp_log2, n_chunks, include_self, ev, ext, (A*)ties, no_empty)
 #define RUA_TEAM_OP(NTV)                                                                           \
@@ -1873,7 +1949,7 @@ template <typename T, int EPL>
 static int launch_backward(int op, unsigned grid, hipStream_t s, const rua_layout& L, const int64_t* perm,
                            const void* data, const void* out, const void* gout, void* gin, int64_t H, int lp_log2,
                            int64_t n_chunks, int extra_count, int64_t split, void* ws, void* ties,
-                           bool ties_final, const void* self_in) {
+                           bool ties_final, const void* self_in, bool fill_padding) {
   using A = typename elem<T>::acc;
   const dim3 g(grid), b(RUA_WAVE);
   const T* sp = (const T*)self_in;
@@ -1890,6 +1966,15 @@ static int launch_backward(int op, unsigned grid, hipStream_t s, const rua_layou
     W = carve_ws<A>(ws, max_u, split);
   }
   A* tp = (A*)ties;
+  if (tracing()) {
+    const bool pad = fill_padding && (L.kind == RUA_LEFT || L.kind == RUA_RIGHT);
+    const int tvs[2] = {phased ? (ties_final ? 2 : 1) : 0, 2};
+    for (int k = 0; k < (phased && !ties_final ? 2 : 1); ++k) {
+      trace_bwd<T>("seg_backward_kernel", EPL, op, false, tvs[k], n_chunks > 1, false, do_split, phased, ties_final, pad);
+      if (do_split)
+        trace_bwd<T>("seg_backward_tail_kernel", EPL, op, false, tvs[k], n_chunks > 1, false, true, phased, ties_final, pad);
+    }
+  }
 #define RUA_PHASE(OP, TIESV)                                                                                       \
   {                                                                                                                \
     if (do_split) {                                                                                                \
@@ -1963,6 +2048,8 @@ static int dispatch_backward(int op, hipStream_t s, const rua_layout& L, const i
     const bool nt = (double)L.n_rows * (double)row_bytes >= (double)(512ll << 20);
     const dim3 gg((unsigned)grid), bb(RUA_BLOCK);
     using A = typename elem<T>::acc;
+    if (tracing())
+      trace_bwd<T>("seg_backward_rows_kernel", FULL, op, nt, 0, n_chunks > 1, span, false, false, ties_final, false);
 #define RUA_BROWS(OPV, NTV)                                                                                         \
   if (n_chunks == 1)                                                                                                \
     hipLaunchKernelGGL((seg_backward_rows_kernel<T, FULL, OPV, NTV, false>), gg, bb, 0, s, L, (const T*)data, (const T*)out,  \
@@ -1984,7 +2071,8 @@ static int dispatch_backward(int op, hipStream_t s, const rua_layout& L, const i
     return (int)hipGetLastError();
   }
   // the walk-per-sequence kernels write token rows only: zero the padding rows of a padded layout first when asked to
-  if (fill_padding && (L.kind == RUA_LEFT || L.kind == RUA_RIGHT)) {
+  const bool pad_memset = fill_padding && (L.kind == RUA_LEFT || L.kind == RUA_RIGHT);
+  if (pad_memset) {
     const hipError_t e = hipMemsetAsync(gin, 0, (size_t)L.n_rows * (size_t)H * sizeof(T), s);
     if (e != hipSuccess) return (int)e;
   }
@@ -1995,6 +2083,9 @@ static int dispatch_backward(int op, hipStream_t s, const rua_layout& L, const i
     const int64_t nblk = (L.B + rpw - 1) / rpw;
     if (nblk > 0x7fffffffLL) return RUA_ERANGE;
     const dim3 gg((unsigned)nblk), bb(RUA_WAVE);
+    if (tracing())
+      trace_bwd<T>("seg_backward_ranks_kernel", epl, op, false, ((op == RUA_MAX || op == RUA_MIN) && ties) ? 2 : 0, false,
+                   false, false, false, ties_final, pad_memset);
 #define RUA_BRANKS(EPLV, OPV, TV)                                                                                   \
   hipLaunchKernelGGL((seg_backward_ranks_kernel<T, EPLV, OPV, TV>), gg, bb, 0, s, L, (const T*)data,              \
                      (const T*)out, (const T*)gout, (T*)gin, H, lp_log2, tie_rule, (typename elem<T>::acc*)ties)
@@ -2019,6 +2110,8 @@ static int dispatch_backward(int op, hipStream_t s, const rua_layout& L, const i
     const bool nt = (double)L.n_rows * (double)H * (double)sizeof(T) >= (double)(512ll << 20);
     const dim3 gg((unsigned)blocks), bb(RUA_WAVE);
     using A = typename elem<T>::acc;
+    if (tracing())
+      trace_bwd<T>("seg_backward_walk_kernel", epl, op, nt, 0, n_chunks > 1, false, false, false, ties_final, pad_memset);
 #define RUA_BWALK(EPLV, OPV, NTV)                                                                                   \
   hipLaunchKernelGGL((seg_backward_walk_kernel<T, EPLV, OPV, NTV>), gg, bb, 0, s, L, (const T*)data, (const T*)out,  \
                      (const T*)gout, (T*)gin, H, lp_log2, n_chunks, tie_rule, (const A*)ties)
@@ -2039,12 +2132,12 @@ static int dispatch_backward(int op, hipStream_t s, const rua_layout& L, const i
   }
   if (vec_ok)
     return launch_backward<T, FULL>(op, (unsigned)blocks, s, L, perm, data, out, gout, gin, H, lp_log2, n_chunks,
-                                    extra_count, split, ws, ties, ties_final, self_in);
+                                    extra_count, split, ws, ties, ties_final, self_in, fill_padding);
   if (half_ok)
     return launch_backward<T, HALF>(op, (unsigned)blocks, s, L, perm, data, out, gout, gin, H, lp_log2, n_chunks,
-                                    extra_count, split, ws, ties, ties_final, self_in);
+                                    extra_count, split, ws, ties, ties_final, self_in, fill_padding);
   return launch_backward<T, 1>(op, (unsigned)blocks, s, L, perm, data, out, gout, gin, H, lp_log2, n_chunks, extra_count,
-                               split, ws, ties, ties_final, self_in);
+                               split, ws, ties, ties_final, self_in, fill_padding);
 }
 
 // ---- per-dtype entry points: each element type is compiled in its own translation unit
@@ -2082,6 +2175,12 @@ RUA_DECLARE_REDUCE_DTYPE(f64)
   int fill_empty_##NAME(hipStream_t s, const rua_layout& L, void* out, int64_t H, int want_max, void* ext,        \
                         int reset) {                                                                             \
     /* (the body strides over the batch: a capped grid; in the common case every workgroup reads one flag word) */ \
+    if (tracing()) {                                                                                                \
+      constexpr int VE = 16 / (int)sizeof(T);    /* fill_empty_body's own predicate */                              \
+      const bool wide = (H % VE) == 0 && ((uintptr_t)out & 15) == 0;                                                \
+      trace_fmt("fill_empty_kernel T=%s form=%s want_max=%d reset=%d", tname<T>(),                                  \
+                wide && H / VE <= 8 ? "narrow" : wide ? "ballot" : "ballot_scalar", want_max, reset);               \
+    }                                                                                                               \
     hipLaunchKernelGGL(fill_empty_kernel<T>, dim3(grid_for(L.B) < 2048u ? (grid_for(L.B) ? grid_for(L.B) : 1u) : 2048u), dim3(RUA_BLOCK), 0, s, L, (T*)out, H, want_max,  \
                        (unsigned long long*)ext, reset);                                                           \
     return (int)hipGetLastError();                                                                                  \
