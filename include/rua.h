@@ -163,6 +163,24 @@ int rua_move_rows(const rua_layout* dst, const rua_layout* src, int32_t tmap, in
                   void* dst_data, const void* src_data, int64_t row_bytes,
                   const void* fill16, int64_t pad_row, int32_t flags, void* stream);
 
+/* Backward of a row scatter  rows_of(src)[list] = value  (core/set.py:21-92; torch's index_put_ backward, which the
+ * reference inherits through autograd: a clone, an index_put of zeros and an index gather):
+ *   for every entry j of the LIST layout `list` (M entries), r = the storage row of `src` it names, resolved exactly
+ *   as rua_move_rows(..., RUA_MOVE_SCATTER) resolves it (negative flat rows wrap; a pair that names no token is skipped):
+ *     grad_value[j, :] = grad[r, :]      (zeros for a skipped entry)         if grad_value != NULL
+ *     grad_raw[r, :]   = 0                                                   if grad_raw   != NULL
+ *   and every other row of grad_raw is a copy of the same row of grad.
+ * grad_raw must not alias grad (RUA_EINVAL).  Rows may repeat in the list: every repeat receives the row of `grad`,
+ * and the result does not depend on the order the entries are served in (`grad` is only read, `grad_raw` only written).
+ * With grad_raw != NULL the call is two launches in stream order — the mover's streaming copy of `grad`, then the
+ * gather-and-zero kernel; with grad_raw == NULL the copy does not happen.  flags: 0, or RUA_MOVE_NT_ON / RUA_MOVE_NT_OFF
+ * (default: non-temporal accesses when the larger output is >= 512 MiB, the mover's rule).
+ * Never allocates, never synchronises; like rua_move_rows it accepts any alignment (narrower lanes) and returns the
+ * same codes.  While the dispatch trace is on (below) it records `setitem_backward_copy` and
+ * `setitem_backward_kernel ...`, one line per launch.  Added to ABI 6 (the version number did not move). */
+int rua_setitem_backward(const rua_layout* list, const rua_layout* src, const void* grad, void* grad_value,
+                         void* grad_raw, int64_t row_bytes, int32_t flags, void* stream);
+
 /* ---- reductions ------------------------------------------------------------ */
 enum rua_dtype {
   RUA_F32 = 0, RUA_BF16 = 1, RUA_F16 = 2, RUA_F64 = 3,

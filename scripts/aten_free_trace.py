@@ -1,8 +1,10 @@
 """Which kernels run in forward + backward of indexing, casts, selects and reductions?  Run under
 
-    rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof2_aten -o runc -- python3 scripts/aten_free_trace.py
+    rocprofv3 --kernel-trace --stats --output-format csv -d prof_out/aten_trace -o runc -- python3 scripts/aten_free_trace.py
 
-and condense with `python scripts/aten_free_trace.py --summarize` -> profiles/r02_kernels_fwd_bwd.txt.
+and condense with `python scripts/aten_free_trace.py --summarize [OUT] [--dir DIR] [--timing FILE]` (OUT defaults to
+profiles/r02_kernels_fwd_bwd.txt, DIR to prof_out/aten_trace, as in the command above; FILE — the report of scripts/setitem_grad_ab.py — is
+appended as it is: profiles/kernels_fwd_bwd_setitem.txt is made that way).
 Inputs are drawn on the host and uploaded (copies, not kernels); cotangents are handed to torch.autograd.grad, so the
 only ATen kernels left are the ones the product path itself launches."""
 import csv
@@ -11,16 +13,29 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TRACE_DIR = os.path.join('prof_out', 'aten_trace')           # where the command in the docstring leaves its csv files
 sys.path.insert(0, ROOT)
 
 
+def _arg(flag, default):
+    if flag in sys.argv:
+        i = sys.argv.index(flag)
+        if i + 1 < len(sys.argv) and not sys.argv[i + 1].startswith('--'):
+            return sys.argv[i + 1]
+    return default
+
+
 def summarize():
-    f = glob.glob(os.path.join(ROOT, 'gpurun_out', 'prof2_aten', '**', '*kernel_stats.csv'), recursive=True)[0]
+    out_path = os.path.join(ROOT, _arg('--summarize', os.path.join('profiles', 'r02_kernels_fwd_bwd.txt')))
+    src_dir = os.path.join(ROOT, _arg('--dir', TRACE_DIR))
+    timing = _arg('--timing', None)
+    f = glob.glob(os.path.join(src_dir, '**', '*kernel_stats.csv'), recursive=True)[0]
     rows = list(csv.DictReader(open(f)))
     ours = [r for r in rows if 'rua::' in r['Name']]
     other = [r for r in rows if 'rua::' not in r['Name']]
     out = ['# kernels launched by scripts/aten_free_trace.py (rocprofv3 --kernel-trace --stats): forward + backward of',
-           '# getitem / setitem (tuple, tensor and Z keys), scatter_* x include_self, every cast, roll/rev/last/head/trunc,',
+           '# getitem / setitem (tuple, tensor and Z keys; setitem also as a write autograd records: the value requires grad,',
+           '# the storage is a non-leaf), scatter_* x include_self, every cast, roll/rev/last/head/trunc,',
            '# reduce_* over all four layouts.  "other" = everything that is not a rua:: kernel.', '',
            f'rua:: kernels: {len(ours)} distinct, {sum(int(r["Calls"]) for r in ours)} launches',
            f'other kernels: {len(other)} distinct, {sum(int(r["Calls"]) for r in other)} launches', '', 'other:']
@@ -29,8 +44,12 @@ def summarize():
     out += ['', 'rua:']
     for r in ours:
         out.append(f'  {int(r["Calls"]):5d} x  avg {float(r["AverageNs"]) / 1e3:8.1f} us   {r["Name"].replace("void ", "").split("(")[0][:120]}')
+    bad = [r['Name'] for r in other if 'index_put' in r['Name'] or 'indexing_backward' in r['Name']]
+    out += ['', f'index_put / indexing_backward kernels among "other": {len(bad)}']
     text = '\n'.join(out) + '\n'
-    open(os.path.join(ROOT, 'profiles', 'r02_kernels_fwd_bwd.txt'), 'w').write(text)
+    if timing:
+        text += '\n' + open(os.path.join(ROOT, timing)).read()
+    open(out_path, 'w').write(text)
     print(text)
 
 
@@ -69,6 +88,21 @@ def main():
         grad_of(lambda d: zz[zz.idx()], leaf)                       # Z key
         zz2 = z._replace(data=z.data.detach().clone() if False else z.data.detach())
         zz2[bp, tp] = W[:n]                                         # setitem, tuple key
+        # ... and as a write autograd records: the value requires grad, the storage is a non-leaf
+        base = z.data.detach().requires_grad_()
+        val = W[:n].detach().clone().requires_grad_()
+        zz3 = z._replace(data=base.clone())
+        zz3[bp, tp] = val
+        torch.autograd.grad(zz3.data, [base, val], W[:zz3.data.numel() // H].reshape(zz3.data.shape))
+        val = W[:n].detach().clone().requires_grad_()
+        zz4 = z._replace(data=base.clone())
+        zz4[zz.idx()] = val                                         # Z key (row indices); the storage requires grad
+        # (only d/d value is asked for, but the storage requires grad: the backward computes d/d raw too — copy and zero)
+        torch.autograd.grad(zz4.data, [val], W[:zz4.data.numel() // H].reshape(zz4.data.shape))
+        val = W[:n].detach().clone().requires_grad_()
+        zz5 = z._replace(data=z.data.detach().clone())
+        zz5[bp, tp] = val                                           # value only: a plain storage, no copy in the backward
+        torch.autograd.grad(zz5.data, [val], W[:zz5.data.numel() // H].reshape(zz5.data.shape))
         for name, f in (('cat', lambda q: q.cat()), ('left', lambda q: q.left()), ('pack', lambda q: q.pack()),
                         ('right', lambda q: q.right()), ('roll', lambda q: q.roll(3)), ('rev', lambda q: q.rev()),
                         ('last', lambda q: q.last()), ('head', lambda q: q.head(1)), ('trunc', lambda q: q.trunc((0, 0)))):

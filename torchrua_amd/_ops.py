@@ -429,3 +429,119 @@ def scatter_sum_rows(rows: Tensor, index: Tensor, n_out: int) -> Tensor:
                                             L.stream_ptr(rows.device)), 'rua_segment_reduce')
         return out
     return launch_reduce(lay, rows, L.SUM, perm=perm, hidden=hidden, reference_initial=False, name='scatter')
+
+
+# ------------------------------------------------------------------ a row scatter autograd sees (core/set.py)
+def _prod(shape) -> int:
+    n = 1
+    for d in shape:
+        n *= d
+    return n
+
+
+def setitem_backward(plan: MovePlan, grad: Tensor, hidden: Tuple[int, ...], want_value: bool, want_raw: bool):
+    """rua_setitem_backward for the scatter `plan` describes: (grad_value [M, *hidden] or None, grad_raw or None)."""
+    dev = L.require_device(grad)
+    grad = grad.contiguous()
+    m, n_rows = plan.dst.n_rows, plan.src.n_rows
+    rb = _prod(hidden) * grad.element_size() if n_rows else 0
+    g_value = torch.empty((m,) + hidden, dtype=grad.dtype, device=dev) if want_value else None
+    g_raw = torch.empty_like(grad) if want_raw else None
+    if rb == 0 or (m == 0 and not want_raw):
+        return (g_value.zero_() if want_value and g_value.numel() else g_value), g_raw
+    if _kernel_hook:
+        _kernel_hook(plan.name + '_bwd', True)
+    L.check(L.load().rua_setitem_backward(plan.dst.ref(), plan.src.ref(), L.ptr(grad), L.ptr(g_value), L.ptr(g_raw), rb,
+                                          0, L.stream_ptr(dev)), 'rua_setitem_backward')
+    if _kernel_hook:
+        _kernel_hook(plan.name + '_bwd', False)
+    return g_value, g_raw
+
+
+def _sum_rows(g: Tensor, n_seq: int, per_seq: int, hidden: Tuple[int, ...]) -> Tensor:
+    """[n_seq * per_seq, *hidden] -> [n_seq, *hidden]: the sum over each run of per_seq rows, by the segmented reducer
+    (its split path keeps a long sum deterministic).  Differentiable (the adjoint is the reducer's broadcast)."""
+    lay = M.lay_cat(None, n_seq, n_seq * per_seq, len_add=per_seq)
+    return reduce(g.reshape((n_seq * per_seq,) + hidden), lay, L.SUM, hidden, None)
+
+
+def _sum_to_value(g: Tensor, lead: Tuple[int, ...], hidden: Tuple[int, ...], vshape: Tuple[int, ...]) -> Tensor:
+    """The adjoint of broadcasting `value` [vshape] to [*lead, *hidden], applied to g [M, *hidden].  A broadcast along
+    the ROWS is summed by the library's reducer; what remains is a broadcast inside a row (sum_to_size)."""
+    full = tuple(lead) + tuple(hidden)
+    if tuple(vshape) == full:
+        return g.reshape(vshape)
+    k = len(lead)
+    v = (1,) * (len(full) - len(vshape)) + tuple(vshape)
+    summed = [i for i in range(k) if v[i] == 1 and lead[i] != 1]
+    live = [i for i in range(k) if lead[i] != 1]
+    g = g.reshape(full)
+    if summed and g.numel():
+        cut = len(summed)
+        if summed == live[:cut]:              # a leading run of row dims ([H], [1, H], 0-d ...): ONE sequence per kept row
+            keep = tuple(lead[i] for i in live[cut:])
+            rest = keep + tuple(hidden)
+            g = _sum_rows(g, 1, _prod(lead) // _prod(keep), rest)
+            g = g.reshape(tuple(1 if i in summed else lead[i] for i in range(k)) + tuple(hidden))
+        elif summed == live[len(live) - cut:]:  # a trailing run of row dims: one sequence per leading row
+            n_seq = _prod(lead[i] for i in live[:len(live) - cut])
+            g = _sum_rows(g, n_seq, _prod(lead) // n_seq, tuple(hidden))
+            g = g.reshape(tuple(1 if i in summed else lead[i] for i in range(k)) + tuple(hidden))
+        # (row dims broadcast in the middle of others: left to sum_to_size below)
+    return g.sum_to_size(vshape) if tuple(g.shape) != tuple(vshape) else g
+
+
+class _ScatterRows(torch.autograd.Function):
+    """rows_of(raw)[key] = value, in place, recorded by autograd (core/set.py:21-92).  Forward: the row mover in scatter
+    mode into `raw` itself (mark_dirty).  Backward: rua_setitem_backward — one index resolution serves the gather of
+    d/d value and the zeroing of d/d raw.  `value` arrives in its own shape and is broadcast HERE, so that the sum over
+    broadcast rows is the library's reducer, not the backward of an ATen expand.
+    What the backward computes follows `ctx.needs_input_grad`, i.e. which inputs REQUIRE grad, not which gradients the
+    caller asked for: with a storage that requires grad, `torch.autograd.grad(out, [value])` still pays the copy and the
+    zeroing of d/d raw, and the engine drops the result.  Only a storage that does not require grad skips them.
+    `flat_fn` is kept on the node of the written storage, so it must not reference that storage (or a container that
+    holds it): that would be a reference cycle only Python's cyclic collector frees."""
+
+    @staticmethod
+    def forward(ctx, raw: Tensor, value: Tensor, plan: MovePlan, lead: Tuple[int, ...], flat_fn, row_dims: int = 1):
+        hidden = tuple(raw.shape[row_dims:])       # (the first row_dims dims of raw enumerate its storage rows)
+        ctx.row_dims = row_dims
+        ctx.plan, ctx.lead, ctx.hidden, ctx.flat_fn = plan, tuple(lead), hidden, flat_fn
+        ctx.vshape = tuple(value.shape)
+        ctx.save_for_backward(*[t for t in plan.dst.keep if t is not None])    # (saved: autograd checks the keys' versions)
+        m = plan.dst.n_rows
+        if m and plan.src.n_rows:
+            rows = value.detach().expand(tuple(lead) + hidden).reshape((m,) + hidden)
+            launch_move(plan, rows, out=raw.detach())
+        ctx.mark_dirty(raw)
+        return raw
+
+    @staticmethod
+    def backward(ctx, grad: Tensor):
+        _ = ctx.saved_tensors                   # raises if a key tensor was modified in place since the forward
+        plan = ctx.plan
+        want_raw, want_value = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if torch.is_grad_enabled() and grad.requires_grad:
+            # a graph of this backward is being recorded (create_graph=True): torch's setitem differentiates any number of
+            # times, so here the two gradients are spelled with differentiable pieces of the library — the row gather
+            # (whose adjoint is the scatter-sum) and this very Function with the value 0 — and the recursion gives every order
+            g_value = g_raw = None
+            if want_value:
+                n_rows = plan.src.n_rows
+                rows = gather_rows(grad.reshape((n_rows,) + ctx.hidden), ctx.flat_fn().reshape(-1))
+                g_value = _sum_to_value(rows, ctx.lead, ctx.hidden, ctx.vshape)
+            if want_raw:
+                zero = torch.zeros((), dtype=grad.dtype, device=grad.device)
+                g_raw = _ScatterRows.apply(grad.clone(), zero, plan, ctx.lead, ctx.flat_fn, ctx.row_dims)
+            return g_raw, g_value, None, None, None, None
+        g_value, g_raw = setitem_backward(plan, grad.detach(), ctx.hidden, want_value, want_raw)
+        if want_value:
+            with torch.no_grad():
+                g_value = _sum_to_value(g_value, ctx.lead, ctx.hidden, ctx.vshape)
+        return g_raw, g_value, None, None, None, None
+
+
+def scatter_rows(raw: Tensor, value: Tensor, plan: MovePlan, lead: Sequence[int], flat_fn, row_dims: int = 1) -> None:
+    """The write of `_ScatterRows`; `flat_fn()` -> the non-negative flat storage rows of the keys (rows >= n_rows for a
+    key that names no token), only asked for when a second derivative is taken."""
+    _ScatterRows.apply(raw, value, plan, tuple(lead), flat_fn, row_dims)

@@ -283,9 +283,13 @@ def _is_ptr_pair(key) -> bool:
 def _flat_rows(z: Z, key: Tuple[Tensor, Tensor]) -> Tensor:
     """Flat storage rows of (batch_ptr, token_ptr) — core/get.py:25-26, 41-42, 57-58, 73-74 —
     produced by the mover itself (moving an iota of the storage)."""
-    n_rows = describe(z).n_rows
-    iota = _iota(n_rows, z.data.device)
-    return O.launch_move(O.MovePlan(M.lay_list(*key), describe(z), (key[0].numel(),), name='flat_rows'), iota)
+    return _flat_rows_of(describe(z), key, z.data.device)
+
+
+def _flat_rows_of(lay: M.Lay, key: Tuple[Tensor, Tensor], dev: torch.device, missing: int = 0) -> Tensor:
+    """... from the storage's layout alone (no reference to the payload); `missing` for a pair that names no token."""
+    iota = _iota(lay.n_rows, dev)
+    return O.launch_move(O.MovePlan(M.lay_list(*key), lay, (key[0].numel(),), fill=missing, name='flat_rows'), iota)
 
 
 def _iota(n: int, dev: torch.device) -> Tensor:
@@ -328,8 +332,28 @@ def _gather_flat(raw: Tensor, index: Tensor) -> Tensor:
 def _needs_autograd(raw: Tensor, value) -> bool:
     """Would torch record this in-place write?  (the mover writes into raw.detach(); a gradient to `value`
     or through a non-leaf `raw` would be dropped, a leaf that requires grad would be overwritten without torch's
-    error.)  Such writes take torch's own setitem — what the reference does (core/set.py:10-18)."""
+    error.)  Such writes go through `_ops._ScatterRows`, which autograd records (core/set.py:10-18)."""
     return torch.is_grad_enabled() and (raw.requires_grad or (isinstance(value, Tensor) and value.requires_grad))
+
+
+def _is_leaf_write(raw: Tensor) -> bool:
+    """An in-place write torch refuses: `raw` is a leaf that requires grad, or a view of one.  (The Function's own
+    mark_dirty check would raise too, but only after the forward has written.)"""
+    if not raw.requires_grad:
+        return False
+    base = raw._base if raw._is_view() else None
+    return raw.is_leaf or (base is not None and base.is_leaf and base.requires_grad)
+
+
+def _autograd_value(raw: Tensor, value, full: Tuple[int, ...]) -> Tensor:
+    """`value` as the Function takes it: a tensor of raw's dtype on raw's device, in its OWN shape (the cast is
+    differentiable, so autograd undoes it; the broadcast happens inside the Function)."""
+    if not isinstance(value, Tensor):
+        return torch.as_tensor(value, dtype=raw.dtype, device=raw.device)
+    value = value.to(device=raw.device, dtype=raw.dtype)
+    while value.dim() > len(full) and value.size(0) == 1:          # torch's setitem drops leading 1s of the value
+        value = value.squeeze(0)
+    return value
 
 
 def _written(raw: Tensor) -> None:
@@ -342,11 +366,18 @@ def _written(raw: Tensor) -> None:
 def _scatter_flat(raw: Tensor, index: Tensor, value) -> None:
     """raw[index] = value (core/set.py:30,45,67,82) via the mover in scatter mode."""
     rows = _row_index(index, int(raw.size(0)))
-    if rows is None or not raw.is_contiguous() or _needs_autograd(raw, value):
-        _tensor_setitem(raw, index, value)
+    if rows is None or not raw.is_contiguous() or (_needs_autograd(raw, value) and _is_leaf_write(raw)):
+        _tensor_setitem(raw, index, value)       # (not a row index / strided storage / a write torch refuses: its error)
         return
     index = rows
     flat = index.reshape(-1)
+    if _needs_autograd(raw, value):
+        n_rows = int(raw.size(0))
+        plan = O.MovePlan(M.lay_list(None, flat), M.lay_flat(n_rows), raw.shape, flags=K.MOVE_SCATTER, name='scatter_flat')
+        full = tuple(index.shape) + tuple(raw.shape[1:])
+        O.scatter_rows(raw, _autograd_value(raw, value, full), plan, tuple(index.shape),
+                       lambda: torch.where(flat < 0, flat + n_rows, flat))
+        return
     value = torch.as_tensor(value, dtype=raw.dtype, device=raw.device)
     value = value.detach().expand(tuple(index.shape) + tuple(raw.shape[1:])).contiguous()
     plan = O.MovePlan(M.lay_list(None, flat), M.lay_flat(int(raw.size(0))), raw.shape, flags=K.MOVE_SCATTER,
@@ -386,8 +417,18 @@ def _setitem(cls):
                 raise K.RuaError('__setitem__ needs contiguous storage')
             hidden = _hidden(self)
             if _needs_autograd(self.data, value):
-                # autograd has to see the write: torch's own setitem on the flat rows the kernels compute
-                _tensor_setitem(self.raw(), _flat_rows(self, (bp, tp)), value)
+                # autograd has to see the write: the same scatter, recorded (_ops._ScatterRows)
+                if _is_leaf_write(self.data):
+                    _tensor_setitem(self.raw(), _flat_rows(self, (bp, tp)), value)      # torch's own error
+                    return None
+                src, dev = describe(self), self.data.device
+                plan = O.MovePlan(M.lay_list(bp, tp), src, self.data.shape, flags=K.MOVE_SCATTER, name='setitem')
+                lead = tuple(key[0].shape)
+                # (the closure lives on the autograd node of the written storage: it must not hold the container or the
+                # storage itself — that would be a reference cycle through 17 GiB — only the layout, the keys, the device)
+                O.scatter_rows(self.data, _autograd_value(self.data, value, lead + hidden), plan, lead,
+                               lambda: _flat_rows_of(src, (bp, tp), dev, missing=src.n_rows),
+                               len(self.data.shape) - len(hidden))
                 return None
             value = torch.as_tensor(value, dtype=self.data.dtype, device=self.data.device)
             value = value.detach().expand((bp.numel(),) + hidden).contiguous()

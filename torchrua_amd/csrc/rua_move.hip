@@ -12,7 +12,10 @@
 // Tiles are contiguous in the DESTINATION storage, so stores are perfectly coalesced and every
 // tile carries the same number of bytes (no ragged load imbalance); loads are row-granular
 // gathers (>= 128 B lines, 1 KiB at the north-star shape).
+#include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
+#include <atomic>
 #include "rua_dev.h"
 
 namespace rua {
@@ -1468,4 +1471,189 @@ extern "C" int rua_move_rows(const rua_layout* dst, const rua_layout* src, int32
   }
   return nt ? launch_move<false, true>(vec, nr, s, *dst, *src, tmap, tmap_arg, d, c, row_bytes, fp, pad_row, narrow_same_pack, tile_rows, xcd_span, tail8)
             : launch_move<false, false>(vec, nr, s, *dst, *src, tmap, tmap_arg, d, c, row_bytes, fp, pad_row, narrow_same_pack, tile_rows, xcd_span, tail8);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Backward of a row scatter  rows_of(src)[list] = value  (rua_setitem_backward, include/rua.h): gather-and-zero.
+// A wave takes 64 consecutive list entries; each lane resolves ONE of them into a storage row of `src` with the mover's own
+// resolve_wave_rows<true> (a LIST layout takes none of its cooperative searches: every lane reads its own pair and maps it —
+// exactly the rows the scatter wrote, -1 for an entry that names no token); then the wave walks the 64 rows, UNR row groups in
+// flight, the rows handed from lane to lane by shuffles (no LDS, no barrier).  Per entry j with row r:
+//   grad_value[j] = grad[r] (zeros when r < 0)      and      grad_raw[r] = 0.
+// `grad` is only read and `grad_raw` only written, so repeated rows are race-free (two lanes may store the same zeros)
+// and the result does not depend on the order of the waves.  The stores to grad_value are contiguous per wave (64 rows).
+namespace rua {
+
+extern std::atomic<int> g_trace_on;        // the dispatch trace (rua_reduce.hip)
+void trace_add(const char* rec);
+
+constexpr int SETITEM_BWD_UNROLL = 4;
+
+template <int VEC, bool NT, bool TAIL8>
+__global__ __launch_bounds__(RUA_BLOCK) void setitem_backward_kernel(rua_layout D, rua_layout S,
+                                                                     const char* __restrict__ grad,
+                                                                     char* __restrict__ gval, char* __restrict__ graw,
+                                                                     int64_t row_bytes, int64_t lpr, int lp_log2, int cpr) {
+  using V = typename vec_of<VEC>::type;
+  constexpr int UNR = SETITEM_BWD_UNROLL;
+  const int lane = threadIdx.x & (RUA_WAVE - 1);
+  const int64_t wave_id = ((int64_t)blockIdx.x * RUA_BLOCK + threadIdx.x) >> 6;
+  const int64_t jw0 = wave_id * RUA_WAVE;
+  const int64_t left = D.n_rows - jw0;
+  if (left <= 0) return;                                             // wave-uniform
+  const int nw = left < RUA_WAVE ? (int)left : RUA_WAVE;
+  const int64_t mine = resolve_wave_rows<true>(D, S, RUA_T_SHIFT, 0, -1, jw0, nw, lane, false);
+
+  const int rpw = RUA_WAVE >> lp_log2;           // rows per wave instruction
+  const int rsub = lane >> lp_log2;              // which of those rows this lane serves
+  const int64_t col0 = lane & ((1 << lp_log2) - 1);
+  const V zero = fill_of<VEC>(make_uint4(0, 0, 0, 0));
+  for (int g0 = 0; g0 * rpw < nw; g0 += UNR) {                       // wave-uniform trip counts: every lane shuffles
+    int64_t row[UNR];
+    int ent[UNR];
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      const int e = (g0 + u) * rpw + rsub;
+      const int64_t r = __shfl(mine, e & (RUA_WAVE - 1), RUA_WAVE);
+      ent[u] = e < nw ? e : -1;
+      row[u] = e < nw ? r : -1;
+    }
+    for (int c = 0; c < cpr; ++c) {
+      const int64_t col = col0 + (int64_t)c * RUA_WAVE;
+      if (col >= lpr) continue;
+      const bool last8 = TAIL8 && col == lpr - 1;                    // the row's last, 8-byte piece
+      V val[UNR];
+#pragma unroll
+      for (int u = 0; u < UNR; ++u) {
+        val[u] = zero;
+        if (ent[u] >= 0 && row[u] >= 0 && gval) {
+          const char* p = grad + row[u] * row_bytes + col * VEC;
+          if constexpr (TAIL8) {
+            if (last8) {
+              const u32x2 h = ld_row<u32x2, NT>(p);
+              const u32x4 v2 = {h.x, h.y, 0u, 0u};
+              val[u] = v2;
+            } else {
+              val[u] = ld_row_a8<NT>(p);
+            }
+          } else {
+            val[u] = ld_row<V, NT>(p);
+          }
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < UNR; ++u) {
+        if (ent[u] < 0) continue;
+        if (gval) {
+          char* p = gval + (jw0 + ent[u]) * row_bytes + col * VEC;
+          if constexpr (TAIL8) {
+            if (last8) { u32x2 h = {val[u].x, val[u].y}; st_row<u32x2, NT>(p, h); }
+            else st_row_a8<NT>(p, val[u]);
+          } else {
+            st_row<V, NT>(p, val[u]);
+          }
+        }
+        if (graw && row[u] >= 0) {
+          char* p = graw + row[u] * row_bytes + col * VEC;
+          if constexpr (TAIL8) {
+            if (last8) { u32x2 h = {0u, 0u}; st_row<u32x2, NT>(p, h); }
+            else st_row_a8<NT>(p, zero);
+          } else {
+            st_row<V, NT>(p, zero);
+          }
+        }
+      }
+    }
+  }
+}
+
+template <bool NT>
+static int launch_setitem_backward(int vec, bool tail8, hipStream_t s, const rua_layout& D, const rua_layout& S,
+                                   const char* grad, char* gval, char* graw, int64_t row_bytes) {
+  if (tail8) vec = 16;
+  const int64_t lpr = (row_bytes + vec - 1) / vec;
+  int lp_log2 = 0;
+  while ((1 << lp_log2) < lpr && lp_log2 < 6) ++lp_log2;
+  const int cpr = (int)((lpr + RUA_WAVE - 1) / RUA_WAVE);
+  const int64_t waves = (D.n_rows + RUA_WAVE - 1) / RUA_WAVE;
+  const int64_t grid = (waves + RUA_WAVES_PER_BLOCK - 1) / RUA_WAVES_PER_BLOCK;
+  if (grid > 0x7fffffffLL) return RUA_ERANGE;
+  const dim3 g((unsigned)grid), b(RUA_BLOCK);
+  if (g_trace_on.load(std::memory_order_relaxed)) {
+    char rec[160];
+    snprintf(rec, sizeof rec, "setitem_backward_kernel VEC=%d NT=%d TAIL8=%d value=%d raw=%d", vec, (int)NT, (int)tail8,
+             gval != nullptr, graw != nullptr);
+    trace_add(rec);
+  }
+#define RUA_LAUNCH_S(VEC, T8) \
+  hipLaunchKernelGGL((setitem_backward_kernel<VEC, NT, T8>), g, b, 0, s, D, S, grad, gval, graw, row_bytes, lpr, lp_log2, cpr)
+  if (tail8) { RUA_LAUNCH_S(16, true); return (int)hipGetLastError(); }
+  switch (vec) {
+    case 16: RUA_LAUNCH_S(16, false); break;
+    case 8:  RUA_LAUNCH_S(8, false); break;
+    case 4:  RUA_LAUNCH_S(4, false); break;
+    case 2:  RUA_LAUNCH_S(2, false); break;
+    default: RUA_LAUNCH_S(1, false); break;
+  }
+#undef RUA_LAUNCH_S
+  return (int)hipGetLastError();
+}
+
+// `nbytes` from src to dst through the row mover's own streaming geometry: the bytes seen as ONE sequence of 1-KiB rows
+// (what C.roll(0) launches at the north-star shape: 16-row tiles in destination order, an XCD span on big launches),
+// and the last, shorter piece as a row of its own.
+constexpr int64_t COPY_ROW_BYTES = 1024;
+static int stream_copy(void* dst, const void* src, int64_t nbytes, void* stream) {
+  auto flat = [](int64_t rows) {
+    rua_layout L;
+    memset(&L, 0, sizeof L);
+    L.kind = RUA_LEFT; L.n_rows = rows; L.B = 1; L.T_phys = rows; L.T_log = rows; L.len_add = rows;
+    return L;
+  };
+  const int64_t rows = nbytes / COPY_ROW_BYTES, tail = nbytes - rows * COPY_ROW_BYTES;
+  if (rows > 0) {
+    const rua_layout L = flat(rows);
+    const int e = rua_move_rows(&L, &L, RUA_T_SHIFT, 0, dst, src, COPY_ROW_BYTES, nullptr, -1, 0, stream);
+    if (e) return e;
+  }
+  if (tail > 0) {
+    const rua_layout L = flat(1);
+    return rua_move_rows(&L, &L, RUA_T_SHIFT, 0, (char*)dst + rows * COPY_ROW_BYTES,
+                         (const char*)src + rows * COPY_ROW_BYTES, tail, nullptr, -1, 0, stream);
+  }
+  return 0;
+}
+
+}  // namespace rua
+
+extern "C" int rua_setitem_backward(const rua_layout* list, const rua_layout* src, const void* grad, void* grad_value,
+                                    void* grad_raw, int64_t row_bytes, int32_t flags, void* stream) {
+  int e;
+  if (!list || list->kind != RUA_LIST) return RUA_EINVAL;
+  if ((e = check_layout(list, true)) != 0) return e;
+  if ((e = check_layout(src, false)) != 0) return e;
+  if (row_bytes < 0 || (flags & ~(RUA_MOVE_NT_ON | RUA_MOVE_NT_OFF)) != 0) return RUA_EINVAL;
+  if (grad_raw && grad_raw == grad) return RUA_EINVAL;
+  if (!grad && list->n_rows > 0) return RUA_EINVAL;
+  if (row_bytes == 0 || (!grad_value && !grad_raw)) return 0;
+  if (grad_raw && src->n_rows > 0) {
+    // every row nobody names is a copy of the same row of `grad`: the streaming copy first, the named rows are zeroed behind it
+    if (!grad) return RUA_EINVAL;
+    if ((double)src->n_rows * (double)row_bytes >= 9.0e18) return RUA_ERANGE;
+    if (g_trace_on.load(std::memory_order_relaxed)) trace_add("setitem_backward_copy");
+    if ((e = stream_copy(grad_raw, grad, src->n_rows * row_bytes, stream)) != 0) return e;
+  }
+  if (list->n_rows == 0) return 0;
+
+  // widest power-of-two access that divides the row size and all three base addresses (the mover's rule)
+  const uint64_t mix = (uint64_t)row_bytes | (uint64_t)(uintptr_t)grad | (uint64_t)(uintptr_t)grad_value |
+                       (uint64_t)(uintptr_t)grad_raw | 16u;
+  const int vec = (int)(mix & (~mix + 1));
+  const bool tail8 = vec == 8 && (row_bytes & 15) == 8 && row_bytes >= 24;
+  const int64_t dst_rows = grad_raw && src->n_rows > list->n_rows ? src->n_rows : list->n_rows;
+  const bool big = (double)dst_rows * (double)row_bytes >= (double)(512ll << 20);
+  const bool nt = (flags & RUA_MOVE_NT_ON) ? true : (flags & RUA_MOVE_NT_OFF) ? false : big;
+  hipStream_t s = (hipStream_t)stream;
+  return nt ? launch_setitem_backward<true>(vec, tail8, s, *list, *src, (const char*)grad, (char*)grad_value, (char*)grad_raw, row_bytes)
+            : launch_setitem_backward<false>(vec, tail8, s, *list, *src, (const char*)grad, (char*)grad_value, (char*)grad_raw, row_bytes);
 }
