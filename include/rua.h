@@ -316,6 +316,44 @@ int rua_scatter_self_grad(const int64_t* counts, int64_t S, int64_t H, const voi
                           const void* grad_out, const void* aux, void* grad_self, int32_t dtype, int32_t op,
                           int32_t include_self, void* stream);
 
+/* Per-sequence softmax / log_softmax (an EXTENSION, added to ABI 6 — the version number did not move: the reference
+ * spells it as segment_logsumexp, reduce.py:56-61, followed by repeat_interleave, a subtraction and an exp over [N, H]
+ * temporaries, for a CattedSequence only).  For every sequence b of `lay` (ANY layout) and column h, over t < len[b]:
+ *   log == 0:  out[row(b,t), h] = exp(data[row(b,t), h] - lse[b,h])      lse[b,h] = logsumexp_t data[row(b,t), h]
+ *   log != 0:  out[row(b,t), h] =     data[row(b,t), h] - lse[b,h]
+ * i.e. torch.softmax(seq, dim=0) / torch.log_softmax(seq, dim=0) of every sequence on its own, NaN included: a column
+ * of a sequence that holds NaN or +inf, or only -inf, is NaN throughout, and stays inside its sequence and column (no
+ * global `initial`, no `extreme` scratch, no rua_fill_empty).  fp32 accumulation (fp64 for RUA_F64), every output
+ * element rounded once; RUA_F32 / RUA_BF16 / RUA_F16 / RUA_F64 (integer dtypes: RUA_EINVAL).  An empty sequence owns no
+ * row of CAT / PACK: nothing is written for it.  Padding rows of a LEFT / RIGHT result are written as zeros in the same
+ * pass (no pre-zeroing) and padding rows of the input are never read.
+ * The fold order of a (sequence, column) — blocks of 2 048 tokens in order; inside a block 32 interleaved chains joined
+ * by a butterfly — depends on NOTHING but the sequence's length: not on the layout, the kernel form, the alignment or
+ * `ws`.  The operator therefore commutes with the casts BIT FOR BIT: cat(softmax(z)) == softmax(cat(z)) etc.
+ * Three kernel forms by row width and lengths: rows of one vector (<= 16 bytes) put consecutive tokens on consecutive
+ * lanes, two sequences per wave; wider rows give a workgroup per (sequence x 128-byte column chunk), which keeps the
+ * slab in LDS between the fold and the rewrite when the sequence has at most 512 rows (backward: 256) and otherwise walks
+ * global memory twice; few but long sequences (fewer than 1 024 units whose length bound — CAT: T_log or n_rows, LEFT /
+ * RIGHT: T_phys, PACK: T — is at least 8 192) are cut into their blocks across workgroups when `ws` is given:
+ * rua_softmax_ws_bytes(lay, H, dtype) bytes (0 = never needed; ws == NULL = do not cut).  Two launches then.
+ * A CAT layout's T_log, where it is given (> 0), must be a TRUE upper bound of every length: the cut form sizes `ws` and
+ * its grid from it, and never touches `ws` or rows beyond that bound, so tokens of a longer sequence past
+ * ceil(T_log / 2 048) blocks would be left unwritten.  T_log == 0 (unknown) is always safe: the bound is then n_rows.
+ * `out` may equal `data` (every row is read before it is written, by the same wave or workgroup).  Any alignment is
+ * accepted (narrower accesses).  While the dispatch trace is on (below) every launch records
+ * `seg_softmax_lanes_kernel`, `seg_softmax_resident_kernel` or `seg_softmax_stream_kernel` (cut=1 phase=partial|finish for
+ * the cut form) with key=value pairs. */
+int64_t rua_softmax_ws_bytes(const rua_layout* lay, int64_t H, int32_t dtype);
+int rua_segment_softmax(const rua_layout* lay, const void* data, void* out, int64_t H, int32_t dtype, int32_t log,
+                        void* ws, void* stream);
+/* Its backward, from the forward's OUTPUT y alone:
+ *   log == 0:  grad_in = y * (g - s),        s[b,h] = sum_t g * y
+ *   log != 0:  grad_in = g - exp(y) * s,     s[b,h] = sum_t g
+ * the sums in the forward's fold order; padding rows of grad_in are written as zeros.  grad_in may equal grad_out; y must
+ * not alias grad_in (RUA_EINVAL).  Same forms, same `ws`; the trace names are `seg_softmax_backward_lanes_kernel` etc. */
+int rua_segment_softmax_backward(const rua_layout* lay, const void* y, const void* grad_out, void* grad_in, int64_t H,
+                                 int32_t dtype, int32_t log, void* ws, void* stream);
+
 /* After rua_segment_reduce / rua_pack_reduce with `extreme` (MAX/MIN/LOGSUMEXP): write the
  * global extreme — the reduce left it in the scratch — into the rows of empty sequences, or NaN into every row when
  * the NaN flag is up (the reference's initial=NaN behaviour).  Every workgroup patches its share of the batch.

@@ -20,8 +20,9 @@ from torch import Tensor
 from importlib import import_module as _im
 
 # (import_module, not `from torchrua_amd import x`: the package attribute `compose` is the FUNCTION, as in the reference)
-_compose_mod, _core, _detach, _layout, _mask_mod, _reduce, _segment, _select, _utils = (
-    _im(f'torchrua_amd.{m}') for m in ('compose', 'core', 'detach', 'layout', 'mask', 'reduce', 'segment', 'select', 'utils'))
+_compose_mod, _core, _detach, _layout, _mask_mod, _reduce, _segment, _select, _utils, _softmax_mod = (
+    _im(f'torchrua_amd.{m}') for m in ('compose', 'core', 'detach', 'layout', 'mask', 'reduce', 'segment', 'select', 'utils',
+                                       'softmax'))
 from torchrua_amd.layout import C, L, P, R, T, Z, CattedSequence, LeftAlignedSequence, RightAlignedSequence, PackedSequence
 
 _PKG = 'torchrua_amd'
@@ -112,7 +113,8 @@ def build(pkg) -> None:
     _fill(_detach, DETACH)
     _fill(_utils, UTILS)
     _fill(_compose_mod, dict(invert_permutation=_utils.invert_permutation, List=List))
-    for mod in (_compose_mod, _core, _detach, _layout, _mask_mod, _reduce, _segment, _select, _utils):
+    # (softmax.py — like `compose`, the package attribute `softmax` is the FUNCTION: an extension the reference lacks)
+    for mod in (_compose_mod, _core, _detach, _layout, _mask_mod, _reduce, _segment, _select, _utils, _softmax_mod):
         _fill(mod, _TYPES)
     # the package itself: every public name of every submodule (torchrua/__init__.py:1-8), then the submodules
     for table in (CAST, GET, SET, VIEW, NEW, HEAD, LAST, REV, ROLL, TRUNC, SEG, MASK, DETACH, PACK, LAY_CAT,

@@ -342,6 +342,108 @@ def reduce(data: Tensor, lay: M.Lay, op: int, hidden, lens: Optional[Tensor]) ->
     return launch_reduce(lay, data.detach() if data.requires_grad else data, op, hidden=tuple(hidden))
 
 
+# ------------------------------------------------------------------ per-sequence softmax / log_softmax (an extension)
+def _softmax_args(lay: M.Lay, data: Tensor, hidden):
+    dev = L.require_device(data)
+    if data.dtype not in L.DTYPES:
+        raise L.RuaError(f'softmax / log_softmax support {list(L.DTYPES)}; got {data.dtype}')
+    H = _prod(hidden)
+    lib = L.load()
+    nbytes = lib.rua_softmax_ws_bytes(lay.ref(), H, L.DTYPES[data.dtype])      # > 0: few but long sequences get cut
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    return dev, lib, H, ws
+
+
+def launch_softmax(lay: M.Lay, data: Tensor, log: bool, hidden: Tuple[int, ...], out: Optional[Tensor] = None) -> Tensor:
+    """rua_segment_softmax: one launch (two for cut sequences), no [N, H] temporary.  `out` may be `data` itself."""
+    dev, lib, H, ws = _softmax_args(lay, data, hidden)
+    data = data.contiguous()
+    if out is None:
+        out = torch.empty(data.shape, dtype=data.dtype, device=dev)      # padding rows: zeroed by the call
+    elif not out.is_contiguous() or out.dtype != data.dtype or out.shape != data.shape:
+        raise L.RuaError('softmax target must be contiguous, of the payload dtype and of the payload shape')
+    name = 'log_softmax' if log else 'softmax'
+    if _kernel_hook:
+        _kernel_hook(name, True)
+    L.check(lib.rua_segment_softmax(lay.ref(), L.ptr(data), L.ptr(out), H, L.DTYPES[data.dtype], int(bool(log)),
+                                    L.ptr(ws), L.stream_ptr(dev)), 'rua_segment_softmax')
+    if _kernel_hook:
+        _kernel_hook(name, False)
+    return out
+
+
+def launch_softmax_backward(lay: M.Lay, y: Tensor, grad: Tensor, log: bool, hidden: Tuple[int, ...],
+                            out: Optional[Tensor] = None) -> Tensor:
+    """rua_segment_softmax_backward: the gradient from the forward's output alone.  `out` may be `grad` itself."""
+    dev, lib, H, ws = _softmax_args(lay, y, hidden)
+    L.require_device(grad)
+    if grad.dtype != y.dtype or grad.shape != y.shape:
+        raise L.RuaError('softmax backward: the cotangent must have the dtype and shape of the output')
+    y, grad = y.contiguous(), grad.contiguous()
+    if out is None:
+        out = torch.empty(y.shape, dtype=y.dtype, device=dev)
+    elif not out.is_contiguous() or out.dtype != y.dtype or out.shape != y.shape:
+        raise L.RuaError('softmax backward target must be contiguous, of the payload dtype and of the payload shape')
+    name = 'log_softmax_bwd' if log else 'softmax_bwd'
+    if _kernel_hook:
+        _kernel_hook(name, True)
+    L.check(lib.rua_segment_softmax_backward(lay.ref(), L.ptr(y), L.ptr(grad), L.ptr(out), H, L.DTYPES[y.dtype],
+                                             int(bool(log)), L.ptr(ws), L.stream_ptr(dev)),
+            'rua_segment_softmax_backward')
+    if _kernel_hook:
+        _kernel_hook(name, False)
+    return out
+
+
+class _Softmax(torch.autograd.Function):
+    """y = softmax / log_softmax of every sequence.  Saves ONLY y; the backward is one fused kernel."""
+
+    @staticmethod
+    def forward(ctx, data: Tensor, lay: M.Lay, log: bool, hidden):
+        y = launch_softmax(lay, data, log, hidden)
+        ctx.lay, ctx.log, ctx.hidden = lay, log, tuple(hidden)
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad: Tensor):
+        y, = ctx.saved_tensors
+        if torch.is_grad_enabled():
+            # a graph of this backward is being recorded (create_graph=True): the gradient spelled with the library's
+            # differentiable pieces — the per-sequence sum (twice differentiable) and its broadcast — as
+            # _composed_reduce_grad does; [N, H] temporaries, paid only by callers who ask for second derivatives
+            return _composed_softmax_grad(grad, y, ctx.lay, ctx.log, ctx.hidden), None, None, None
+        return launch_softmax_backward(ctx.lay, y, grad, ctx.log, ctx.hidden), None, None, None
+
+
+def _composed_softmax_grad(grad: Tensor, y: Tensor, lay: M.Lay, log: bool, hidden) -> Tensor:
+    """d softmax / d data as a differentiable function of (grad, y)."""
+    def spread(v: Tensor) -> Tensor:                 # every sequence's row of `v` over the sequence's storage rows
+        return _ReduceBwd.apply(v.contiguous(), y.detach(), v.detach(), lay, L.SUM, None)
+
+    B = lay.B
+    ones = torch.ones((B,) + tuple(hidden), dtype=y.dtype, device=y.device)
+    live = spread(ones) != 0
+    zero = torch.zeros_like(y)
+    # padding rows of a padded layout: y is 0 there, but the cotangent may hold anything (inf, NaN) and exp(0) is 1 —
+    # both variants are evaluated on live rows only and are exactly 0 elsewhere (the mask comes BEFORE the exp)
+    g = torch.where(live, grad, zero)
+    if log:
+        e = torch.where(live, y, zero).exp()
+        return torch.where(live, g - e * spread(reduce(g.contiguous(), lay, L.SUM, hidden, None)), zero)
+    return torch.where(live, y * (g - spread(reduce((g * y).contiguous(), lay, L.SUM, hidden, None))), zero)
+
+
+def softmax(data: Tensor, lay: M.Lay, log: bool, hidden) -> Tensor:
+    if data.dtype not in L.DTYPES:
+        L.require_device(data)
+        raise L.RuaError(f'softmax / log_softmax support {list(L.DTYPES)}; got {data.dtype}')
+    if data.requires_grad and torch.is_grad_enabled():
+        # contiguous HERE, inside the graph (as in reduce()): a copy made inside forward() would carry no history
+        return _Softmax.apply(data.contiguous(), lay, bool(log), tuple(hidden))
+    return launch_softmax(lay, data.detach() if data.requires_grad else data, bool(log), tuple(hidden))
+
+
 # ------------------------------------------------------------------ scatter-sum of rows (adjoint of a row gather)
 def index_buckets(index: Tensor, S: int) -> Tuple[Tensor, Tensor]:
     """(counts[S], perm[M]): the entries of `index` bucketed by destination, every bucket in ascending entry order
