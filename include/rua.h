@@ -354,6 +354,45 @@ int rua_segment_softmax(const rua_layout* lay, const void* data, void* out, int6
 int rua_segment_softmax_backward(const rua_layout* lay, const void* y, const void* grad_out, void* grad_in, int64_t H,
                                  int32_t dtype, int32_t log, void* ws, void* stream);
 
+/* Per-sequence inclusive cumsum (an EXTENSION, added to ABI 6 — the version number did not move: the reference has no
+ * prefix operator; its users pad, call torch.cumsum along dim 1 and cast back).  For every sequence b of `lay` (ANY
+ * layout) and column h:
+ *   reverse == 0:  out[row(b,t), h] = sum over s <= t of data[row(b,s), h]
+ *   reverse != 0:  out[row(b,t), h] = sum over s >= t of data[row(b,s), h]
+ * i.e. torch.cumsum(seq, dim=0) of every sequence on its own: a NaN or an infinity poisons only the later (reverse: the
+ * earlier) tokens of its own sequence and column.  RUA_F32 / RUA_F64 / RUA_BF16 / RUA_F16 — fp32 accumulation (fp64 for
+ * RUA_F64), every output element rounded once — and RUA_I64, which wraps; any other dtype: RUA_EINVAL.  An empty
+ * sequence owns no row of CAT / PACK: nothing is written for it; B == 0, H == 0 and n_rows == 0 return 0 without a
+ * launch.  Padding rows of a LEFT / RIGHT result are written as zeros in the same pass (no pre-zeroing) and padding rows
+ * of the input are never read.  Lengths are clamped to the storage and every row is range-checked.
+ * The association order of a (sequence, column, direction), with u = t (reverse: u = len - 1 - t) the position along the
+ * scan: groups of 8 positions are scanned by three doubling steps (p_j <- p_(j-d) + p_j for j >= d; d = 1, 2, 4); a tile
+ * is 4 groups, whose totals g0 .. g3 precede the later groups as g0, g0 + g1, (g0 + g1) + g2, the tile's total being
+ * ((g0 + g1) + g2) + g3; a block is 64 tiles (2 048 positions), whose carry adds the tile totals one after the other,
+ * afresh in every block; the base of a block adds the totals of the blocks before it one after the other; and
+ *   out = ((base + carry) + groups before) + prefix inside the group.
+ * A term that does not exist is the additive identity (-0.0 for floats, so that the sign of a zero survives).  The
+ * order depends on NOTHING but the sequence's length and the direction: not on the layout, the kernel form, the
+ * alignment or `ws`.  The operator therefore commutes with the casts BIT FOR BIT — cat(cumsum(z)) == cumsum(cat(z))
+ * etc. — and `reverse` equals reversing every sequence, scanning forward and reversing back, bit for bit.
+ * Kernel forms by row width and lengths: rows of one vector (<= 16 bytes) put consecutive tokens on consecutive lanes,
+ * two sequences per wave, the carry in registers; wider rows give a workgroup per (sequence x 128-byte column chunk),
+ * 32 rows per step, the carry in registers again: the payload is read once and written once, there is no slab and no
+ * second walk.  Few but long sequences (fewer than 1 024 units whose length bound — CAT: T_log or n_rows, LEFT / RIGHT:
+ * T_phys, PACK: T — is at least 8 192) are cut into their blocks across workgroups when `ws` is given: phase 1 leaves
+ * every block's total in `ws`, phase 2 adds the totals before a block in order and scans it (two launches; the payload
+ * is read twice).  rua_cumsum_ws_bytes(lay, H, dtype) =
+ *   B * ceil(bound / 2 048) * ceil(H * esize / 128) * (128 / esize) * (4, or 8 for RUA_F64 / RUA_I64)
+ * bytes when the cut form applies, else 0 (0 = never needed; ws == NULL = do not cut).  A CAT layout's T_log, where it
+ * is given (> 0), must be a TRUE upper bound of every length, as for rua_segment_softmax.
+ * `out` may equal `data` (every row is read before it is written, by the same thread; the cut form's first launch only
+ * reads).  Any alignment is accepted (narrower accesses).  While the dispatch trace is on (below) every launch records
+ * `seg_cumsum_lanes_kernel` or `seg_cumsum_rows_kernel` (cut=1 phase=partial|finish for the cut form) with key=value
+ * pairs (T=, AL=, rev=, kind=). */
+int64_t rua_cumsum_ws_bytes(const rua_layout* lay, int64_t H, int32_t dtype);
+int rua_segment_cumsum(const rua_layout* lay, const void* data, void* out, int64_t H, int32_t dtype, int32_t reverse,
+                       void* ws, void* stream);
+
 /* After rua_segment_reduce / rua_pack_reduce with `extreme` (MAX/MIN/LOGSUMEXP): write the
  * global extreme — the reduce left it in the scratch — into the rows of empty sequences, or NaN into every row when
  * the NaN flag is up (the reference's initial=NaN behaviour).  Every workgroup patches its share of the batch.

@@ -37,6 +37,8 @@ I64, I32, I16, I8, U8 = 4, 5, 6, 7, 8
 DTYPES = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16, torch.float64: F64}
 # integer element types: rua_segment_reduce over a CAT layout only (scatter_* on integer tensors, reduce.py:6-23)
 INT_DTYPES = {torch.int64: I64, torch.int32: I32, torch.int16: I16, torch.int8: I8, torch.uint8: U8}
+# per-sequence cumsum (rua_segment_cumsum): the float types and int64
+SCAN_DTYPES = {**DTYPES, torch.int64: I64}
 
 
 class RuaLayout(Structure):
@@ -85,6 +87,8 @@ SYMBOLS = {
                                     c_void_p]),
     'rua_segment_softmax_backward': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_int64, c_int32,
                                              c_int32, c_void_p, c_void_p]),
+    'rua_cumsum_ws_bytes': (c_int64, [POINTER(RuaLayout), c_int64, c_int32]),
+    'rua_segment_cumsum': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
     'rua_fill_empty': (c_int, [POINTER(RuaLayout), c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
     'rua_bucket_ws_elems': (c_int64, [c_int64, c_int64]),
     'rua_index_buckets': (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -444,6 +444,61 @@ def softmax(data: Tensor, lay: M.Lay, log: bool, hidden) -> Tensor:
     return launch_softmax(lay, data.detach() if data.requires_grad else data, bool(log), tuple(hidden))
 
 
+# ------------------------------------------------------------------ per-sequence cumsum (an extension)
+def _cumsum_dtype(data: Tensor) -> int:
+    if data.dtype not in L.SCAN_DTYPES:
+        L.require_device(data)
+        raise L.RuaError(f'cumsum supports {list(L.SCAN_DTYPES)}; got {data.dtype}')
+    return L.SCAN_DTYPES[data.dtype]
+
+
+def launch_cumsum(lay: M.Lay, data: Tensor, reverse: bool, hidden: Tuple[int, ...], out: Optional[Tensor] = None,
+                  cut: bool = True) -> Tensor:
+    """rua_segment_cumsum: one launch (two for cut sequences), one read and one write of the payload.  `out` may be
+    `data` itself.  cut=False withholds the workspace (the same bits from one workgroup per unit: a developer A/B)."""
+    dev = L.require_device(data)
+    code = _cumsum_dtype(data)
+    lib = L.load()
+    H = _prod(hidden)
+    nbytes = lib.rua_cumsum_ws_bytes(lay.ref(), H, code) if cut else 0      # > 0: few but long sequences get cut
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    data = data.contiguous()
+    if out is None:
+        out = torch.empty(data.shape, dtype=data.dtype, device=dev)      # padding rows: zeroed by the call
+    elif not out.is_contiguous() or out.dtype != data.dtype or out.shape != data.shape:
+        raise L.RuaError('cumsum target must be contiguous, of the payload dtype and of the payload shape')
+    name = 'cumsum_rev' if reverse else 'cumsum'
+    if _kernel_hook:
+        _kernel_hook(name, True)
+    L.check(lib.rua_segment_cumsum(lay.ref(), L.ptr(data), L.ptr(out), H, code, int(bool(reverse)), L.ptr(ws),
+                                   L.stream_ptr(dev)), 'rua_segment_cumsum')
+    if _kernel_hook:
+        _kernel_hook(name, False)
+    return out
+
+
+class _Cumsum(torch.autograd.Function):
+    """y = the inclusive prefix sums of every sequence.  Saves NOTHING: the map is linear and the adjoint of the forward
+    scan is the reverse scan, so the backward is this Function with `reverse` flipped — any order of derivative."""
+
+    @staticmethod
+    def forward(ctx, data: Tensor, lay: M.Lay, reverse: bool, hidden):
+        ctx.lay, ctx.reverse, ctx.hidden = lay, reverse, tuple(hidden)
+        return launch_cumsum(lay, data, reverse, hidden)
+
+    @staticmethod
+    def backward(ctx, grad: Tensor):
+        return cumsum(grad, ctx.lay, not ctx.reverse, ctx.hidden), None, None, None
+
+
+def cumsum(data: Tensor, lay: M.Lay, reverse: bool, hidden) -> Tensor:
+    _cumsum_dtype(data)
+    if data.is_floating_point() and data.requires_grad and torch.is_grad_enabled():
+        # contiguous HERE, before the Function (as in reduce()): a copy made inside forward() would carry no history
+        return _Cumsum.apply(data.contiguous(), lay, bool(reverse), tuple(hidden))
+    return launch_cumsum(lay, data.detach() if data.requires_grad else data, bool(reverse), tuple(hidden))
+
+
 # ------------------------------------------------------------------ scatter-sum of rows (adjoint of a row gather)
 def index_buckets(index: Tensor, S: int) -> Tuple[Tensor, Tensor]:
     """(counts[S], perm[M]): the entries of `index` bucketed by destination, every bucket in ascending entry order
