@@ -449,6 +449,19 @@ int rua_host_pack_scans(const int64_t* lens, int64_t B, const int64_t* batch_siz
  * returns the bytes written (with buf == NULL: the bytes the whole log needs, nothing removed). */
 int rua_debug_trace(int32_t on);
 int64_t rua_debug_trace_take(char* buf, int64_t cap);
+/* The plan of a reduce call, without the call: the records rua_segment_reduce, rua_pack_reduce (`pack` = its second
+ * layout) or rua_segment_reduce_backward would append to the trace for these arguments, one per line, into `buf`.
+ * Launches nothing and touches no device.  In place of the device pointers: `present` says which optional ones are
+ * given, `align` is the OR of the payload pointers' low 8 bits; of the layouts only scalars and the null-ness of
+ * pointers are read.  Returns the bytes written (0: nothing to launch), the call's own RUA_E*, or RUA_ERANGE (`cap`). */
+enum { RUA_PLAN_SEGMENT_REDUCE, RUA_PLAN_PACK_REDUCE, RUA_PLAN_BACKWARD };      /* `call` */
+#define RUA_PLAN_PERM 1
+#define RUA_PLAN_WS 2
+#define RUA_PLAN_TIES 4
+#define RUA_PLAN_SELF_IN 8
+int64_t rua_debug_reduce_plan(int32_t call, const rua_layout* lay, const rua_layout* pack, int64_t H, int32_t dtype,
+                              int32_t op, int32_t include_self, int64_t split_rows, int32_t present, int32_t align,
+                              char* buf, int64_t cap);
 int rua_abi_version(void);
 const char* rua_build_target(void);
 

@@ -100,6 +100,8 @@ SYMBOLS = {
     'rua_host_pack_scans': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
     'rua_debug_trace': (c_int, [c_int32]),
     'rua_debug_trace_take': (c_int64, [c_char_p, c_int64]),
+    'rua_debug_reduce_plan': (c_int64, [c_int32, POINTER(RuaLayout), POINTER(RuaLayout), c_int64, c_int32, c_int32, c_int32,
+                                        c_int64, c_int32, c_int32, c_char_p, c_int64]),
     'rua_abi_version': (c_int, []),
     'rua_build_target': (c_char_p, []),
 }

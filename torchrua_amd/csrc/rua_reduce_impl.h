@@ -10,19 +10,14 @@
 // Row addressing per layout (include/rua.h): CAT off[b]+t (contiguous), PACK boff[t]+rank[b]
 // (stride varies with t), LEFT/RIGHT b*T+t(+pad), and CAT+perm for the bucketed scatter_*.
 #pragma once
-#include <stdarg.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <atomic>
+#include <type_traits>
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
 #include "rua_dev.h"
+#include "rua_reduce_plan.h"
 
 namespace rua {
 
-#ifndef RUA_UNROLL_T
-#define RUA_UNROLL_T 8
-#endif
 constexpr int UNROLL_T = RUA_UNROLL_T;
 constexpr int EXTREME_SLOTS = 1024;  // contention spreading for the global min/max tracker (fold_flags)
 
@@ -803,12 +798,6 @@ __global__ __launch_bounds__(RUA_WAVE) void seg_reduce_tail_kernel(rua_layout L,
 //   pass B  units with more parts take the whole workgroup: wave w folds the contiguous range of parts
 //           [w*per, (w+1)*per) in order, then wave 0 folds the 16 range results in wave order.
 // Either association depends only on the part count, so the result is bitwise reproducible.
-constexpr int COMBINE_WAVES_MAX = 16;
-constexpr int REDUCE_HINT_NO_EMPTY = 1, REDUCE_HINT_SHORT_SEQS = 2;    // dispatch_reduce's `hints`
-constexpr int64_t RANKS_MIN_WAVES = 4096;   // adjacent-rank waves (RANKS) only when B / ranks-per-wave still fills the chip
-constexpr int64_t RANKS_MIN_WAVES_SHORT = 512;   // ... of SHORT sequences (dispatch_reduce_main)
-constexpr int COMBINE_SOLO = 32;
-constexpr int64_t COMBINE_GRID = 512;   // 2 workgroups per CU
 
 template <typename A, int NE, int OP>
 __device__ __forceinline__ void combine_range(Fold<A, NE>& f, const A* __restrict__ P, int64_t pbase, int64_t p_lo,
@@ -907,9 +896,6 @@ constexpr int UNROLL_B = 4;
 //              scatter_max/min with include_self); one walk writes the gradient.
 //   RANKS: as in the forward (make_unit) — the wave's row groups are adjacent ranks of a PackedSequence walking the
 //   same time steps; every group is its own sequence (per-lane len, no cross-group combine).
-// `extra_count` of the backward kernels: bit 0 = the old destination row of a scatter_* took part (MEAN's divisor,
-// PROD's factors); bit 1 = RUA_BWD_TIES_POSITIVE
-constexpr int BWD_SELF_COUNTS = 1, BWD_TIES_POSITIVE = 2;
 
 // the share of one of `c` tied extrema in the gradient g.  torch.segment_reduce's backward hands every tie the whole
 // g and then divides only the entries that are > 0 (SegmentReduce.cpp: `if (grad_input > 0) grad_input /= counter`),
@@ -1252,7 +1238,6 @@ __global__ __launch_bounds__(RUA_WAVE) void seg_backward_ranks_kernel(rua_layout
 // (every row of a sequence asks for the same ones).  No sequence-length imbalance, stores sweep the buffer in
 // order, and rows of padded layouts that hold no token are written as zeros in the same pass (the caller need not
 // pre-zero the gradient).  Walk-per-sequence form (seg_backward_kernel): max over C 4.7 TB/s at 1 KiB rows.
-constexpr int BROWS_MAX = 256;
 // (8 waves per SIMD, forced: max / min sit ON the 64-VGPR line and the allocator lands on 63 .. 66 from one edit to the
 // next — 7 waves per SIMD cost 7-11 % at the north-star shape, two spilled dwords cost nothing measurable: r5u/bwd_ab.txt)
 template <typename T, int EPL, int OP, bool NT, bool WIDE = false>
@@ -1617,10 +1602,6 @@ __global__ __launch_bounds__(RUA_BLOCK) void scatter_self_grad_kernel(const int6
 }
 
 // workspace carving for the long-sequence split (see SplitWs)
-static inline int64_t split_max_extra(int64_t n_rows, int64_t split) { return split > 0 ? n_rows / split : 0; }
-constexpr int64_t SPLIT_GRID_CAP = 16384;   // tail / combine grids: 2x the wave slots of the chip, then stride
-static inline unsigned split_grid(int64_t max_u) { return (unsigned)(max_u < SPLIT_GRID_CAP ? max_u : SPLIT_GRID_CAP); }
-
 template <typename A>
 static SplitWs carve_ws(void* ws, int64_t max_u, int64_t split) {
   SplitWs W;
@@ -1634,564 +1615,233 @@ static SplitWs carve_ws(void* ws, int64_t max_u, int64_t split) {
   return W;
 }
 
-// ---- dispatch trace (rua_debug_trace, include/rua.h): the host records which kernel template a dispatcher committed to,
-// one line per launch, named as in this file.  Off: one relaxed load per dispatch.  The log lives in rua_reduce.hip.
-extern std::atomic<int> g_trace_on;
-void trace_add(const char* rec);
-static inline bool tracing() { return g_trace_on.load(std::memory_order_relaxed) != 0; }
-__attribute__((format(printf, 1, 2))) static void trace_fmt(const char* fmt, ...) {
-  char buf[320];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  trace_add(buf);
-}
-template <typename T> static const char* tname();
-template <> const char* tname<float>() { return "f32"; }
-template <> const char* tname<double>() { return "f64"; }
-template <> const char* tname<__hip_bfloat16>() { return "bf16"; }
-template <> const char* tname<__half>() { return "f16"; }
-// the OP template argument the switch below a dispatcher picks (max / min count their ties when `ties` is given)
-static inline const char* op_name(int op, bool ties) {
-  switch (op) {
-    case RUA_SUM: return "sum";
-    case RUA_MEAN: return "mean";
-    case RUA_MAX: return ties ? "max_t" : "max";
-    case RUA_MIN: return ties ? "min_t" : "min";
-    case RUA_PROD: return "prod";
-    case RUA_LOGSUMEXP: return "logsumexp";
+// ---- the launchers: a plan (rua_reduce_plan.h) says WHAT to launch; these turn its run-time values into the template
+// arguments of the kernels.  Each helper hands a generic lambda one compile-time value; `if constexpr` in the lambdas
+// keeps the kernels that exist to the combinations the plans can ask for.
+template <int V> using int_c = std::integral_constant<int, V>;
+// the OP template argument (COUNTING, the forward: max / min count their ties when `ties` is set); RUA_EINVAL for an
+// op there is none of
+template <bool COUNTING, typename F>
+static int with_op(int op, bool ties, F&& f) {
+  if constexpr (COUNTING) {
+    if (ties && op == RUA_MAX) { f(int_c<RUA_MAX_T>{}); return 0; }
+    if (ties && op == RUA_MIN) { f(int_c<RUA_MIN_T>{}); return 0; }
   }
-  return "?";
+  switch (op) {
+    case RUA_SUM: f(int_c<RUA_SUM>{}); return 0;
+    case RUA_MEAN: f(int_c<RUA_MEAN>{}); return 0;
+    case RUA_MAX: f(int_c<RUA_MAX>{}); return 0;
+    case RUA_MIN: f(int_c<RUA_MIN>{}); return 0;
+    case RUA_PROD: f(int_c<RUA_PROD>{}); return 0;
+    case RUA_LOGSUMEXP: f(int_c<RUA_LOGSUMEXP>{}); return 0;
+  }
+  return RUA_EINVAL;
 }
-template <typename T>
-static void trace_fwd(const char* kern, int epl, int op, bool ties, bool nt, bool copy, int cpw, int wpb, int team,
-                      int glog, int check, bool split, int no_empty) {
-  trace_fmt("%s T=%s EPL=%d OP=%s NT=%d COPY=%d CPW=%d WPB=%d team=%d glog=%d check=%d split=%d no_empty=%d", kern,
-            tname<T>(), epl, op_name(op, ties), nt ? 1 : 0, copy ? 1 : 0, cpw, wpb, team, glog, check, split ? 1 : 0,
-            no_empty);
+template <typename F>
+static void with_bool(bool v, F&& f) { if (v) f(std::true_type{}); else f(std::false_type{}); }
+// elements per lane: 16-byte lanes (FULL), 8-byte lanes (HALF; there are none for f64) or one element
+template <typename T, typename F>
+static void with_epl(int epl, F&& f) {
+  constexpr int FULL = 16 / sizeof(T), HALF = FULL >= 4 ? FULL / 2 : 1;
+  if (epl == FULL) f(int_c<FULL>{}); else if (epl == HALF) f(int_c<HALF>{}); else f(int_c<1>{});
 }
 
 template <typename T>
-static void trace_bwd(const char* kern, int epl, int op, bool nt, int tv, bool multi_chunk, bool span, bool split,
-                      bool phased, bool ties_final, bool pad_memset) {
-  trace_fmt("%s T=%s EPL=%d OP=%s NT=%d TV=%d chunks=%d span=%d split=%d phased=%d ties_final=%d pad_memset=%d", kern,
-            tname<T>(), epl, op_name(op, false), nt ? 1 : 0, tv, multi_chunk ? 1 : 0, span ? 1 : 0, split ? 1 : 0,
-            phased ? 1 : 0, ties_final ? 1 : 0, pad_memset ? 1 : 0);
-}
-
-template <typename T, int EPL, bool NT, bool COPY, int CPW>
-static int launch_reduce(int op, unsigned grid, hipStream_t s, const rua_layout& L, const int64_t* perm,
-                         const void* data, void* out, int64_t H, int lp_log2, int64_t n_chunks, int include_self,
-                         uint64_t empty_bits, void* extreme, const rua_layout& CD, void* copy, int64_t split,
-                         void* ws, void* ties, int no_empty) {
+static int launch_reduce(const ReducePlan& P, hipStream_t s, const rua_layout& L, const int64_t* perm, const void* data,
+                         void* out, int64_t H, int include_self, uint64_t empty_bits, void* extreme, void* ws,
+                         const rua_layout* CD, void* copy, void* ties) {
   using A = typename elem<T>::acc;
+  constexpr int FULL = 16 / sizeof(T), HALF = FULL >= 4 ? FULL / 2 : 1;
   T ev;
   __builtin_memcpy(&ev, &empty_bits, sizeof(T));
-  const dim3 g(grid), b(RUA_WAVE);
-  const int64_t max_u = split_max_extra(L.n_rows, split) * n_chunks;
-  const bool do_split = split > 0 && ws && max_u > 0;
+  unsigned long long* ext = (unsigned long long*)extreme;
+  const rua_layout& cd = copy ? *CD : L;
+  const int lp_log2 = P.lp_log2, no_empty = P.no_empty;
+  const int64_t n_chunks = P.n_chunks;
   SplitWs W = {};
-  if (do_split) {
-    if (max_u > 0x7fffffffLL) return RUA_ERANGE;
-    W = carve_ws<A>(ws, max_u, split);
-    hipError_t e = hipMemsetAsync(W.ctr, 0, 4 * sizeof(unsigned long long), s);
+  if (P.split) {
+    W = carve_ws<A>(ws, P.max_u, P.split_rows);
+    const hipError_t e = hipMemsetAsync(W.ctr, 0, 4 * sizeof(unsigned long long), s);
     if (e != hipSuccess) return (int)e;
   }
   W.ties = ties;
-  unsigned long long* ext = (unsigned long long*)extreme;
-  // Two INDEPENDENT waves per workgroup over the batch-major layouts (C / L / R): neighbouring sequences are
-  // neighbouring storage, and halving the number of workgroups is worth 6-9 % there (cfg3 segment_sum 108.8 -> 101.3 us,
-  // north-star segment_sum(c) 2.86 -> 2.70 ms); four are no better, and over a PackedSequence — walked longest sequence
-  // first, every rank its own slot — two LOSE 7 % (2.64 -> 2.84 ms): one wave per workgroup stays there
-  // (profiles/r04_reduce_wpb_ab.txt, measured with a temporary environment knob).
-  // Rows of at least 512 bytes only: at 16 / 32-byte rows (a whole short sequence per wave instruction) two waves per
-  // workgroup lose 7-10 % (final width sweep of round 4: 2.36 -> 2.20, 4.40 -> 3.95 TB/s).
-  const int wpb = (COPY || CPW != 1) ? 1 : ((L.kind != RUA_PACK && H * (int64_t)sizeof(T) >= 512) ? 2 : 1);
-  if (tracing()) {
-    const bool tk = !COPY && ties;
-    trace_fwd<T>("seg_reduce_kernel", EPL, op, tk, NT, COPY, CPW, do_split ? 1 : wpb, 1, 0, 0, do_split, no_empty);
-    if (do_split) {
-      trace_fwd<T>("seg_reduce_tail_kernel", EPL, op, tk, NT, COPY, CPW, 1, 1, 0, 0, true, no_empty);
-      trace_fwd<T>("seg_reduce_combine_kernel", EPL, op, tk, false, COPY, CPW, COMBINE_WAVES_MAX / CPW, 1, 0, 0, true,
-                   no_empty);
+  const dim3 g(P.grid), b(RUA_WAVE);
+  const int rc = with_op<true>(P.op, P.ties, [&](auto op_c) {
+    constexpr int OP = decltype(op_c)::value;
+    // what follows a main kernel that published parts of long sequences: the parts, then the fold of the partials
+    auto split_rest = [&](auto epl_c, auto nt_c, auto copy_c, auto cpw_c) {
+      constexpr int EPL = decltype(epl_c)::value, CPW = decltype(cpw_c)::value;
+      constexpr bool NT = decltype(nt_c)::value, COPY = decltype(copy_c)::value;
+      hipLaunchKernelGGL((seg_reduce_tail_kernel<T, EPL, OP, NT, COPY, CPW>), dim3(split_grid(P.max_u)), b, 0, s, L, perm,
+                         (const T*)data, H, lp_log2, ext, cd, (T*)copy, W, no_empty);
+      hipLaunchKernelGGL((seg_reduce_combine_kernel<T, EPL, OP, CPW>),
+                         dim3((unsigned)(P.max_u < COMBINE_GRID ? P.max_u : COMBINE_GRID)),
+                         dim3(RUA_WAVE * (COMBINE_WAVES_MAX / CPW)), 0, s, L, perm, (T*)out, H, lp_log2, include_self, ev,
+                         cd, COPY ? 1 : 0, W);
+    };
+    if (P.form == REDUCE_TEAM) {        // 16-byte lanes only
+      with_bool(P.nt, [&](auto nt_c) {
+        hipLaunchKernelGGL((seg_reduce_team_kernel<T, FULL, OP, decltype(nt_c)::value>), g, dim3(RUA_WAVE * P.team), 0, s,
+                           L, perm, (const T*)data, (T*)out, H, lp_log2, n_chunks, include_self, ev, ext, (A*)ties, no_empty);
+      });
+      return;
     }
-  }
-#define RUA_LAUNCH(OP)                                                                                             \
-  if (do_split) {                                                                                                   \
-    hipLaunchKernelGGL((seg_reduce_kernel<T, EPL, OP, NT, COPY, true, CPW>), g, b, 0, s, L, perm, (const T*)data,   \
-                       (T*)out, H, lp_log2, n_chunks, include_self, ev, ext, CD, (T*)copy, W, no_empty);            \
-    hipLaunchKernelGGL((seg_reduce_tail_kernel<T, EPL, OP, NT, COPY, CPW>), dim3(split_grid(max_u)), b, 0, s, L, perm, \
-                       (const T*)data, H, lp_log2, ext, CD, (T*)copy, W, no_empty);                                 \
-    hipLaunchKernelGGL((seg_reduce_combine_kernel<T, EPL, OP, CPW>),                                                \
-                       dim3((unsigned)(max_u < COMBINE_GRID ? max_u : COMBINE_GRID)),                               \
-                       dim3(RUA_WAVE * (COMBINE_WAVES_MAX / CPW)), 0, s, L, perm, (T*)out,                          \
-                       H, lp_log2, include_self, ev, CD, COPY ? 1 : 0, W);                                          \
-  } else if (wpb == 2) {                                                                                            \
-    hipLaunchKernelGGL((seg_reduce_kernel<T, EPL, OP, NT, COPY, false, CPW, 2>), dim3((grid + 1) / 2), dim3(RUA_WAVE * 2), \
-                       0, s, L, perm, (const T*)data, (T*)out, H, lp_log2, n_chunks, include_self, ev, ext, CD, (T*)copy, W, no_empty); \
-  } else {                                                                                                          \
-    hipLaunchKernelGGL((seg_reduce_kernel<T, EPL, OP, NT, COPY, false, CPW>), g, b, 0, s, L, perm, (const T*)data,  \
-                       (T*)out, H, lp_log2, n_chunks, include_self, ev, ext, CD, (T*)copy, W, no_empty);            \
-  }
-  switch (op) {
-    case RUA_SUM: RUA_LAUNCH(RUA_SUM); break;
-    case RUA_MEAN: RUA_LAUNCH(RUA_MEAN); break;
-    case RUA_MAX:
-      if constexpr (!COPY) { if (ties) { RUA_LAUNCH(RUA_MAX_T); break; } }   // also count the ties (for the backward)
-      RUA_LAUNCH(RUA_MAX); break;
-    case RUA_MIN:
-      if constexpr (!COPY) { if (ties) { RUA_LAUNCH(RUA_MIN_T); break; } }
-      RUA_LAUNCH(RUA_MIN); break;
-    case RUA_PROD: RUA_LAUNCH(RUA_PROD); break;
-    case RUA_LOGSUMEXP: RUA_LAUNCH(RUA_LOGSUMEXP); break;
-    default: return RUA_EINVAL;
-  }
-#undef RUA_LAUNCH
-  return (int)hipGetLastError();
+    with_epl<T>(P.epl, [&](auto epl_c) {
+      constexpr int EPL = decltype(epl_c)::value;
+      with_bool(P.nt, [&](auto nt_c) {
+        constexpr bool NT = decltype(nt_c)::value;
+        if constexpr (!NT || EPL == FULL) {       // streaming loads: 16-byte lanes only
+          if (P.form == REDUCE_RANKS) {
+            if (!P.split) {
+              hipLaunchKernelGGL((seg_reduce_ranks_kernel<T, EPL, OP, NT>), g, b, 0, s, L, (const T*)data, (T*)out, H,
+                                 lp_log2, include_self, ev, ext, (A*)ties, P.glog, W, no_empty, P.check);
+            } else if constexpr (EPL == FULL) {   // (plan_reduce: ranks_split needs vec_ok)
+              hipLaunchKernelGGL((seg_reduce_ranks_kernel<T, EPL, OP, NT, true>), g, b, 0, s, L, (const T*)data, (T*)out,
+                                 H, lp_log2, include_self, ev, ext, (A*)ties, P.glog, W, no_empty, P.check);
+              split_rest(epl_c, nt_c, std::false_type{}, int_c<1>{});
+            }
+            return;
+          }
+          with_bool(P.copy, [&](auto copy_c) {
+            constexpr bool COPY = decltype(copy_c)::value;
+            with_bool(P.cpw == 4, [&](auto wide_c) {
+              constexpr int CPW = decltype(wide_c)::value ? 4 : 1;
+              // fused pack + reduce: 16-byte lanes, no tie counting; four column chunks per wave: vector lanes
+              if constexpr ((!COPY || (EPL == FULL && !op_counts(OP))) && (CPW == 1 || EPL == FULL || EPL == HALF)) {
+                if (P.split) {
+                  hipLaunchKernelGGL((seg_reduce_kernel<T, EPL, OP, NT, COPY, true, CPW>), g, b, 0, s, L, perm,
+                                     (const T*)data, (T*)out, H, lp_log2, n_chunks, include_self, ev, ext, cd, (T*)copy, W,
+                                     no_empty);
+                  split_rest(epl_c, nt_c, copy_c, int_c<CPW>{});
+                } else if (P.wpb == 2) {      // (plan_reduce: one column chunk per wave, no copy)
+                  if constexpr (!COPY && CPW == 1)
+                    hipLaunchKernelGGL((seg_reduce_kernel<T, EPL, OP, NT, COPY, false, CPW, 2>), dim3((P.grid + 1) / 2),
+                                       dim3(RUA_WAVE * 2), 0, s, L, perm, (const T*)data, (T*)out, H, lp_log2, n_chunks,
+                                       include_self, ev, ext, cd, (T*)copy, W, no_empty);
+                } else {
+                  hipLaunchKernelGGL((seg_reduce_kernel<T, EPL, OP, NT, COPY, false, CPW>), g, b, 0, s, L, perm,
+                                     (const T*)data, (T*)out, H, lp_log2, n_chunks, include_self, ev, ext, cd, (T*)copy, W,
+                                     no_empty);
+                }
+              }
+            });
+          });
+        }
+      });
+    });
+  });
+  return rc ? rc : (int)hipGetLastError();
 }
 
 template <typename T>
-static int dispatch_reduce_main(int op, hipStream_t s, const rua_layout& L, const int64_t* perm, const void* data,
-                                void* out, int64_t H, int include_self, uint64_t empty_bits, void* extreme,
-                                int64_t split, void* ws, const rua_layout* CD = nullptr, void* copy = nullptr,
-                                void* ties = nullptr, bool short_seqs = false, int no_empty = 0) {
-  constexpr int FULL = 16 / sizeof(T);
-  constexpr int HALF = FULL >= 4 ? FULL / 2 : 1;      // 8-byte loads: hidden sizes that are a multiple of 8 bytes only
-  const uintptr_t fptrs = (uintptr_t)data | (uintptr_t)out | (uintptr_t)copy | (uintptr_t)ties;
-  const bool aligned_ok = (H % FULL == 0) && (fptrs % 16 == 0);
-  // Rows of 8 (mod 16) bytes (H = 500 in bf16): every other row starts on an 8-byte boundary only and the last lane of
-  // a row would hold half a vector.  gfx950 takes a dwordx4 at any dword-aligned address, and the LAST lane simply
-  // covers the last FULL elements of the row, overlapping its neighbour by half a vector: both lanes fold the same
-  // elements in the same order and store the same results (make_unit clamps the column).  Round 2 used 8-byte lanes
-  // there — two column chunks, two waves per row, 4.0 TB/s for segment_max over a CattedSequence at H = 500.
-  // (Not with include_self == 1: the store then reads the old row, and two lanes would fold it in twice.)
-  const bool tail_ok = !aligned_ok && FULL > 1 && H > FULL && (H + FULL - 1) / FULL <= RUA_WAVE &&
-                       (H * (int64_t)sizeof(T)) % 8 == 0 && (fptrs % 8 == 0) && include_self != 1 && !copy;
-  const bool vec_ok = aligned_ok || tail_ok;
-  // (H = 300 or 650 in bf16 — GloVe vectors, PTB-sized LSTMs: the scalar path moves 128 B per wave instruction and
-  // measured 2.9 TB/s; 8-byte lanes move 512 B)
-  const bool half_ok = !vec_ok && HALF > 1 && (H % HALF == 0) && (fptrs % 8 == 0);
-  const int epl = vec_ok ? FULL : half_ok ? HALF : 1;
-  const int64_t lpr = (H + epl - 1) / epl;  // lanes per row
-  int lp_log2 = 0;
-  while ((1 << lp_log2) < lpr && lp_log2 < 6) ++lp_log2;
-  // rows wider than one wave instruction (1 KiB): one wave owns 4 column chunks, i.e. up to 4 KiB of the row
-  // (the same for 8-byte lanes: H = 500 in bf16 is 125 lanes — as two column chunks two waves each read every other
-  // 512-byte half of the rows: reduce over P at H = 500 5.0 -> 5.7 TB/s
-  // — over a PackedSequence only: over the batch-major layouts, whose sequences are contiguous, the two waves per row
-  // were the better half of the bytes in flight: 4.0 -> 2.7 TB/s when tried)
-  const bool wide = (vec_ok || (half_ok && L.kind == RUA_PACK)) && lpr > RUA_WAVE;
-  const int cpw = wide ? 4 : 1;
-  const int64_t n_chunks = (lpr + RUA_WAVE * cpw - 1) / (RUA_WAVE * cpw);
-  const int64_t blocks = L.B * n_chunks;  // one wave per workgroup
-  if (blocks > 0x7fffffffLL) return RUA_ERANGE;
-  const bool nt = (double)L.n_rows * (double)H * sizeof(T) >= (double)(512ll << 20);
-  const unsigned g = (unsigned)blocks;
-  static const rua_layout none = {};
-  const rua_layout& cd = copy ? *CD : none;
-  if (copy && !aligned_ok) return RUA_EALIGN;   // fused pack + reduce: vector path only (caller falls back to two launches)
-  // (only when that still leaves >= 4 waves per SIMD: with fewer sequences one wave per sequence fills the chip better)
-  // (RUA_OP_SHORT_SEQS: the caller knows the longest sequence and vouches that none is far above the average — the
-  // wave walks to the longest of its sequences, so ONE long sequence among short ones would be walked by one lane group)
-  bool cat_ranks = L.kind == RUA_CAT && L.lens && L.len_add == 0 && lp_log2 < 6;
-  int glog = 0;                                   // log2 of the row slots of one sequence's lane group (make_unit)
-  if (cat_ranks) {
-    const int64_t side = RUA_WAVE >> lp_log2;     // sequences side by side with one row slot each
-    const int64_t short_avg = 4 * side < 16 ? 16 : (4 * side > 64 ? 64 : 4 * side);
-    if (L.n_rows > short_avg * L.B) {             // longer than that on average:
-      if (lp_log2 <= 1) glog = 4 - lp_log2;       // FOUR sequences per wave at rows of <= 32 bytes (16 / 8 rows of each
-      else cat_ranks = false;                     // per instruction; the wave checks its own lengths), else one wave each
-    }                                             // (short on average, no word about the longest: the waves check, `check`)
-    // ([r5] a batch too small to fill the chip with every row slot its own sequence still fills it four to a wave at
-    // rows of <= 32 bytes)
-    if (cat_ranks && glog == 0 && lp_log2 <= 1 && (L.B >> (6 - lp_log2)) < RANKS_MIN_WAVES_SHORT) glog = 4 - lp_log2;
-  }
-  // How many side-by-side waves are enough: RANKS_MIN_WAVES when the sequences may be long (a wave then walks hundreds of
-  // steps one after the other, and only plenty of them keep the chip busy); a few hundred when they are SHORT — a
-  // CattedSequence that is short on average, a PackedSequence of at most 128 time steps — where the alternative is one
-  // wave per sequence at one row per instruction: 200 000 x U(1,32) rows of 16 bytes are 3 125 waves of 64 sequences
-  const bool short_form = (cat_ranks && glog == 0) || (L.kind == RUA_PACK && L.T > 0 && L.T <= 128);
-  const int64_t ranks_min_waves = short_form ? RANKS_MIN_WAVES_SHORT : RANKS_MIN_WAVES;
-  // ([r5] with the long-sequence split armed — lengths nobody vouches for — the four-per-wave form splits by itself)
-  const int ranks_check = (cat_ranks && !short_seqs) ? 1 : 0;
-  const bool ranks_split = split > 0 && ws && cat_ranks && (glog > 0 || ranks_check) && vec_ok && split_max_extra(L.n_rows, split) > 0;
-  if (((L.kind == RUA_PACK && L.sorted) || cat_ranks) && !copy && !perm && lp_log2 < 6 && (!(split > 0 && ws) || ranks_split) &&
-      (L.B >> (6 - lp_log2 - glog)) >= ranks_min_waves) {
-    // narrow rows of a PackedSequence: adjacent ranks share a wave instruction
-    // (tried for a CattedSequence with 32-byte rows too — groups = adjacent sequences: 4.0 -> 2.8 TB/s at U(8,512),
-    // unsorted neighbours differ too much in length — so C keeps one wave per sequence, EXCEPT for batches of short
-    // sequences, when the caller says so: there a wave per sequence is bound by the rate at which workgroups can be
-    // dispatched at all — 4 M singletons: 2.98 ms, 1.3 workgroups per ns; 500 000 sequences of 16 rows on average:
-    // 0.40 -> 0.06-0.07 ms at 16 / 32-byte rows, 0.43 -> 0.21 at 128: profiles/r04_cat_ranks_ab.txt.  And at rows of
-    // <= 32 bytes a whole sequence of a few hundred rows is a handful of wave instructions behind a chain of dependent
-    // loads — 2.2 / 4.1 TB/s at 16 / 32 bytes with U(8,512) lengths — so there FOUR sequences share a wave, sixteen /
-    // eight rows of each per instruction.  Every row slot its own sequence only under the caller's word that no sequence
-    // is far above the average, because the wave walks to the longest of its sequences; the four-per-wave form checks
-    // that by itself, wave by wave (seg_reduce_ranks_kernel), so it also serves lengths that live on the device only)
-    const int64_t rpw = RUA_WAVE >> (lp_log2 + glog);
-    const int64_t nblk = (L.B + rpw - 1) / rpw;
-    if (nblk > 0x7fffffffLL) return RUA_ERANGE;
-    T ev;
-    __builtin_memcpy(&ev, &empty_bits, sizeof(T));
-    const dim3 gg((unsigned)nblk), bb(RUA_WAVE);
-    unsigned long long* ext = (unsigned long long*)extreme;
-    SplitWs W = {};
-    const int64_t max_u = ranks_split ? split_max_extra(L.n_rows, split) : 0;      // (one column chunk per row here)
-    if (ranks_split) {
-      if (max_u > 0x7fffffffLL) return RUA_ERANGE;
-      W = carve_ws<typename elem<T>::acc>(ws, max_u, split);
-      const hipError_t e = hipMemsetAsync(W.ctr, 0, 4 * sizeof(unsigned long long), s);
-      if (e != hipSuccess) return (int)e;
-      W.ties = ties;
-    }
-    if (tracing()) {
-      const int ntr = vec_ok && nt;
-      trace_fwd<T>("seg_reduce_ranks_kernel", epl, op, ties != nullptr, ntr, false, 1, 1, 1, glog, ranks_check,
-                   ranks_split, no_empty);
-      if (ranks_split) {
-        trace_fwd<T>("seg_reduce_tail_kernel", epl, op, ties != nullptr, ntr, false, 1, 1, 1, glog, ranks_check, true,
-                     no_empty);
-        trace_fwd<T>("seg_reduce_combine_kernel", epl, op, ties != nullptr, false, false, 1, COMBINE_WAVES_MAX, 1, glog,
-                     ranks_check, true, no_empty);
-      }
-    }
-#define RUA_RANKS(EPLV, NTV, OPV)                                                                                 \
-  do { if (ranks_split) {                                                                                               \
-    if constexpr (EPLV == FULL) {                                                                                  \
-      hipLaunchKernelGGL((seg_reduce_ranks_kernel<T, EPLV, OPV, NTV, true>), gg, bb, 0, s, L, (const T*)data, (T*)out, H, \
-                         lp_log2, include_self, ev, ext, (typename elem<T>::acc*)ties, glog, W, no_empty, ranks_check); \
-      hipLaunchKernelGGL((seg_reduce_tail_kernel<T, EPLV, OPV, NTV, false, 1>), dim3(split_grid(max_u)), bb, 0, s, L, \
-                         (const int64_t*)nullptr, (const T*)data, H, lp_log2, ext, L, (T*)nullptr, W, no_empty);   \
-      hipLaunchKernelGGL((seg_reduce_combine_kernel<T, EPLV, OPV, 1>),                                             \
-                         dim3((unsigned)(max_u < COMBINE_GRID ? max_u : COMBINE_GRID)),                            \
-                         dim3(RUA_WAVE * COMBINE_WAVES_MAX), 0, s, L, (const int64_t*)nullptr, (T*)out, H, lp_log2, \
-                         include_self, ev, L, 0, W);                                                               \
-    }                                                                                                              \
-  } else                                                                                                           \
-  hipLaunchKernelGGL((seg_reduce_ranks_kernel<T, EPLV, OPV, NTV>), gg, bb, 0, s, L, (const T*)data, (T*)out, H,    \
-                     lp_log2, include_self, ev, ext, (typename elem<T>::acc*)ties, glog, W, no_empty, ranks_check); } while (0)
-#define RUA_RANKS_OP(EPLV, NTV)                                  \
-  switch (op) {                                                  \
-    case RUA_SUM: RUA_RANKS(EPLV, NTV, RUA_SUM); break;          \
-    case RUA_MEAN: RUA_RANKS(EPLV, NTV, RUA_MEAN); break;        \
-    case RUA_MAX: if (ties) RUA_RANKS(EPLV, NTV, RUA_MAX_T); else RUA_RANKS(EPLV, NTV, RUA_MAX); break; \
-    case RUA_MIN: if (ties) RUA_RANKS(EPLV, NTV, RUA_MIN_T); else RUA_RANKS(EPLV, NTV, RUA_MIN); break; \
-    case RUA_PROD: RUA_RANKS(EPLV, NTV, RUA_PROD); break;        \
-    case RUA_LOGSUMEXP: RUA_RANKS(EPLV, NTV, RUA_LOGSUMEXP); break; \
-    default: return RUA_EINVAL;                                  \
-  }
-    if (vec_ok) { if (nt) { RUA_RANKS_OP(FULL, true) } else { RUA_RANKS_OP(FULL, false) } }
-    else if (half_ok) { RUA_RANKS_OP(HALF, false) }
-    else { RUA_RANKS_OP(1, false) }
-#undef RUA_RANKS_OP
-#undef RUA_RANKS
-    return (int)hipGetLastError();
-  }
-  // few-but-long units: a team of waves per unit (seg_reduce_team_kernel) — vector path, rows up to 1 KiB, no split
-  if (vec_ok && !wide && !copy && !(split > 0 && ws)) {
-    const int team = reduce_team_waves(L.n_rows, L.B, lp_log2, blocks, UNROLL_T);   // (rua_dev.h: the one rule)
-    if (team > 1) {
-      T ev;
-      __builtin_memcpy(&ev, &empty_bits, sizeof(T));
-      const dim3 gg((unsigned)blocks), bb(RUA_WAVE * team);
-      unsigned long long* ext = (unsigned long long*)extreme;
-      using A = typename elem<T>::acc;
-      if (tracing())
-        trace_fwd<T>("seg_reduce_team_kernel", FULL, op, ties != nullptr, nt, false, 1, team, team, 0, 0, false, no_empty);
-#define RUA_TEAM(NTV, OPV)                                                                                          \
-  hipLaunchKernelGGL((seg_reduce_team_kernel<T, FULL, OPV, NTV>), gg, bb, 0, s, L, perm, (const T*)data, (T*)out, H, \
-                     lp_log2, n_chunks, include_self, ev, ext, (A*)ties, no_empty)
-#define RUA_TEAM_OP(NTV)                                                                           \
-  switch (op) {                                                                                    \
-    case RUA_SUM: RUA_TEAM(NTV, RUA_SUM); break;                                                   \
-    case RUA_MEAN: RUA_TEAM(NTV, RUA_MEAN); break;                                                 \
-    case RUA_MAX: if (ties) RUA_TEAM(NTV, RUA_MAX_T); else RUA_TEAM(NTV, RUA_MAX); break;          \
-    case RUA_MIN: if (ties) RUA_TEAM(NTV, RUA_MIN_T); else RUA_TEAM(NTV, RUA_MIN); break;          \
-    case RUA_PROD: RUA_TEAM(NTV, RUA_PROD); break;                                                 \
-    case RUA_LOGSUMEXP: RUA_TEAM(NTV, RUA_LOGSUMEXP); break;                                       \
-    default: return RUA_EINVAL;                                                                    \
-  }
-      if (nt) { RUA_TEAM_OP(true) } else { RUA_TEAM_OP(false) }
-#undef RUA_TEAM_OP
-#undef RUA_TEAM
-      return (int)hipGetLastError();
-    }
-  }
-#define RUA_GO(EPLV, NTV, COPYV, CPWV)                                                                             \
-  return launch_reduce<T, EPLV, NTV, COPYV, CPWV>(op, g, s, L, perm, data, out, H, lp_log2, n_chunks, include_self, \
-                                                  empty_bits, extreme, cd, copy, split, ws, ties, no_empty)
-  if (copy) {
-    if (wide) { if (nt) RUA_GO(FULL, true, true, 4); else RUA_GO(FULL, false, true, 4); }      // (copy: vec_ok)
-    if (nt) RUA_GO(FULL, true, true, 1); else RUA_GO(FULL, false, true, 1);
-  }
-  if (wide && vec_ok) { if (nt) RUA_GO(FULL, true, false, 4); else RUA_GO(FULL, false, false, 4); }
-  if (wide && half_ok) RUA_GO(HALF, false, false, 4);
-  if (vec_ok) { if (nt) RUA_GO(FULL, true, false, 1); else RUA_GO(FULL, false, false, 1); }
-  if (half_ok) RUA_GO(HALF, false, false, 1);
-  RUA_GO(1, false, false, 1);
-#undef RUA_GO
-}
-
-
-// (rounds 1-4 launched a conditional second walk for the global extreme behind the reduce; the reduce now tracks it
-// itself — fold_flags — so this is the reduce and nothing else)
-template <typename T>
-static int dispatch_reduce(int op, hipStream_t s, const rua_layout& L, const int64_t* perm, const void* data,
-                           void* out, int64_t H, int include_self, uint64_t empty_bits, void* extreme,
-                           int64_t split, void* ws, const rua_layout* CD = nullptr, void* copy = nullptr,
-                           void* ties = nullptr, int hints = 0) {
-  return dispatch_reduce_main<T>(op, s, L, perm, data, out, H, include_self, empty_bits, extreme, split, ws, CD, copy,
-                                 ties, (hints & REDUCE_HINT_SHORT_SEQS) != 0, (hints & REDUCE_HINT_NO_EMPTY) ? 1 : 0);
-}
-
-template <typename T, int EPL>
-static int launch_backward(int op, unsigned grid, hipStream_t s, const rua_layout& L, const int64_t* perm,
-                           const void* data, const void* out, const void* gout, void* gin, int64_t H, int lp_log2,
-                           int64_t n_chunks, int extra_count, int64_t split, void* ws, void* ties,
-                           bool ties_final, const void* self_in, bool fill_padding) {
+static int launch_backward(const BackwardPlan& P, hipStream_t s, const rua_layout& L, const int64_t* perm,
+                           const void* data, const void* out, const void* gout, void* gin, int64_t H, int extra_count,
+                           void* ws, void* ties, const void* self_in) {
   using A = typename elem<T>::acc;
-  const dim3 g(grid), b(RUA_WAVE);
-  const T* sp = (const T*)self_in;
-  const bool extreme_op = op == RUA_MAX || op == RUA_MIN;
-  const bool phased = extreme_op && ties != nullptr;        // count phase, then apply phase
-  // ties_final: the forward already counted them (RUA_MAX_T / RUA_MIN_T) -> the apply phase alone, ONE walk
-  const int64_t max_u = split_max_extra(L.n_rows, split) * n_chunks;
-  // PROD keeps whole sequences: its zero-factor special case needs the zero count and the product of the other
-  // factors of the whole sequence, and a product combined by atomics would not be reproducible
-  const bool do_split = split > 0 && ws && max_u > 0 && (!extreme_op || phased) && op != RUA_PROD;
-  SplitWs W = {};
-  if (do_split) {
-    if (max_u > 0x7fffffffLL) return RUA_ERANGE;
-    W = carve_ws<A>(ws, max_u, split);
-  }
-  A* tp = (A*)ties;
-  if (tracing()) {
-    const bool pad = fill_padding && (L.kind == RUA_LEFT || L.kind == RUA_RIGHT);
-    const int tvs[2] = {phased ? (ties_final ? 2 : 1) : 0, 2};
-    for (int k = 0; k < (phased && !ties_final ? 2 : 1); ++k) {
-      trace_bwd<T>("seg_backward_kernel", EPL, op, false, tvs[k], n_chunks > 1, false, do_split, phased, ties_final, pad);
-      if (do_split)
-        trace_bwd<T>("seg_backward_tail_kernel", EPL, op, false, tvs[k], n_chunks > 1, false, true, phased, ties_final, pad);
-    }
-  }
-#define RUA_PHASE(OP, TIESV)                                                                                       \
-  {                                                                                                                \
-    if (do_split) {                                                                                                \
-      hipError_t e_ = hipMemsetAsync(W.ctr, 0, 4 * sizeof(unsigned long long), s);                                 \
-      if (e_ != hipSuccess) return (int)e_;                                                                        \
-      hipLaunchKernelGGL((seg_backward_kernel<T, EPL, OP, true, TIESV>), g, b, 0, s, L, perm, (const T*)data,      \
-                         (const T*)out, (const T*)gout, (T*)gin, H, lp_log2, n_chunks, extra_count, W, tp, sp);    \
-      hipLaunchKernelGGL((seg_backward_tail_kernel<T, EPL, OP, TIESV>), dim3(split_grid(max_u)), b, 0, s, L, perm, \
-                         (const T*)data, (const T*)out, (const T*)gout, (T*)gin, H, lp_log2, extra_count, W, tp, sp); \
-    } else {                                                                                                       \
-      hipLaunchKernelGGL((seg_backward_kernel<T, EPL, OP, false, TIESV>), g, b, 0, s, L, perm, (const T*)data,     \
-                         (const T*)out, (const T*)gout, (T*)gin, H, lp_log2, n_chunks, extra_count, W, tp, sp);    \
-    }                                                                                                              \
-  }
-#define RUA_EXTREME(OP)                                       \
-  if (phased && ties_final) RUA_PHASE(OP, 2)                  \
-  else if (phased) { RUA_PHASE(OP, 1) RUA_PHASE(OP, 2) } else RUA_PHASE(OP, 0)
-  switch (op) {
-    case RUA_SUM: RUA_PHASE(RUA_SUM, 0); break;
-    case RUA_MEAN: RUA_PHASE(RUA_MEAN, 0); break;
-    case RUA_MAX: RUA_EXTREME(RUA_MAX); break;
-    case RUA_MIN: RUA_EXTREME(RUA_MIN); break;
-    case RUA_PROD: RUA_PHASE(RUA_PROD, 0); break;
-    case RUA_LOGSUMEXP: RUA_PHASE(RUA_LOGSUMEXP, 0); break;
-    default: return RUA_EINVAL;
-  }
-#undef RUA_EXTREME
-#undef RUA_PHASE
-  return (int)hipGetLastError();
-}
-
-template <typename T>
-static int dispatch_backward(int op, hipStream_t s, const rua_layout& L, const int64_t* perm, const void* data,
-                             const void* out, const void* gout, void* gin, int64_t H, int extra_count,
-                             int64_t split, void* ws, void* ties, bool ties_final, const void* self_in,
-                             bool fill_padding) {
   constexpr int FULL = 16 / sizeof(T);
-  const uintptr_t ptrs = (uintptr_t)data | (uintptr_t)out | (uintptr_t)gout | (uintptr_t)gin | (uintptr_t)ties |
-                         (uintptr_t)self_in;
-  constexpr int HALF = FULL >= 4 ? FULL / 2 : 1;
-  const bool vec_ok = (H % FULL == 0) && (ptrs % 16 == 0);
-  const bool half_ok = !vec_ok && HALF > 1 && (H % HALF == 0) && (ptrs % 8 == 0);
-  const int epl = vec_ok ? FULL : half_ok ? HALF : 1;
-  const int64_t lpr = (H + epl - 1) / epl;
-  int lp_log2 = 0;
-  while ((1 << lp_log2) < lpr && lp_log2 < 6) ++lp_log2;
-  const int64_t n_chunks = (lpr + RUA_WAVE - 1) / RUA_WAVE;
-  const int64_t blocks = L.B * n_chunks;
-  if (blocks > 0x7fffffffLL) return RUA_ERANGE;
-  // one storage row at a time (seg_backward_rows_kernel): every op whose row gradient needs no walk over the sequence
-  const bool rows_op = op == RUA_SUM || op == RUA_MEAN || op == RUA_LOGSUMEXP ||
-                       ((op == RUA_MAX || op == RUA_MIN) && ties && ties_final);
-  // — for the BATCH-MAJOR layouts: consecutive storage rows there belong to one sequence and share its out / grad /
-  // ties rows (L1 hits); consecutive rows of a PackedSequence belong to 16 different sequences, each with its own
-  // three rows to fetch — measured 3.4 TB/s for sum over P against 6.0 for the walk, which loads them once per sequence
-  // (ops that read x: rows up to 1 KiB — one wave instruction per row; wider rows leave a wave one row of a 4-row
-  // tile and the walk's 4.4 TB/s beats 3.5)
-  // ([r5] every width: at rows wider than 1 KiB the waves of a workgroup take the column chunks of the same few rows)
-  const bool rows_width_ok = true;
-  const int tie_rule = extra_count & BWD_TIES_POSITIVE;
-  if (vec_ok && !perm && !self_in && !(extra_count & BWD_SELF_COUNTS) && rows_op && rows_width_ok && L.kind != RUA_PACK &&
-      H * (int64_t)sizeof(T) >= 64) {
-    const int64_t row_bytes = H * (int64_t)sizeof(T);
-    int tile_rows = BROWS_MAX;
-    for (int64_t tb = BROWS_MAX * row_bytes; tile_rows > 4 && tb > (16 << 10); tb >>= 1) tile_rows >>= 1;
-    const int64_t ntiles = (L.n_rows + tile_rows - 1) / tile_rows;
-    const bool span = ntiles >= 2048;
-    const int64_t per_xcd = span ? (ntiles + 7) / 8 : 0;
-    const int64_t grid = span ? per_xcd * 8 : ntiles;
-    if (grid > 0x7fffffffLL) return RUA_ERANGE;
-    const bool nt = (double)L.n_rows * (double)row_bytes >= (double)(512ll << 20);
-    const dim3 gg((unsigned)grid), bb(RUA_BLOCK);
-    using A = typename elem<T>::acc;
-    if (tracing())
-      trace_bwd<T>("seg_backward_rows_kernel", FULL, op, nt, 0, n_chunks > 1, span, false, false, ties_final, false);
-#define RUA_BROWS(OPV, NTV)                                                                                         \
-  if (n_chunks == 1)                                                                                                \
-    hipLaunchKernelGGL((seg_backward_rows_kernel<T, FULL, OPV, NTV, false>), gg, bb, 0, s, L, (const T*)data, (const T*)out,  \
-                       (const T*)gout, (T*)gin, H, lp_log2, 1, tile_rows, per_xcd, tie_rule, (const A*)ties);       \
-  else                                                                                                              \
-    hipLaunchKernelGGL((seg_backward_rows_kernel<T, FULL, OPV, NTV, true>), gg, bb, 0, s, L, (const T*)data, (const T*)out,  \
-                       (const T*)gout, (T*)gin, H, lp_log2, (int)n_chunks, tile_rows, per_xcd, tie_rule, (const A*)ties)
-#define RUA_BROWS_OP(NTV)                                 \
-  switch (op) {                                           \
-    case RUA_SUM: RUA_BROWS(RUA_SUM, NTV); break;         \
-    case RUA_MEAN: RUA_BROWS(RUA_MEAN, NTV); break;       \
-    case RUA_MAX: RUA_BROWS(RUA_MAX, NTV); break;         \
-    case RUA_MIN: RUA_BROWS(RUA_MIN, NTV); break;         \
-    default: RUA_BROWS(RUA_LOGSUMEXP, NTV); break;        \
-  }
-    if (nt) { RUA_BROWS_OP(true) } else { RUA_BROWS_OP(false) }
-#undef RUA_BROWS_OP
-#undef RUA_BROWS
-    return (int)hipGetLastError();
-  }
-  // the walk-per-sequence kernels write token rows only: zero the padding rows of a padded layout first when asked to
-  const bool pad_memset = fill_padding && (L.kind == RUA_LEFT || L.kind == RUA_RIGHT);
-  if (pad_memset) {
+  if (P.pad_memset) {
     const hipError_t e = hipMemsetAsync(gin, 0, (size_t)L.n_rows * (size_t)H * sizeof(T), s);
     if (e != hipSuccess) return (int)e;
   }
-  if (L.kind == RUA_PACK && L.sorted && !perm && (!ties || ties_final) && lp_log2 < 6 && !(split > 0 && ws) &&
-      !(extra_count & BWD_SELF_COUNTS) && !self_in && (L.B >> (6 - lp_log2)) >= RANKS_MIN_WAVES) {
-    // narrow rows of a PackedSequence: adjacent ranks share a wave instruction
-    const int64_t rpw = RUA_WAVE >> lp_log2;
-    const int64_t nblk = (L.B + rpw - 1) / rpw;
-    if (nblk > 0x7fffffffLL) return RUA_ERANGE;
-    const dim3 gg((unsigned)nblk), bb(RUA_WAVE);
-    if (tracing())
-      trace_bwd<T>("seg_backward_ranks_kernel", epl, op, false, ((op == RUA_MAX || op == RUA_MIN) && ties) ? 2 : 0, false,
-                   false, false, false, ties_final, pad_memset);
-#define RUA_BRANKS(EPLV, OPV, TV)                                                                                   \
-  hipLaunchKernelGGL((seg_backward_ranks_kernel<T, EPLV, OPV, TV>), gg, bb, 0, s, L, (const T*)data,              \
-                     (const T*)out, (const T*)gout, (T*)gin, H, lp_log2, tie_rule, (typename elem<T>::acc*)ties)
-#define RUA_BRANKS_OP(EPLV)                                     \
-  switch (op) {                                                 \
-    case RUA_SUM: RUA_BRANKS(EPLV, RUA_SUM, 0); break;          \
-    case RUA_MEAN: RUA_BRANKS(EPLV, RUA_MEAN, 0); break;        \
-    case RUA_MAX: if (ties) RUA_BRANKS(EPLV, RUA_MAX, 2); else RUA_BRANKS(EPLV, RUA_MAX, 0); break; \
-    case RUA_MIN: if (ties) RUA_BRANKS(EPLV, RUA_MIN, 2); else RUA_BRANKS(EPLV, RUA_MIN, 0); break; \
-    case RUA_PROD: RUA_BRANKS(EPLV, RUA_PROD, 0); break;        \
-    case RUA_LOGSUMEXP: RUA_BRANKS(EPLV, RUA_LOGSUMEXP, 0); break; \
-    default: return RUA_EINVAL;                                 \
-  }
-    if (vec_ok) { RUA_BRANKS_OP(FULL) } else if (half_ok) { RUA_BRANKS_OP(HALF) } else { RUA_BRANKS_OP(1) }
-#undef RUA_BRANKS_OP
-#undef RUA_BRANKS
-    return (int)hipGetLastError();
-  }
-  // whole sequences, no indirection, an op whose row gradient needs no counting walk: the lean walk (one wave per
-  // (sequence, column chunk) — a PackedSequence of wide rows, and x-reading ops over rows wider than 1 KiB)
-  if (!perm && !self_in && !(extra_count & BWD_SELF_COUNTS) && rows_op && !(split > 0 && ws)) {
-    const bool nt = (double)L.n_rows * (double)H * (double)sizeof(T) >= (double)(512ll << 20);
-    const dim3 gg((unsigned)blocks), bb(RUA_WAVE);
-    using A = typename elem<T>::acc;
-    if (tracing())
-      trace_bwd<T>("seg_backward_walk_kernel", epl, op, nt, 0, n_chunks > 1, false, false, false, ties_final, pad_memset);
-#define RUA_BWALK(EPLV, OPV, NTV)                                                                                   \
-  hipLaunchKernelGGL((seg_backward_walk_kernel<T, EPLV, OPV, NTV>), gg, bb, 0, s, L, (const T*)data, (const T*)out,  \
-                     (const T*)gout, (T*)gin, H, lp_log2, n_chunks, tie_rule, (const A*)ties)
-#define RUA_BWALK_OP(EPLV, NTV)                                 \
-  switch (op) {                                                 \
-    case RUA_SUM: RUA_BWALK(EPLV, RUA_SUM, NTV); break;         \
-    case RUA_MEAN: RUA_BWALK(EPLV, RUA_MEAN, NTV); break;       \
-    case RUA_MAX: RUA_BWALK(EPLV, RUA_MAX, NTV); break;         \
-    case RUA_MIN: RUA_BWALK(EPLV, RUA_MIN, NTV); break;         \
-    default: RUA_BWALK(EPLV, RUA_LOGSUMEXP, NTV); break;        \
-  }
-#define RUA_BWALK_NT(EPLV) if (nt) { RUA_BWALK_OP(EPLV, true) } else { RUA_BWALK_OP(EPLV, false) }
-    if (vec_ok) { RUA_BWALK_NT(FULL) } else if (half_ok) { RUA_BWALK_NT(HALF) } else { RUA_BWALK_NT(1) }
-#undef RUA_BWALK_NT
-#undef RUA_BWALK_OP
-#undef RUA_BWALK
-    return (int)hipGetLastError();
-  }
-  if (vec_ok)
-    return launch_backward<T, FULL>(op, (unsigned)blocks, s, L, perm, data, out, gout, gin, H, lp_log2, n_chunks,
-                                    extra_count, split, ws, ties, ties_final, self_in, fill_padding);
-  if (half_ok)
-    return launch_backward<T, HALF>(op, (unsigned)blocks, s, L, perm, data, out, gout, gin, H, lp_log2, n_chunks,
-                                    extra_count, split, ws, ties, ties_final, self_in, fill_padding);
-  return launch_backward<T, 1>(op, (unsigned)blocks, s, L, perm, data, out, gout, gin, H, lp_log2, n_chunks, extra_count,
-                               split, ws, ties, ties_final, self_in, fill_padding);
+  const T *xp = (const T*)data, *op_ = (const T*)out, *gp = (const T*)gout, *sp = (const T*)self_in;
+  T* ip = (T*)gin;
+  A* tp = (A*)ties;
+  const int lp_log2 = P.lp_log2, tie_rule = extra_count & BWD_TIES_POSITIVE;
+  const int64_t n_chunks = P.n_chunks;
+  SplitWs W = {};
+  if (P.do_split) W = carve_ws<A>(ws, P.max_u, P.split_rows);
+  const dim3 g(P.grid), b(RUA_WAVE);
+  hipError_t err = hipSuccess;
+  const int rc = with_op<false>(P.op, false, [&](auto op_c) {
+    constexpr int OP = decltype(op_c)::value;
+    constexpr bool EXTREME = OP == RUA_MAX || OP == RUA_MIN;
+    if (P.form == BWD_ROWS) {             // 16-byte lanes, ops whose row gradient needs no walk (plan_backward: rows_op)
+      if constexpr (OP != RUA_PROD)
+        with_bool(P.nt, [&](auto nt_c) {
+          with_bool(n_chunks > 1, [&](auto wide_c) {
+            hipLaunchKernelGGL((seg_backward_rows_kernel<T, FULL, OP, decltype(nt_c)::value, decltype(wide_c)::value>), g,
+                               dim3(RUA_BLOCK), 0, s, L, xp, op_, gp, ip, H, lp_log2, (int)n_chunks, P.tile_rows, P.per_xcd,
+                               tie_rule, (const A*)tp);
+          });
+        });
+      return;
+    }
+    with_epl<T>(P.epl, [&](auto epl_c) {
+      constexpr int EPL = decltype(epl_c)::value;
+      // one launch of the walk-per-sequence kernel (+ the published parts of long sequences) with the kernels' TIES
+      auto phase = [&](auto ties_c) {
+        constexpr int TIES = decltype(ties_c)::value;
+        if constexpr (TIES == 0 || EXTREME) {
+          if (P.form == BWD_RANKS) {
+            if constexpr (TIES != 1)
+              hipLaunchKernelGGL((seg_backward_ranks_kernel<T, EPL, OP, TIES>), g, b, 0, s, L, xp, op_, gp, ip, H, lp_log2,
+                                 tie_rule, tp);
+          } else if (P.do_split) {
+            err = hipMemsetAsync(W.ctr, 0, 4 * sizeof(unsigned long long), s);
+            if (err != hipSuccess) return;
+            hipLaunchKernelGGL((seg_backward_kernel<T, EPL, OP, true, TIES>), g, b, 0, s, L, perm, xp, op_, gp, ip, H,
+                               lp_log2, n_chunks, extra_count, W, tp, sp);
+            hipLaunchKernelGGL((seg_backward_tail_kernel<T, EPL, OP, TIES>), dim3(split_grid(P.max_u)), b, 0, s, L, perm,
+                               xp, op_, gp, ip, H, lp_log2, extra_count, W, tp, sp);
+          } else {
+            hipLaunchKernelGGL((seg_backward_kernel<T, EPL, OP, false, TIES>), g, b, 0, s, L, perm, xp, op_, gp, ip, H,
+                               lp_log2, n_chunks, extra_count, W, tp, sp);
+          }
+        }
+      };
+      if (P.form == BWD_WALK) {
+        if constexpr (OP != RUA_PROD)
+          with_bool(P.nt, [&](auto nt_c) {
+            hipLaunchKernelGGL((seg_backward_walk_kernel<T, EPL, OP, decltype(nt_c)::value>), g, b, 0, s, L, xp, op_, gp,
+                               ip, H, lp_log2, n_chunks, tie_rule, (const A*)tp);
+          });
+        return;
+      }
+      for (int k = 0; k < P.n_phases && err == hipSuccess; ++k)
+        if (P.tv[k] == 0) phase(int_c<0>{}); else if (P.tv[k] == 1) phase(int_c<1>{}); else phase(int_c<2>{});
+    });
+  });
+  if (err != hipSuccess) return (int)err;
+  return rc ? rc : (int)hipGetLastError();
 }
 
-// ---- per-dtype entry points: each element type is compiled in its own translation unit
-// (rua_reduce_<dtype>.hip) so the ~300 kernel instantiations build in parallel
-#define RUA_DECLARE_REDUCE_DTYPE(NAME)                                                                              \
-  int reduce_##NAME(int op, hipStream_t s, const rua_layout& L, const int64_t* perm, const void* data, void* out,  \
-                    int64_t H, int include_self, uint64_t empty_bits, void* extreme, int64_t split, void* ws,     \
-                    const rua_layout* CD, void* copy, void* ties, int hints);                                  \
-  int backward_##NAME(int op, hipStream_t s, const rua_layout& L, const int64_t* perm, const void* data,           \
-                      const void* out, const void* gout, void* gin, int64_t H, int extra_count, int64_t split,    \
-                      void* ws, void* ties, bool ties_final, const void* self_in, bool fill_padding);              \
-  int fill_empty_##NAME(hipStream_t s, const rua_layout& L, void* out, int64_t H, int want_max, void* ext,        \
-                        int reset);                                                                              \
-  int self_grad_##NAME(hipStream_t s, const int64_t* counts, int64_t S, int64_t H, const void* self_in,            \
-                       const void* out, const void* gout, const void* aux, void* gself, int op, int inc);
-RUA_DECLARE_REDUCE_DTYPE(f32)
-RUA_DECLARE_REDUCE_DTYPE(bf16)
-RUA_DECLARE_REDUCE_DTYPE(f16)
-RUA_DECLARE_REDUCE_DTYPE(f64)
+// ---- per-dtype entry points: each element type is compiled in its own translation unit (rua_reduce_<dtype>.hip) so
+// the ~300 kernel instantiations build in parallel; rua_reduce.hip reaches them through entry_for(dtype)
+struct ReduceEntry {
+  const char* name;         // as the dispatch trace spells the element type
+  int esize;
+  int (*reduce)(const ReducePlan& P, hipStream_t s, const rua_layout& L, const int64_t* perm, const void* data, void* out,
+                int64_t H, int include_self, uint64_t empty_bits, void* extreme, void* ws, const rua_layout* CD,
+                void* copy, void* ties);
+  int (*backward)(const BackwardPlan& P, hipStream_t s, const rua_layout& L, const int64_t* perm, const void* data,
+                  const void* out, const void* gout, void* gin, int64_t H, int extra_count, void* ws, void* ties,
+                  const void* self_in);
+  int (*fill_empty)(hipStream_t s, const rua_layout& L, void* out, int64_t H, int want_max, void* ext, int reset);
+  int (*self_grad)(hipStream_t s, const int64_t* counts, int64_t S, int64_t H, const void* self_in, const void* out,
+                   const void* gout, const void* aux, void* gself, int op, int inc);
+};
+const ReduceEntry &reduce_entry_f32(), &reduce_entry_bf16(), &reduce_entry_f16(), &reduce_entry_f64();
 
-#define RUA_DEFINE_REDUCE_DTYPE(NAME, T)                                                                            \
-  namespace rua {                                                                                                   \
-  int reduce_##NAME(int op, hipStream_t s, const rua_layout& L, const int64_t* perm, const void* data, void* out,  \
-                    int64_t H, int include_self, uint64_t empty_bits, void* extreme, int64_t split, void* ws,     \
-                    const rua_layout* CD, void* copy, void* ties, int hints) {                                 \
-    return dispatch_reduce<T>(op, s, L, perm, data, out, H, include_self, empty_bits, extreme, split, ws, CD,      \
-                              copy, ties, hints);                                                                  \
-  }                                                                                                                 \
-  int backward_##NAME(int op, hipStream_t s, const rua_layout& L, const int64_t* perm, const void* data,           \
-                      const void* out, const void* gout, void* gin, int64_t H, int extra_count, int64_t split,    \
-                      void* ws, void* ties, bool ties_final, const void* self_in, bool fill_padding) {             \
-    return dispatch_backward<T>(op, s, L, perm, data, out, gout, gin, H, extra_count, split, ws, ties, ties_final, \
-                                self_in, fill_padding);                                                            \
-  }                                                                                                                 \
-  int fill_empty_##NAME(hipStream_t s, const rua_layout& L, void* out, int64_t H, int want_max, void* ext,        \
-                        int reset) {                                                                             \
-    /* (the body strides over the batch: a capped grid; in the common case every workgroup reads one flag word) */ \
-    if (tracing()) {                                                                                                \
-      constexpr int VE = 16 / (int)sizeof(T);    /* fill_empty_body's own predicate */                              \
-      const bool wide = (H % VE) == 0 && ((uintptr_t)out & 15) == 0;                                                \
-      trace_fmt("fill_empty_kernel T=%s form=%s want_max=%d reset=%d", tname<T>(),                                  \
-                wide && H / VE <= 8 ? "narrow" : wide ? "ballot" : "ballot_scalar", want_max, reset);               \
-    }                                                                                                               \
-    hipLaunchKernelGGL(fill_empty_kernel<T>, dim3(grid_for(L.B) < 2048u ? (grid_for(L.B) ? grid_for(L.B) : 1u) : 2048u), dim3(RUA_BLOCK), 0, s, L, (T*)out, H, want_max,  \
-                       (unsigned long long*)ext, reset);                                                           \
-    return (int)hipGetLastError();                                                                                  \
-  }                                                                                                                 \
-  int self_grad_##NAME(hipStream_t s, const int64_t* counts, int64_t S, int64_t H, const void* self_in,            \
-                       const void* out, const void* gout, const void* aux, void* gself, int op, int inc) {         \
-    if (S * H > 0x7fffffffLL * RUA_BLOCK) return RUA_ERANGE;                                                        \
-    hipLaunchKernelGGL(scatter_self_grad_kernel<T>, dim3(grid_for(S * H)), dim3(RUA_BLOCK), 0, s, counts, S, H,    \
-                       (const T*)self_in, (const T*)out, (const T*)gout, aux, (T*)gself, op, inc);                 \
-    return (int)hipGetLastError();                                                                                  \
-  }                                                                                                                 \
+template <typename T>
+static int launch_fill_empty(hipStream_t s, const rua_layout& L, void* out, int64_t H, int want_max, void* ext, int reset) {
+  // (the body strides over the batch: a capped grid; in the common case every workgroup reads one flag word)
+  hipLaunchKernelGGL(fill_empty_kernel<T>, dim3(grid_for(L.B) < 2048u ? (grid_for(L.B) ? grid_for(L.B) : 1u) : 2048u),
+                     dim3(RUA_BLOCK), 0, s, L, (T*)out, H, want_max, (unsigned long long*)ext, reset);
+  return (int)hipGetLastError();
+}
+template <typename T>
+static int launch_self_grad(hipStream_t s, const int64_t* counts, int64_t S, int64_t H, const void* self_in,
+                            const void* out, const void* gout, const void* aux, void* gself, int op, int inc) {
+  if (S * H > 0x7fffffffLL * RUA_BLOCK) return RUA_ERANGE;
+  hipLaunchKernelGGL(scatter_self_grad_kernel<T>, dim3(grid_for(S * H)), dim3(RUA_BLOCK), 0, s, counts, S, H,
+                     (const T*)self_in, (const T*)out, (const T*)gout, aux, (T*)gself, op, inc);
+  return (int)hipGetLastError();
+}
+#define RUA_DEFINE_REDUCE_DTYPE(NAME, T)                                                                   \
+  const rua::ReduceEntry& rua::reduce_entry_##NAME() {                                                     \
+    static const ReduceEntry e = {#NAME, (int)sizeof(T), launch_reduce<T>, launch_backward<T>, launch_fill_empty<T>, \
+                                  launch_self_grad<T>};                                                    \
+    return e;                                                                                              \
   }
 
 }  // namespace rua
