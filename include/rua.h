@@ -393,6 +393,59 @@ int64_t rua_cumsum_ws_bytes(const rua_layout* lay, int64_t H, int32_t dtype);
 int rua_segment_cumsum(const rua_layout* lay, const void* data, void* out, int64_t H, int32_t dtype, int32_t reverse,
                        void* ws, void* stream);
 
+/* Per-sequence argmax / argmin with the selected values (an EXTENSION, added to ABI 6 — the version number did not
+ * move: the reference has no position-returning reduction; its users pad with -inf and call torch.argmax along dim 1).
+ * For every sequence b of `lay` (ANY layout) and column h, over t < len[b] (op = RUA_MAX or RUA_MIN, anything else:
+ * RUA_EINVAL):
+ *   index[b,h]  = the token position t — NOT a storage row: the same number in every layout — of the largest
+ *                 (smallest) data[row(b,t), h]; [B, H] int64 in batch order (PACK: original order, not sorted order)
+ *   values[b,h] = data[row(b, index[b,h]), h], in the payload dtype (values == NULL: positions only)
+ * under ONE total order on (value, position): a NaN beats every number, for max AND for min; otherwise the greater
+ * (smaller) value wins, +0.0 == -0.0; between equals (two NaNs included) the smaller position wins.  That is
+ * torch.max(seq, dim=0) / torch.min(seq, dim=0) of every sequence on its own (CPU torch).  An EMPTY sequence gives
+ * index -1 and the identity as its value: -inf (max) / +inf (min) in the float types, INT64_MIN / INT64_MAX for RUA_I64
+ * — no global `initial`, no `extreme` scratch, no rua_fill_empty: both outputs are written completely in the one pass
+ * (also when n_rows == 0; B == 0 and H == 0 return 0 without a launch).  RUA_F32 / RUA_F64 / RUA_BF16 / RUA_F16 (the 16-bit
+ * types compare after the exact widening to fp32) and RUA_I64; any other dtype: RUA_EINVAL.  The result is exact, and
+ * because the order is total the fold is associative and commutative: the bits depend on NOTHING but the sequence —
+ * not on the layout, the kernel form, the alignment or `ws`.  Padding rows of a LEFT / RIGHT input are never read;
+ * lengths are clamped to the storage and every row is range-checked.
+ * Three kernel forms, chosen as rua_segment_softmax chooses its own: rows of one vector (<= 16 bytes) put consecutive
+ * tokens on consecutive lanes, two sequences per wave, eight tokens in flight per lane; wider rows give a workgroup per
+ * (sequence x 128-byte column chunk), 32 rows x 4 in flight, combined by shuffles and through LDS; few but long sequences
+ * (fewer than 1 024 units whose length bound — CAT: T_log or n_rows, LEFT / RIGHT: T_phys, PACK: T — is at least 8 192)
+ * are cut into blocks of 2 048 tokens across workgroups when `ws` is given: every block leaves its (value, position) per
+ * column in `ws` and a finish launch combines them (two launches; the payload is still read once).
+ * rua_argreduce_ws_bytes(lay, H, dtype) =
+ *   B * ceil(bound / 2 048) * ceil(H * esize / 128) * (128 / esize) * (8 + (4, or 8 for RUA_F64 / RUA_I64))
+ * bytes when the cut form applies, else 0 (0 = never needed; ws == NULL = do not cut).  A CAT layout's T_log, where it
+ * is given (> 0), must be a TRUE upper bound of every length, as for rua_segment_softmax.
+ * `data` is only read; `values` / `index` must not overlap it.  Any alignment of `data` is accepted (narrower
+ * accesses).  While the dispatch trace is on (below) every launch records `seg_argreduce_lanes_kernel` or
+ * `seg_argreduce_rows_kernel` (cut=1 phase=partial|finish for the cut form) with key=value pairs (T=, op=, AL=,
+ * values=, kind=). */
+int64_t rua_argreduce_ws_bytes(const rua_layout* lay, int64_t H, int32_t dtype);
+int rua_segment_argreduce(const rua_layout* lay, const void* data, void* values /* NULL: indices only */,
+                          int64_t* index, int64_t H, int32_t dtype, int32_t op /* RUA_MAX | RUA_MIN */,
+                          void* ws, void* stream);
+/* The two row operators the autograd of the selected values is made of; each is the adjoint of the other (put is the
+ * backward of the values, take the backward of put, and so on: derivatives of any order).  `index` is a [B, H] int64
+ * tensor of token positions as rua_segment_argreduce writes it; elements move as bits, so both take the dtypes above
+ * (by element size) and are exact.
+ *   take:  out[b,h] = data[row(b, index[b,h]), h];  0 where index[b,h] < 0 or >= len[b].  [B, H], one thread per
+ *          element, written completely.  Trace: `seg_take_kernel`.
+ *   put:   out[row(b,t), h] = (t == index[b,h]) ? src[b,h] : 0 for EVERY token; padding rows of a LEFT / RIGHT `out`
+ *          are zeros: the whole payload is written once, with 16-byte stores where rows and base allow, and needs no
+ *          pre-zeroing.  A position that names no token of its sequence puts nothing.  The thread that owns a 16-byte
+ *          piece of a row loads its positions and source elements once per sequence; few but long sequences are cut
+ *          into blocks of 2 048 positions across workgroups (no workspace: a row needs nothing from another block).
+ *          Trace: `seg_put_kernel`.
+ * `out` must not alias `data` / `src` (RUA_EINVAL). */
+int rua_segment_take(const rua_layout* lay, const void* data, const int64_t* index, void* out,
+                     int64_t H, int32_t dtype, void* stream);
+int rua_segment_put(const rua_layout* lay, const void* src, const int64_t* index, void* out,
+                    int64_t H, int32_t dtype, void* stream);
+
 /* After rua_segment_reduce / rua_pack_reduce with `extreme` (MAX/MIN/LOGSUMEXP): write the
  * global extreme — the reduce left it in the scratch — into the rows of empty sequences, or NaN into every row when
  * the NaN flag is up (the reference's initial=NaN behaviour).  Every workgroup patches its share of the batch.

@@ -89,6 +89,11 @@ SYMBOLS = {
                                              c_int32, c_void_p, c_void_p]),
     'rua_cumsum_ws_bytes': (c_int64, [POINTER(RuaLayout), c_int64, c_int32]),
     'rua_segment_cumsum': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
+    'rua_argreduce_ws_bytes': (c_int64, [POINTER(RuaLayout), c_int64, c_int32]),
+    'rua_segment_argreduce': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p,
+                                      c_void_p]),
+    'rua_segment_take': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
+    'rua_segment_put': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
     'rua_fill_empty': (c_int, [POINTER(RuaLayout), c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
     'rua_bucket_ws_elems': (c_int64, [c_int64, c_int64]),
     'rua_index_buckets': (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -499,6 +499,163 @@ def cumsum(data: Tensor, lay: M.Lay, reverse: bool, hidden) -> Tensor:
     return launch_cumsum(lay, data.detach() if data.requires_grad else data, bool(reverse), tuple(hidden))
 
 
+# ------------------------------------------------------------------ per-sequence argmax / argmin (an extension)
+def _argreduce_dtype(data: Tensor) -> int:
+    if data.dtype not in L.SCAN_DTYPES:
+        L.require_device(data)
+        raise L.RuaError(f'argmax / argmin support {list(L.SCAN_DTYPES)}; got {data.dtype}')
+    return L.SCAN_DTYPES[data.dtype]
+
+
+def launch_argreduce(lay: M.Lay, data: Tensor, op: int, hidden: Tuple[int, ...], want_values: bool = True,
+                     cut: bool = True) -> Tuple[Optional[Tensor], Tensor]:
+    """rua_segment_argreduce: (values or None, index), both [B, *hidden] and written completely by the call — one launch
+    (two for cut sequences), one read of the payload.  cut=False withholds the workspace (the same bits from one
+    workgroup per unit: a developer A/B)."""
+    dev = L.require_device(data)
+    code = _argreduce_dtype(data)
+    if op not in (L.MAX, L.MIN):
+        raise L.RuaError('argreduce: the operator is MAX or MIN')
+    lib = L.load()
+    H = _prod(hidden)
+    nbytes = lib.rua_argreduce_ws_bytes(lay.ref(), H, code) if cut else 0    # > 0: few but long sequences get cut
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    data = data.contiguous()
+    shape = (lay.B,) + tuple(hidden)
+    index = torch.empty(shape, dtype=torch.int64, device=dev)
+    values = torch.empty(shape, dtype=data.dtype, device=dev) if want_values else None
+    name = ('seq_max' if op == L.MAX else 'seq_min') if want_values else ('argmax' if op == L.MAX else 'argmin')
+    if _kernel_hook:
+        _kernel_hook(name, True)
+    L.check(lib.rua_segment_argreduce(lay.ref(), L.ptr(data), L.ptr(values), L.ptr(index), H, code, op, L.ptr(ws),
+                                      L.stream_ptr(dev)), 'rua_segment_argreduce')
+    if _kernel_hook:
+        _kernel_hook(name, False)
+    return values, index
+
+
+def _index_arg(lay: M.Lay, index: Tensor, hidden: Tuple[int, ...], dev) -> Tensor:
+    L.require_device(index)
+    if index.dtype != torch.int64 or index.device != dev or tuple(index.shape) != (lay.B,) + tuple(hidden):
+        raise L.RuaError('take / put: the index is a [B, *hidden] int64 tensor on the payload\'s device')
+    return index.contiguous()
+
+
+def launch_take(lay: M.Lay, data: Tensor, index: Tensor, hidden: Tuple[int, ...]) -> Tensor:
+    """rua_segment_take: out[b, h] = data[row(b, index[b, h]), h], 0 where the position names no token of b."""
+    dev = L.require_device(data)
+    code = _argreduce_dtype(data)
+    lib = L.load()
+    index = _index_arg(lay, index, hidden, dev)
+    data = data.contiguous()
+    out = torch.empty((lay.B,) + tuple(hidden), dtype=data.dtype, device=dev)
+    if _kernel_hook:
+        _kernel_hook('take', True)
+    L.check(lib.rua_segment_take(lay.ref(), L.ptr(data), L.ptr(index), L.ptr(out), _prod(hidden), code,
+                                 L.stream_ptr(dev)), 'rua_segment_take')
+    if _kernel_hook:
+        _kernel_hook('take', False)
+    return out
+
+
+def launch_put(lay: M.Lay, src: Tensor, index: Tensor, hidden: Tuple[int, ...], shape: Sequence[int],
+               out: Optional[Tensor] = None) -> Tensor:
+    """rua_segment_put: a payload of storage shape `shape` that holds src[b, h] at token index[b, h] of sequence b and
+    zeros everywhere else, padding rows included — written completely by the call (no pre-zeroing)."""
+    dev = L.require_device(src)
+    code = _argreduce_dtype(src)
+    lib = L.load()
+    index = _index_arg(lay, index, hidden, dev)
+    if tuple(src.shape) != (lay.B,) + tuple(hidden):
+        raise L.RuaError('put: the source is a [B, *hidden] tensor')
+    src = src.contiguous()
+    if out is None:
+        out = torch.empty(tuple(shape), dtype=src.dtype, device=dev)
+    elif not out.is_contiguous() or out.dtype != src.dtype or tuple(out.shape) != tuple(shape):
+        raise L.RuaError('put target must be contiguous, of the source dtype and of the payload shape')
+    if _kernel_hook:
+        _kernel_hook('put', True)
+    L.check(lib.rua_segment_put(lay.ref(), L.ptr(src), L.ptr(index), L.ptr(out), _prod(hidden), code,
+                                L.stream_ptr(dev)), 'rua_segment_put')
+    if _kernel_hook:
+        _kernel_hook('put', False)
+    return out
+
+
+class _ArgReduce(torch.autograd.Function):
+    """(values, index) of every sequence's largest / smallest token.  Saves ONLY the [B, *H] index; the gradient goes
+    to the chosen token whole (torch.max(dim)'s rule, not torch.segment_reduce's split among ties): put(grad, index)."""
+
+    @staticmethod
+    def forward(ctx, data: Tensor, lay: M.Lay, op: int, hidden):
+        values, index = launch_argreduce(lay, data, op, hidden)
+        ctx.lay, ctx.hidden, ctx.shape = lay, tuple(hidden), tuple(data.shape)
+        ctx.save_for_backward(index)
+        ctx.mark_non_differentiable(index)
+        return values, index
+
+    @staticmethod
+    def backward(ctx, grad: Tensor, _grad_index):
+        index, = ctx.saved_tensors
+        return put(grad, index, ctx.lay, ctx.hidden, ctx.shape), None, None, None
+
+
+class _Put(torch.autograd.Function):
+    """src [B, *H] -> payload: linear in src, its adjoint is take at the same index."""
+
+    @staticmethod
+    def forward(ctx, src: Tensor, index: Tensor, lay: M.Lay, hidden, shape):
+        ctx.lay, ctx.hidden = lay, tuple(hidden)
+        ctx.save_for_backward(index)
+        return launch_put(lay, src, index, hidden, shape)
+
+    @staticmethod
+    def backward(ctx, grad: Tensor):
+        index, = ctx.saved_tensors
+        return take(grad, index, ctx.lay, ctx.hidden), None, None, None, None
+
+
+class _Take(torch.autograd.Function):
+    """payload -> [B, *H]: linear in the payload, its adjoint is put at the same index."""
+
+    @staticmethod
+    def forward(ctx, data: Tensor, index: Tensor, lay: M.Lay, hidden):
+        ctx.lay, ctx.hidden, ctx.shape = lay, tuple(hidden), tuple(data.shape)
+        ctx.save_for_backward(index)
+        return launch_take(lay, data, index, hidden)
+
+    @staticmethod
+    def backward(ctx, grad: Tensor):
+        index, = ctx.saved_tensors
+        return put(grad, index, ctx.lay, ctx.hidden, ctx.shape), None, None, None
+
+
+def _wants_grad(t: Tensor) -> bool:
+    return t.is_floating_point() and t.requires_grad and torch.is_grad_enabled()
+
+
+def argreduce(data: Tensor, lay: M.Lay, op: int, hidden, want_values: bool = True) -> Tuple[Optional[Tensor], Tensor]:
+    _argreduce_dtype(data)
+    if want_values and _wants_grad(data):
+        # contiguous HERE, before the Function (as in reduce()): a copy made inside forward() would carry no history
+        return _ArgReduce.apply(data.contiguous(), lay, op, tuple(hidden))
+    return launch_argreduce(lay, data.detach() if data.requires_grad else data, op, tuple(hidden), want_values)
+
+
+def put(src: Tensor, index: Tensor, lay: M.Lay, hidden, shape) -> Tensor:
+    _argreduce_dtype(src)
+    if _wants_grad(src):
+        return _Put.apply(src.contiguous(), index, lay, tuple(hidden), tuple(shape))
+    return launch_put(lay, src.detach() if src.requires_grad else src, index, tuple(hidden), tuple(shape))
+
+
+def take(data: Tensor, index: Tensor, lay: M.Lay, hidden) -> Tensor:
+    _argreduce_dtype(data)
+    if _wants_grad(data):
+        return _Take.apply(data.contiguous(), index, lay, tuple(hidden))
+    return launch_take(lay, data.detach() if data.requires_grad else data, index, tuple(hidden))
+
+
 # ------------------------------------------------------------------ scatter-sum of rows (adjoint of a row gather)
 def index_buckets(index: Tensor, S: int) -> Tuple[Tensor, Tensor]:
     """(counts[S], perm[M]): the entries of `index` bucketed by destination, every bucket in ascending entry order

@@ -1,0 +1,94 @@
+"""Per-sequence argmax / argmin over the tokens of any container (C / L / P / R) — an extension, like softmax and cumsum:
+the reference answers "how large is the largest token of each sequence" (`reduce_max`, `segment_max`) but not "which
+token is it".  Its users spell it as
+
+    l = z.left(fill_value=-inf)
+    idx = l.data.argmax(dim=1)
+
+— a copy of the payload plus the padding followed by an ATen kernel, the wrong answer for a sequence that holds only
+-inf, and nothing at all for a PackedSequence.  Here it is ONE fused HIP kernel (rua_segment_argreduce;
+csrc/rua_argreduce.hip), identical for the four layouts:
+
+    argmax(z)[b, h]  = the token position t in [0, len[b]) of the largest z[b, t, h]      LongTensor [B, *H]
+    seq_max(z)       = (values, indices), a namedtuple like torch.max(dim)
+
+The index is a position inside the sequence, not a storage row: `z.argmax()` is the same tensor for `z.cat()`,
+`z.pack()`, `z.left()` and `z.right()`, in batch order (a PackedSequence: original order).  Ties go to the smallest t, a
+NaN beats every number (for argmin too) and the first NaN wins, +0.0 == -0.0 — `torch.max(seq, dim=0)` of every sequence
+on its own.  An empty sequence gives -1, and the identity as its value (-inf / +inf; INT64_MIN / INT64_MAX).  float32 /
+float64 / bfloat16 / float16 and int64; the result is exact.
+
+The values of `seq_max` / `seq_min` are differentiable: the gradient goes to the chosen token whole — `torch.max(dim)`'s
+rule, where `reduce_max` splits it among ties as `torch.segment_reduce` does.  Autograd saves only the [B, *H] index; the
+backward is rua_segment_put, whose own backward is rua_segment_take and so on: derivatives of any order.
+"""
+from typing import NamedTuple, Tuple
+
+from torchrua_amd import _lib as K
+from torchrua_amd import _meta as M
+from torchrua_amd import _ops as O
+from torchrua_amd.layout import C, L, P, R, T, Z, describe
+
+__all__ = ['segment_argmax', 'segment_argmin', 'argmax', 'argmin', 'seq_max', 'seq_min']
+
+
+class SeqExtreme(NamedTuple):
+    """What seq_max / seq_min return: both [B, *H]."""
+    values: T
+    indices: T
+
+
+def _segment(tensor: T, segment_sizes: T, op: int) -> T:
+    K.require_device(tensor, segment_sizes)
+    lay = M.lay_cat(segment_sizes, segment_sizes.numel(), int(tensor.size(0)))
+    return O.argreduce(tensor, lay, op, tuple(tensor.shape[1:]), want_values=False)[1]
+
+
+def segment_argmax(tensor: T, segment_sizes: T) -> T:
+    """The position, inside every run of `segment_sizes` rows of `tensor`, of the run's largest row element
+    (the signature of segment_max); LongTensor [S, *H], -1 for an empty run."""
+    return _segment(tensor, segment_sizes, K.MAX)
+
+
+def segment_argmin(tensor: T, segment_sizes: T) -> T:
+    """The position, inside every run of `segment_sizes` rows of `tensor`, of the run's smallest row element."""
+    return _segment(tensor, segment_sizes, K.MIN)
+
+
+def _lay_hidden(sequence: Z) -> Tuple[M.Lay, Tuple[int, ...]]:
+    data = sequence.data
+    K.require_device(data)
+    if isinstance(sequence, P):
+        return M.lay_pack(sequence), tuple(data.shape[1:])
+    return describe(sequence), tuple(data.shape[1:]) if isinstance(sequence, C) else tuple(data.shape[2:])
+
+
+def argmax(sequence: Z) -> T:
+    """The token position of every sequence's largest element, per column: LongTensor [B, *H]; -1 where empty."""
+    lay, hidden = _lay_hidden(sequence)
+    return O.argreduce(sequence.data, lay, K.MAX, hidden, want_values=False)[1]
+
+
+def argmin(sequence: Z) -> T:
+    """The token position of every sequence's smallest element, per column: LongTensor [B, *H]; -1 where empty."""
+    lay, hidden = _lay_hidden(sequence)
+    return O.argreduce(sequence.data, lay, K.MIN, hidden, want_values=False)[1]
+
+
+def seq_max(sequence: Z) -> SeqExtreme:
+    """(values, indices) of every sequence's largest element, like torch.max(dim); the values are differentiable."""
+    lay, hidden = _lay_hidden(sequence)
+    return SeqExtreme(*O.argreduce(sequence.data, lay, K.MAX, hidden))
+
+
+def seq_min(sequence: Z) -> SeqExtreme:
+    """(values, indices) of every sequence's smallest element, like torch.min(dim); the values are differentiable."""
+    lay, hidden = _lay_hidden(sequence)
+    return SeqExtreme(*O.argreduce(sequence.data, lay, K.MIN, hidden))
+
+
+for _cls in (C, L, P, R):
+    _cls.argmax = argmax
+    _cls.argmin = argmin
+    _cls.max = seq_max
+    _cls.min = seq_min
