@@ -393,6 +393,62 @@ int64_t rua_cumsum_ws_bytes(const rua_layout* lay, int64_t H, int32_t dtype);
 int rua_segment_cumsum(const rua_layout* lay, const void* data, void* out, int64_t H, int32_t dtype, int32_t reverse,
                        void* ws, void* stream);
 
+/* Per-sequence gated linear recurrence (an EXTENSION, added to ABI 6 — the version number did not move: the reference's
+ * users pad, loop over the time steps with elementwise kernels and cast back).  For every sequence b of `lay` (ANY
+ * layout) and column h, with u the position along the scan (u = t; reverse != 0: u = len - 1 - t):
+ *   h_0 = x_0                              (the gate at scan position 0 is NEVER read into the result)
+ *   h_u = a_u * h_(u-1) + x_u   for u >= 1
+ * so reverse != 0 is the return recursion G_t = r_t + a_t * G_(t+1).  Forward ignores the gate of the first token,
+ * reverse the gate of the last one: a NaN or an infinity there reaches no output.  Sequences and columns are
+ * independent; a NaN stays in its own sequence and column, at or after the position where it entered.
+ * `gate` is a tensor of exactly the payload's storage shape and dtype, or NULL: then `gate_scalar` is the gate of every
+ * position, passed by value and held in the accumulator type (no gate tensor is read).  RUA_F32 / RUA_F64 / RUA_BF16 /
+ * RUA_F16 — bf16 / f16 accumulate in fp32, gate included (fp64 for RUA_F64), every output element rounded once; any
+ * other dtype (integers included): RUA_EINVAL.  B == 0, H == 0 and n_rows == 0 return 0 without a launch.  Padding rows
+ * of a LEFT / RIGHT result are written as zeros in the same pass and padding rows of the inputs are never read.  Lengths
+ * are clamped to the storage and every row is range-checked.  Argument checks and error codes are those of
+ * rua_segment_cumsum.
+ * ONE association order: the operator is associative on pairs (A, B); an EARLIER (A1, B1) and a LATER (A2, B2) combine
+ * as (A2 * A1, A2 * B1 + B2), never contracted into an fma.  Position u enters as (a_u, x_u), position 0 as (1, x_0).
+ * The pairs are combined in rua_segment_cumsum's order, unchanged (groups of 8 by three doubling steps, tiles of 4
+ * groups, blocks of 64 tiles whose carry starts afresh, the base of a block from the totals of the blocks before it;
+ *   out = B of (((base . carry) . groups before) . prefix inside the group)),
+ * for every layout, kernel form, alignment and `ws`.  A term that does not exist is the pair (1, -0.0).  Hence, BIT FOR
+ * BIT: the operator commutes with the casts; `reverse` equals reversing every sequence (payload and gate), scanning
+ * forward and reversing back; cut == uncut; aligned == unaligned; a gate that is exactly 1 everywhere gives
+ * rua_segment_cumsum's result; a scalar gate equals a tensor filled with it.
+ * LIMIT: a blocked scan forms partial gate products.  The result is finite only if the product of the gates over any
+ * aligned group, tile or block (and over the blocks before a block) is representable in the accumulator type.
+ * Kernel forms and the cut rule are those of rua_segment_cumsum (rows of one vector: lanes along time; wider rows: a
+ * workgroup per (sequence x 128-byte chunk); fewer than 1 024 units with a length bound of at least 8 192: cut into
+ * blocks across workgroups when `ws` is given — two launches, payload and gate read twice).  The workspace holds an
+ * (A, B) pair per block and column: rua_linear_scan_ws_bytes == 2 * rua_cumsum_ws_bytes (0 for rows of one vector and
+ * for dtypes the scan does not take).  Payload and gate are read once (twice when cut), the result is written once;
+ * no slab, no temporaries.
+ * Aliasing: `out` may equal `data` (every row is read before it is written, by the same thread); it must not be `gate`
+ * (RUA_EINVAL).
+ * rua_segment_linear_scan_backward: from the cotangent `grad_out`, the gate and the forward's OUTPUT `h` (the payload is
+ * not needed), for the scan whose direction was `reverse`:
+ *   grad_x    = the same recurrence run the OTHER way over grad_out, the gate of a position taken from the previous
+ *               position of that scan (forward: dx_t = g_t + a_(t+1) * dx_(t+1)) — which drops exactly the gate the
+ *               forward ignored;
+ *   grad_gate = grad_x * h at the forward's previous position (forward: da_t = dx_t * h_(t-1)), exactly 0 at the
+ *               ignored gate; both factors in the accumulator type, rounded once.  grad_gate == NULL: not computed (and
+ *               `h` is not read: it may be NULL); with gate == NULL (a scalar gate has no gradient) it MUST be NULL.
+ * Padding rows of both gradients are zeros.  `grad_x` may equal `grad_out`; it must not be `gate` or `h`; `grad_gate`
+ * must not be anything that is read, nor `grad_x` (RUA_EINVAL).  The shifted gate and `h` are loaded from the
+ * neighbouring token's row: lines the neighbouring threads load anyway, no second pass.
+ * While the dispatch trace is on (below) every launch records `seg_linear_scan_lanes_kernel` or
+ * `seg_linear_scan_rows_kernel` with key=value pairs: T=, AL=, rev= (the direction this launch scans in: the backward
+ * of a forward scan records rev=1), kind=, gate=scalar|tensor, bwd=, cut= (and phase=partial|finish for the cut form). */
+int64_t rua_linear_scan_ws_bytes(const rua_layout* lay, int64_t H, int32_t dtype);
+int rua_segment_linear_scan(const rua_layout* lay, const void* data, const void* gate /* NULL: scalar */,
+                            double gate_scalar, void* out, int64_t H, int32_t dtype, int32_t reverse, void* ws,
+                            void* stream);
+int rua_segment_linear_scan_backward(const rua_layout* lay, const void* grad_out, const void* gate /* NULL: scalar */,
+                                     double gate_scalar, const void* h, void* grad_x, void* grad_gate /* NULL */,
+                                     int64_t H, int32_t dtype, int32_t reverse, void* ws, void* stream);
+
 /* Per-sequence argmax / argmin with the selected values (an EXTENSION, added to ABI 6 — the version number did not
  * move: the reference has no position-returning reduction; its users pad with -inf and call torch.argmax along dim 1).
  * For every sequence b of `lay` (ANY layout) and column h, over t < len[b] (op = RUA_MAX or RUA_MIN, anything else:

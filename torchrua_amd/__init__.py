@@ -18,6 +18,7 @@ from torchrua_amd.compose import *  # noqa: F401,F403
 from torchrua_amd.detach import *  # noqa: F401,F403
 from torchrua_amd.softmax import *  # noqa: F401,F403
 from torchrua_amd.cumsum import *  # noqa: F401,F403
+from torchrua_amd.linear_scan import *  # noqa: F401,F403
 from torchrua_amd.argmax import *  # noqa: F401,F403
 from torchrua_amd._lib import RuaError, load as load_library  # noqa: F401
 

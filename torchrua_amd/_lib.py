@@ -7,7 +7,7 @@ streams; every kernel is launched through the plain-pointer C ABI on torch's cur
 import ctypes
 import os
 import threading
-from ctypes import POINTER, Structure, c_char_p, c_int, c_int32, c_int64, c_uint64, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_int, c_int32, c_int64, c_uint64, c_void_p
 
 import torch  # noqa: F401  (must be imported first: maps the HIP runtime our library binds to)
 
@@ -89,6 +89,11 @@ SYMBOLS = {
                                              c_int32, c_void_p, c_void_p]),
     'rua_cumsum_ws_bytes': (c_int64, [POINTER(RuaLayout), c_int64, c_int32]),
     'rua_segment_cumsum': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
+    'rua_linear_scan_ws_bytes': (c_int64, [POINTER(RuaLayout), c_int64, c_int32]),
+    'rua_segment_linear_scan': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_double, c_void_p, c_int64, c_int32,
+                                        c_int32, c_void_p, c_void_p]),
+    'rua_segment_linear_scan_backward': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_double, c_void_p, c_void_p,
+                                                 c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
     'rua_argreduce_ws_bytes': (c_int64, [POINTER(RuaLayout), c_int64, c_int32]),
     'rua_segment_argreduce': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p,
                                       c_void_p]),

@@ -499,6 +499,159 @@ def cumsum(data: Tensor, lay: M.Lay, reverse: bool, hidden) -> Tensor:
     return launch_cumsum(lay, data.detach() if data.requires_grad else data, bool(reverse), tuple(hidden))
 
 
+# ------------------------------------------------------------------ per-sequence gated linear recurrence (an extension)
+def _linear_scan_dtype(data: Tensor) -> int:
+    if data.dtype not in L.DTYPES:
+        L.require_device(data)
+        raise L.RuaError(f'linear_scan supports {list(L.DTYPES)}; got {data.dtype}')
+    return L.DTYPES[data.dtype]
+
+
+def _gate_arg(data: Tensor, gate) -> Tuple[Optional[Tensor], float]:
+    """(the gate tensor or None, the scalar gate): a tensor of the payload's storage shape, dtype and device, or ONE
+    Python number — checked before any launch."""
+    if isinstance(gate, Tensor):
+        L.require_device(data, gate)
+        if gate.dtype != data.dtype:
+            raise L.RuaError(f'linear_scan: the gate has dtype {gate.dtype}, the payload {data.dtype}')
+        if gate.shape != data.shape:
+            raise L.RuaError(f'linear_scan: the gate has shape {tuple(gate.shape)}, the payload\'s storage '
+                             f'{tuple(data.shape)} (gates do not broadcast)')
+        return gate, 0.0
+    if isinstance(gate, bool) or not isinstance(gate, (int, float)):
+        raise L.RuaError('linear_scan: the gate is a tensor of the payload\'s storage shape, a container of the same type '
+                         f'or a Python float; got {type(gate).__name__}')
+    return None, float(gate)
+
+
+def launch_linear_scan(lay: M.Lay, data: Tensor, gate, reverse: bool, hidden: Tuple[int, ...],
+                       out: Optional[Tensor] = None, cut: bool = True) -> Tensor:
+    """rua_segment_linear_scan: h_u = a_u * h_(u-1) + x_u in one launch (two for cut sequences); payload and gate are
+    read once, the result is written once.  `gate` is a tensor or a Python float (passed by value: no gate tensor
+    exists).  `out` may be `data` itself, never the gate.  cut=False withholds the workspace (the same bits from one
+    workgroup per unit: a developer A/B)."""
+    dev = L.require_device(data)
+    code = _linear_scan_dtype(data)
+    gt, gs = _gate_arg(data, gate)
+    lib = L.load()
+    H = _prod(hidden)
+    nbytes = lib.rua_linear_scan_ws_bytes(lay.ref(), H, code) if cut else 0      # > 0: few but long sequences get cut
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    data = data.contiguous()
+    gt = None if gt is None else gt.contiguous()
+    if out is None:
+        out = torch.empty(data.shape, dtype=data.dtype, device=dev)      # padding rows: zeroed by the call
+    elif not out.is_contiguous() or out.dtype != data.dtype or out.shape != data.shape:
+        raise L.RuaError('linear_scan target must be contiguous, of the payload dtype and of the payload shape')
+    name = 'linear_scan_rev' if reverse else 'linear_scan'
+    if _kernel_hook:
+        _kernel_hook(name, True)
+    L.check(lib.rua_segment_linear_scan(lay.ref(), L.ptr(data), L.ptr(gt), gs, L.ptr(out), H, code, int(bool(reverse)),
+                                        L.ptr(ws), L.stream_ptr(dev)), 'rua_segment_linear_scan')
+    if _kernel_hook:
+        _kernel_hook(name, False)
+    return out
+
+
+def launch_linear_scan_backward(lay: M.Lay, grad: Tensor, gate, h: Optional[Tensor], reverse: bool,
+                                hidden: Tuple[int, ...], want_gate: bool = True,
+                                cut: bool = True) -> Tuple[Tensor, Optional[Tensor]]:
+    """rua_segment_linear_scan_backward: (grad_x, grad_gate or None) of the scan whose direction was `reverse`, from the
+    cotangent, the gate and the saved output `h` — one launch (two for cut sequences).  Padding rows of both are zeros."""
+    dev = L.require_device(grad)
+    code = _linear_scan_dtype(grad)
+    gt, gs = _gate_arg(grad, gate)
+    want_gate = bool(want_gate) and gt is not None
+    if want_gate:
+        L.require_device(grad, h)
+        if h is None or h.dtype != grad.dtype or h.shape != grad.shape:
+            raise L.RuaError('linear_scan backward: the saved output must have the dtype and shape of the cotangent')
+        h = h.contiguous()
+    lib = L.load()
+    H = _prod(hidden)
+    nbytes = lib.rua_linear_scan_ws_bytes(lay.ref(), H, code) if cut else 0
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    grad = grad.contiguous()
+    gt = None if gt is None else gt.contiguous()
+    gx = torch.empty(grad.shape, dtype=grad.dtype, device=dev)
+    ga = torch.empty(grad.shape, dtype=grad.dtype, device=dev) if want_gate else None
+    name = 'linear_scan_rev_bwd' if reverse else 'linear_scan_bwd'
+    if _kernel_hook:
+        _kernel_hook(name, True)
+    L.check(lib.rua_segment_linear_scan_backward(lay.ref(), L.ptr(grad), L.ptr(gt), gs, L.ptr(h if want_gate else None),
+                                                 L.ptr(gx), L.ptr(ga), H, code, int(bool(reverse)), L.ptr(ws),
+                                                 L.stream_ptr(dev)), 'rua_segment_linear_scan_backward')
+    if _kernel_hook:
+        _kernel_hook(name, False)
+    return gx, ga
+
+
+class _LinearScan(torch.autograd.Function):
+    """h = the gated linear recurrence of every sequence.  Saves the gate and the OUTPUT (not the payload); the
+    backward is one fused kernel: the same recurrence run the other way, and grad_gate = grad_x * the neighbouring h."""
+
+    @staticmethod
+    def forward(ctx, data: Tensor, gate: Optional[Tensor], gate_scalar: float, lay: M.Lay, reverse: bool, hidden):
+        h = launch_linear_scan(lay, data, gate_scalar if gate is None else gate, reverse, hidden)
+        ctx.lay, ctx.reverse, ctx.hidden, ctx.gate_scalar, ctx.has_gate = lay, reverse, tuple(hidden), gate_scalar, gate is not None
+        if gate is None:
+            ctx.save_for_backward(h)
+        else:
+            ctx.save_for_backward(h, gate)
+        return h
+
+    @staticmethod
+    def backward(ctx, grad: Tensor):
+        h = ctx.saved_tensors[0]
+        gate = ctx.saved_tensors[1] if ctx.has_gate else None
+        want_gate = ctx.has_gate and ctx.needs_input_grad[1]
+        if torch.is_grad_enabled():
+            # a graph of this backward is being recorded (create_graph=True): the gradient spelled with the library's
+            # differentiable pieces (the scan itself and the roll), as _composed_softmax_grad does
+            gx, ga = _composed_linear_scan_grad(grad, gate, ctx.gate_scalar, h, ctx.lay, ctx.reverse, ctx.hidden, want_gate)
+        else:
+            gx, ga = launch_linear_scan_backward(ctx.lay, grad, ctx.gate_scalar if gate is None else gate, h, ctx.reverse,
+                                                 ctx.hidden, want_gate)
+        return gx, ga, None, None, None, None
+
+
+def _composed_linear_scan_grad(grad: Tensor, gate: Optional[Tensor], gate_scalar: float, h: Tensor, lay: M.Lay,
+                               reverse: bool, hidden, want_gate: bool):
+    """(d / d payload, d / d gate) as differentiable functions of (grad, gate, h).  roll(a, -1) puts the wrapped-around
+    gate exactly on the position the reverse scan ignores, so dx = linear_scan(g, roll(a, -1), reverse=True); and
+    da = dx * roll(h, 1) with position 0 masked (mirrored for the reverse scan)."""
+    def roll(v: Tensor, shifts: int) -> Tensor:
+        return move(v.contiguous(), MovePlan(lay, lay, tuple(v.shape), L.T_ROLL, shifts, fill=0, name='roll'))
+
+    if gate is None:
+        return linear_scan(grad.contiguous(), gate_scalar, lay, not reverse, hidden), None
+    step = 1 if reverse else -1
+    dx = linear_scan(grad.contiguous(), roll(gate, step), lay, not reverse, hidden)
+    if not want_gate:
+        return dx, None
+    # the token whose gate the scan ignored: the first one (the last one for `reverse`)
+    ones = torch.ones((lay.B,) + tuple(hidden), dtype=h.dtype, device=h.device)
+    zero_pos = torch.zeros((lay.B,) + tuple(hidden), dtype=torch.int64, device=h.device)
+    ignored = launch_put(lay, ones, zero_pos, tuple(hidden), tuple(h.shape))
+    if reverse:
+        ignored = launch_move(MovePlan(lay, lay, tuple(h.shape), L.T_ROLL, -1, fill=0, name='roll'), ignored)
+    da = torch.where(ignored != 0, torch.zeros_like(dx), dx * roll(h, -step))
+    return dx, da
+
+
+def linear_scan(data: Tensor, gate, lay: M.Lay, reverse: bool, hidden) -> Tensor:
+    _linear_scan_dtype(data)
+    gt, gs = _gate_arg(data, gate)
+    if torch.is_grad_enabled() and (data.requires_grad or (gt is not None and gt.requires_grad)):
+        # contiguous HERE, before the Function (as in reduce()): a copy made inside forward() would carry no history
+        return _LinearScan.apply(data.contiguous(), None if gt is None else gt.contiguous(), gs, lay, bool(reverse),
+                                 tuple(hidden))
+    data = data.detach() if data.requires_grad else data
+    if gt is not None and gt.requires_grad:
+        gt = gt.detach()
+    return launch_linear_scan(lay, data, gs if gt is None else gt, bool(reverse), tuple(hidden))
+
+
 # ------------------------------------------------------------------ per-sequence argmax / argmin (an extension)
 def _argreduce_dtype(data: Tensor) -> int:
     if data.dtype not in L.SCAN_DTYPES:
