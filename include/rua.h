@@ -354,6 +354,57 @@ int rua_segment_softmax(const rua_layout* lay, const void* data, void* out, int6
 int rua_segment_softmax_backward(const rua_layout* lay, const void* y, const void* grad_out, void* grad_in, int64_t H,
                                  int32_t dtype, int32_t log, void* ws, void* stream);
 
+/* Per-sequence softmax-weighted sum — attention pooling (an EXTENSION, added to ABI 6 — the version number did not
+ * move: the reference's users spell it as segment_logsumexp, repeat_interleave, exp, a broadcast multiply and segment_sum
+ * over [N, H] temporaries, for a CattedSequence only).  `values` has rows of H elements, `scores` rows of G = H / D
+ * elements in the same row order (the same layout `lay`), both of `dtype`; column h is weighted by score column h / D.
+ * For every sequence b of `lay` (ANY layout) and column h, over t < len[b]:
+ *   out[b, h] = sum_t exp(scores[row(b,t), h / D] - lse[b, h / D]) * values[row(b,t), h]
+ *   lse[b, g] = logsumexp_t scores[row(b,t), g]
+ * i.e. (torch.softmax(s_seq, dim=0)[..., None] * v_seq).sum(0) of every sequence on its own.  out is [B, H] of `dtype`;
+ * lse is [B, G] in the accumulator type (float; double for RUA_F64), -inf for an empty sequence, and may be NULL.  An
+ * empty sequence gives zeros.  A NaN or +inf score, or only -inf scores, make that (sequence, score column) NaN and touch
+ * nothing else; a non-finite value poisons its own (sequence, column) even at weight 0.  fp32 accumulation (fp64 for
+ * RUA_F64), every output element rounded once; RUA_F32 / RUA_BF16 / RUA_F16 / RUA_F64.  Padding rows of LEFT / RIGHT
+ * values and scores are never read.
+ * Checks: a null layout, an integer dtype, D <= 0 or H % D != 0 and an output that aliases an input (or the other
+ * output) give RUA_EINVAL; B == 0, H == 0 or n_rows == 0 return 0 without a launch (the caller fills out / lse);
+ * lengths are clamped to the storage and every row is range-checked, as in rua_segment_softmax.
+ * The fold order of a (sequence, column) is the softmax's — blocks of 2 048 tokens in ascending order; inside a block 32
+ * interleaved chains (chain r takes the tokens t = r mod 32, ascending, with a one-exp online update of (max, sum of
+ * weights, weighted sum)) joined by a butterfly whose combine rescales both sides to the common max and is symmetric —
+ * and depends on NOTHING but the sequence's length: the operator commutes with the casts BIT FOR BIT.  out = weighted
+ * sum / sum of weights.  Two kernel forms by row width: rows of one vector (H * esize <= 16 bytes, 1-D values included)
+ * put consecutive tokens on consecutive lanes, two sequences per wave; wider rows give a workgroup per (sequence x
+ * 128-byte column chunk), 32 rows x 8 lanes of 16 bytes, a lane carrying one (max, sum) where D * esize is a multiple
+ * of 16 and one per element otherwise.  The values are read once, the scores of a sequence once per column chunk (H *
+ * esize / 128 times for wide rows with few score columns).  Any alignment is accepted (narrower accesses, the
+ * same bits).  `ws` is reserved for cutting few-but-long sequences across workgroups: rua_softmax_pool_ws_bytes
+ * returns 0 today, ws may be NULL, and one workgroup walks a whole sequence.
+ * RUA_POOL_OUT_ACC OR-ed into `dtype`: `out` is written UNROUNDED, in the accumulator type — what a caller keeps for the
+ * backward when the payload is bf16 / f16 (delta below is a difference's subtrahend: from a rounded `out` it would carry
+ * the payload dtype's rounding error into grad_scores); the caller rounds it to the payload dtype itself, once.
+ * While the dispatch trace is on every launch records `seg_pool_lanes_kernel` or `seg_pool_rows_kernel` with key=value
+ * pairs (T= AL= D= kind= ...). */
+#define RUA_POOL_OUT_ACC 0x100
+int64_t rua_softmax_pool_ws_bytes(const rua_layout* lay, int64_t H, int64_t D, int32_t dtype);
+int rua_segment_softmax_pool(const rua_layout* lay, const void* values, const void* scores, void* out, void* lse,
+                             int64_t H, int64_t D, int32_t dtype, void* ws, void* stream);
+/* Its backward, token-parallel given the forward's `out` and `lse` (both required), with p = exp(scores - lse):
+ *   grad_values[row, h] = p[row, h / D] * grad_out[b, h]
+ *   grad_scores[row, g] = p[row, g] * (sum_{h in g} values[row, h] * grad_out[b, h] - delta[b, g])
+ *   delta[b, g]         = sum_{h in g} out[b, h] * grad_out[b, h]
+ * ONE launch that reads the values once and writes both gradients once; either gradient pointer may be NULL (both NULL:
+ * returns 0).  With RUA_POOL_OUT_ACC in `dtype`, `out` is read in the accumulator type (the forward's with the same
+ * bit).  Padding rows of LEFT / RIGHT gradients are written as zeros.  The order of the sums over the D columns of a
+ * score column is fixed by (H, D, dtype) alone: rows of one vector ascending; wider rows deal the columns in units (16
+ * bytes when D * esize is a multiple of 16, else one element) round-robin to S = min(64, pow2ceil(units)) lanes, each
+ * lane sums ascending and the lanes are joined by a butterfly.  A gradient that aliases any input or the other gradient:
+ * RUA_EINVAL; the other checks are the forward's.  The trace record is `seg_pool_backward_kernel` (form=lanes|team). */
+int rua_segment_softmax_pool_backward(const rua_layout* lay, const void* grad_out, const void* values,
+                                      const void* scores, const void* out, const void* lse, void* grad_values,
+                                      void* grad_scores, int64_t H, int64_t D, int32_t dtype, void* ws, void* stream);
+
 /* Per-sequence inclusive cumsum (an EXTENSION, added to ABI 6 — the version number did not move: the reference has no
  * prefix operator; its users pad, call torch.cumsum along dim 1 and cast back).  For every sequence b of `lay` (ANY
  * layout) and column h:

@@ -9,6 +9,7 @@ from typing import Callable, Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor
+from torch.autograd.function import once_differentiable
 
 from torchrua_amd import _lib as L
 from torchrua_amd import _meta as M
@@ -442,6 +443,118 @@ def softmax(data: Tensor, lay: M.Lay, log: bool, hidden) -> Tensor:
         # contiguous HERE, inside the graph (as in reduce()): a copy made inside forward() would carry no history
         return _Softmax.apply(data.contiguous(), lay, bool(log), tuple(hidden))
     return launch_softmax(lay, data.detach() if data.requires_grad else data, bool(log), tuple(hidden))
+
+
+# ------------------------------------------------------------------ per-sequence softmax-weighted sum (an extension)
+def _pool_acc(dtype: torch.dtype) -> torch.dtype:
+    return torch.float64 if dtype == torch.float64 else torch.float32
+
+
+def _pool_check(values: Tensor, scores: Tensor) -> torch.device:
+    dev = L.require_device(values, scores)
+    if values.dtype not in L.DTYPES:
+        raise L.RuaError(f'softmax_pool supports {list(L.DTYPES)}; got {values.dtype}')
+    if scores.dtype != values.dtype:
+        raise L.RuaError(f'softmax_pool: the scores have dtype {scores.dtype}, the values {values.dtype}')
+    if scores.device != values.device:
+        raise L.RuaError('softmax_pool: scores and values live on different devices')
+    return dev
+
+
+def launch_softmax_pool(lay: M.Lay, values: Tensor, scores: Tensor, hidden: Tuple[int, ...], G: int,
+                        out_acc: bool = False) -> Tuple[Tensor, Tensor]:
+    """rua_segment_softmax_pool: (out [B, *hidden], lse [B, G] in the accumulator type) in one launch; the values are
+    read once, no [N, H] temporary exists.  out_acc: `out` comes unrounded, in the accumulator type (RUA_POOL_OUT_ACC) —
+    what autograd keeps for a bf16 / f16 payload."""
+    dev = _pool_check(values, scores)
+    lib = L.load()
+    H = _prod(hidden)
+    D = H // G if G else 1
+    values, scores = values.contiguous(), scores.contiguous()
+    acc = _pool_acc(values.dtype)
+    out_dtype = acc if out_acc else values.dtype
+    if lay.B == 0 or lay.n_rows == 0 or H == 0:
+        # (the entry point returns without a launch: every sequence is empty)
+        return (torch.zeros((lay.B,) + tuple(hidden), dtype=out_dtype, device=dev),
+                torch.full((lay.B, G), float('-inf'), dtype=acc, device=dev))
+    out = torch.empty((lay.B,) + tuple(hidden), dtype=out_dtype, device=dev)
+    lse = torch.empty((lay.B, G), dtype=acc, device=dev)
+    if _kernel_hook:
+        _kernel_hook('softmax_pool', True)
+    L.check(lib.rua_segment_softmax_pool(lay.ref(), L.ptr(values), L.ptr(scores), L.ptr(out), L.ptr(lse), H, D,
+                                         L.DTYPES[values.dtype] | (L.POOL_OUT_ACC if out_acc else 0), None,
+                                         L.stream_ptr(dev)), 'rua_segment_softmax_pool')
+    if _kernel_hook:
+        _kernel_hook('softmax_pool', False)
+    return out, lse
+
+
+def launch_softmax_pool_backward(lay: M.Lay, grad: Tensor, values: Tensor, scores: Tensor, out: Tensor, lse: Tensor,
+                                 hidden: Tuple[int, ...], G: int, want_values: bool = True,
+                                 want_scores: bool = True) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+    """rua_segment_softmax_pool_backward: (grad_values or None, grad_scores or None) in one launch, from the inputs, the
+    [B, H] output (in the payload dtype, or unrounded in the accumulator type) and the [B, G] lse.  Padding rows of both
+    are zeros."""
+    dev = _pool_check(values, scores)
+    L.require_device(grad, out, lse)
+    out_acc = out.dtype != values.dtype
+    if out.dtype not in (values.dtype, _pool_acc(values.dtype)) or not out.is_contiguous() or not lse.is_contiguous():
+        raise L.RuaError('softmax_pool backward: `out` is the contiguous forward output, in the payload or accumulator dtype')
+    if grad.dtype != values.dtype or grad.shape != out.shape:
+        raise L.RuaError('softmax_pool backward: the cotangent must have the dtype and shape of the output')
+    lib = L.load()
+    H = _prod(hidden)
+    D = H // G if G else 1
+    grad, values, scores = grad.contiguous(), values.contiguous(), scores.contiguous()
+    if lay.B == 0 or lay.n_rows == 0 or H == 0:
+        # (no launch, as in the forward: nothing depends on either input, so both gradients are zeros)
+        return (torch.zeros(values.shape, dtype=values.dtype, device=dev) if want_values else None,
+                torch.zeros(scores.shape, dtype=scores.dtype, device=dev) if want_scores else None)
+    gv = torch.empty(values.shape, dtype=values.dtype, device=dev) if want_values else None
+    gs = torch.empty(scores.shape, dtype=scores.dtype, device=dev) if want_scores else None
+    if _kernel_hook:
+        _kernel_hook('softmax_pool_bwd', True)
+    L.check(lib.rua_segment_softmax_pool_backward(lay.ref(), L.ptr(grad), L.ptr(values), L.ptr(scores), L.ptr(out),
+                                                  L.ptr(lse), L.ptr(gv), L.ptr(gs), H, D,
+                                                  L.DTYPES[values.dtype] | (L.POOL_OUT_ACC if out_acc else 0), None,
+                                                  L.stream_ptr(dev)), 'rua_segment_softmax_pool_backward')
+    if _kernel_hook:
+        _kernel_hook('softmax_pool_bwd', False)
+    return gv, gs
+
+
+class _SoftmaxPool(torch.autograd.Function):
+    """out[b] = sum_t softmax_t(scores[b])[t] * values[b, t].  Saves the two inputs, the [B, H] output and the [B, G]
+    lse — nothing else of [N, H] size; the backward is one fused kernel and differentiates once.  For a bf16 / f16
+    payload the kernel hands the output unrounded (fp32): that is what is saved — the backward subtracts sum(out * g)
+    from a per-token dot, and a rounded `out` would put 2^-9 of it into grad_scores — and the result is its one rounding."""
+
+    @staticmethod
+    def forward(ctx, values: Tensor, scores: Tensor, lay: M.Lay, hidden, G: int):
+        half = values.dtype in (torch.bfloat16, torch.float16)
+        kept, lse = launch_softmax_pool(lay, values, scores, hidden, G, out_acc=half)
+        out = kept.to(values.dtype) if half else kept
+        ctx.lay, ctx.hidden, ctx.G = lay, tuple(hidden), G
+        ctx.save_for_backward(values, scores, kept, lse)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad: Tensor):
+        values, scores, out, lse = ctx.saved_tensors
+        gv, gs = launch_softmax_pool_backward(ctx.lay, grad, values, scores, out, lse, ctx.hidden, ctx.G,
+                                              ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return gv, gs, None, None, None
+
+
+def softmax_pool(values: Tensor, scores: Tensor, lay: M.Lay, hidden, G: int) -> Tensor:
+    _pool_check(values, scores)
+    if torch.is_grad_enabled() and (values.requires_grad or scores.requires_grad):
+        # contiguous HERE, before the Function (as in reduce()): a copy made inside forward() would carry no history
+        return _SoftmaxPool.apply(values.contiguous(), scores.contiguous(), lay, tuple(hidden), int(G))
+    values = values.detach() if values.requires_grad else values
+    scores = scores.detach() if scores.requires_grad else scores
+    return launch_softmax_pool(lay, values, scores, tuple(hidden), int(G))[0]
 
 
 # ------------------------------------------------------------------ per-sequence cumsum (an extension)
