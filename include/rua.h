@@ -405,6 +405,64 @@ int rua_segment_softmax_pool_backward(const rua_layout* lay, const void* grad_ou
                                       const void* scores, const void* out, const void* lse, void* grad_values,
                                       void* grad_scores, int64_t H, int64_t D, int32_t dtype, void* ws, void* stream);
 
+/* Per-sequence mean / variance and standardize (an EXTENSION, added to ABI 6 — the version number did not move: the
+ * reference's users spell it as segment_mean, repeat_interleave, a subtraction, a square, segment_mean again, rsqrt and
+ * a multiply over [N, H] temporaries, for a CattedSequence only).  For every sequence b of `lay` (ANY layout) and column
+ * h, with n = len[b] and c = correction, over t < n:
+ *   mean[b,h] = (1/n) sum_t x        M2[b,h] = sum_t (x - mean[b,h])^2        var[b,h] = M2 / (n - c)
+ *   standardize:  out[row(b,t), h] = (x - mean[b,h]) * rstd[b,h],   rstd = 1 / sqrt(M2 / (n - c) + eps)
+ * i.e. torch.var_mean(seq, dim=0, correction=c) and (seq - mean) * rsqrt(var + eps) of every sequence on its own.
+ * RUA_F32 / RUA_BF16 / RUA_F16 / RUA_F64 (integer dtypes: RUA_EINVAL); fp32 accumulation (fp64 for RUA_F64), every
+ * output element rounded once.  `var` and `mean` are [B, H] of `dtype` (either may be NULL; both NULL: returns 0);
+ * `rstd` is [B, H] in the accumulator type (float; double for RUA_F64) and may be NULL.  n - c <= 0 makes that
+ * sequence's var, rstd and out NaN; an empty sequence gives NaN var and NaN mean and owns no row of CAT / PACK.  A NaN or
+ * an infinity poisons its own (sequence, column) and nothing else; a constant column has var == 0 exactly.  Padding rows
+ * of a LEFT / RIGHT input are never read; padding rows of a LEFT / RIGHT result are written as zeros in the same pass.
+ * `correction` >= 0 and `eps` >= 0 are passed by value (negative: RUA_EINVAL).
+ * The fold order of a (sequence, column) is the softmax's — blocks of 2 048 tokens in ascending order; inside a block 32
+ * interleaved chains (chain r takes the tokens t = r mod 32, ascending, Welford's update with one reciprocal per token
+ * shared by the columns of a thread) joined by a butterfly with Chan's pairwise formula, both partners computing
+ * merge(lower slot, upper slot); blocks joined in order — and depends on NOTHING but the sequence's length: the operators
+ * commute with the casts BIT FOR BIT.
+ * Kernel forms as for rua_segment_softmax: rows of one vector (<= 16 bytes) put consecutive tokens on consecutive lanes,
+ * two sequences per wave; wider rows give a workgroup per (sequence x 128-byte column chunk), which keeps the slab in
+ * LDS between the fold and the rewrite when the sequence has at most 480 rows (backward: 224 — what a 64 KiB budget
+ * leaves) and otherwise walks global memory twice; few but long sequences (fewer than 1 024 units whose length bound is
+ * at least 8 192) are cut into their blocks across workgroups when `ws` is given: rua_norm_ws_bytes(lay, H, dtype) =
+ *   B * ceil(bound / 2048) * ceil(H * esize / 128) * (128 / esize) * 2 * sizeof(accumulator)
+ * bytes — (mean, M2), or the backward's two sums, per block and padded column — and 0 where the cut form is never
+ * taken (ws == NULL = do not cut).  Two launches then.  A CAT layout's T_log, where given, must be a TRUE bound, as for
+ * rua_segment_softmax.  rua_segment_var_mean is the standardize's first walk alone: it reads the payload once and writes
+ * [B, H].  `out` may equal `data`; a [B, H] output that aliases an input or the other output: RUA_EINVAL.  B == 0,
+ * H == 0 and n_rows == 0 return 0 without a launch (the caller fills var / mean).  Lengths are clamped to the storage,
+ * every row is range-checked, any alignment is accepted (narrower accesses, the same bits).
+ * RUA_NORM_MEAN_ACC OR-ed into `dtype` of rua_segment_var_mean[_backward]: `mean` is written (read) UNROUNDED, in the
+ * accumulator type — what a caller keeps for the backward when the payload is bf16 / f16 (x - mean is a difference).
+ * While the dispatch trace is on every launch records `seg_norm_lanes_kernel`, `seg_norm_resident_kernel` or
+ * `seg_norm_stream_kernel` with key=value pairs (T= AL= cut= phase= cap= kind= W= op=standardize|var_mean). */
+#define RUA_NORM_MEAN_ACC 0x100
+int64_t rua_norm_ws_bytes(const rua_layout* lay, int64_t H, int32_t dtype);
+int rua_segment_var_mean(const rua_layout* lay, const void* data, void* var, void* mean, int64_t H, int32_t dtype,
+                         int64_t correction, void* ws, void* stream);
+int rua_segment_standardize(const rua_layout* lay, const void* data, void* out, void* rstd, int64_t H, int32_t dtype,
+                            int64_t correction, double eps, void* ws, void* stream);
+/* The backward of var_mean, token-parallel, one elementwise form for every width and alignment:
+ *   grad_in = grad_var[b,h] * 2 (x - mean[b,h]) / (n - c) + grad_mean[b,h] / n
+ * grad_var / grad_mean: [B, H] of `dtype`, either may be NULL (its term is dropped); `mean` as the forward wrote it (in
+ * the accumulator type with RUA_NORM_MEAN_ACC).  Padding rows of grad_in are written as zeros.  grad_in may equal data;
+ * grad_in aliasing mean or a cotangent: RUA_EINVAL.  The trace record is `seg_var_mean_backward_kernel`. */
+int rua_segment_var_mean_backward(const rua_layout* lay, const void* data, const void* mean, const void* grad_var,
+                                  const void* grad_mean, void* grad_in, int64_t H, int32_t dtype, int64_t correction,
+                                  void* stream);
+/* The backward of standardize, from the forward's OUTPUT y and its rstd alone:
+ *   grad_in = rstd * (g - (1/n) sum_t g - y * (sum_t g * y) / (n - c))
+ * the sums in the forward's fold order with `+`; padding rows of grad_in are written as zeros.  grad_in may equal
+ * grad_out; y or rstd aliasing grad_in: RUA_EINVAL.  Same forms, same `ws`; the trace names are
+ * `seg_norm_backward_lanes_kernel` etc. */
+int rua_segment_standardize_backward(const rua_layout* lay, const void* y, const void* rstd, const void* grad_out,
+                                     void* grad_in, int64_t H, int32_t dtype, int64_t correction, void* ws,
+                                     void* stream);
+
 /* Per-sequence inclusive cumsum (an EXTENSION, added to ABI 6 — the version number did not move: the reference has no
  * prefix operator; its users pad, call torch.cumsum along dim 1 and cast back).  For every sequence b of `lay` (ANY
  * layout) and column h:

@@ -28,6 +28,7 @@ MOVE_NO_NARROW = 2048               # rua.h: developer A/B — rows of one vecto
 OP_SCRATCH_CLEAN, OP_NO_EMPTY = 0x100, 0x200      # rua.h: bits OR-ed into `op` (persistent zeroed extreme scratch; no sequence is empty: proven)
 EXTREME_WORDS = 1027                               # rua.h: RUA_EXTREME_WORDS
 POOL_OUT_ACC = 0x100       # rua.h: RUA_POOL_OUT_ACC, OR-ed into the dtype of rua_segment_softmax_pool[_backward]
+NORM_MEAN_ACC = 0x100      # rua.h: RUA_NORM_MEAN_ACC, OR-ed into the dtype of rua_segment_var_mean[_backward]
 OP_SHORT_SEQS = 0x400      # rua.h: a CattedSequence of short sequences, none far above the average (a hint)
 # enum rua_dtype / rua_op
 F32, BF16, F16, F64 = 0, 1, 2, 3
@@ -93,6 +94,15 @@ SYMBOLS = {
                                          c_int32, c_void_p, c_void_p]),
     'rua_segment_softmax_pool_backward': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                   c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p]),
+    'rua_norm_ws_bytes': (c_int64, [POINTER(RuaLayout), c_int64, c_int32]),
+    'rua_segment_var_mean': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int64,
+                                     c_void_p, c_void_p]),
+    'rua_segment_var_mean_backward': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_int64, c_int32, c_int64, c_void_p]),
+    'rua_segment_standardize': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int64,
+                                        c_double, c_void_p, c_void_p]),
+    'rua_segment_standardize_backward': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                                 c_int32, c_int64, c_void_p, c_void_p]),
     'rua_cumsum_ws_bytes': (c_int64, [POINTER(RuaLayout), c_int64, c_int32]),
     'rua_segment_cumsum': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
     'rua_linear_scan_ws_bytes': (c_int64, [POINTER(RuaLayout), c_int64, c_int32]),

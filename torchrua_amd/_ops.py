@@ -557,6 +557,248 @@ def softmax_pool(values: Tensor, scores: Tensor, lay: M.Lay, hidden, G: int) -> 
     return launch_softmax_pool(lay, values, scores, tuple(hidden), int(G))[0]
 
 
+# ------------------------------------------------------------------ per-sequence var_mean / standardize (an extension)
+def _norm_args(lay: M.Lay, data: Tensor, hidden, correction, eps=0.0, cut: bool = True):
+    dev = L.require_device(data)
+    if data.dtype not in L.DTYPES:
+        raise L.RuaError(f'var_mean / standardize support {list(L.DTYPES)}; got {data.dtype}')
+    if isinstance(correction, bool) or not isinstance(correction, int) or correction < 0:
+        raise L.RuaError(f'var_mean / standardize: correction is a non-negative integer; got {correction!r}')
+    if not float(eps) >= 0.0:
+        raise L.RuaError(f'standardize: eps is a non-negative float; got {eps!r}')
+    H = _prod(hidden)
+    lib = L.load()
+    nbytes = lib.rua_norm_ws_bytes(lay.ref(), H, L.DTYPES[data.dtype]) if cut else 0    # > 0: few but long sequences get cut
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    return dev, lib, H, ws
+
+
+def launch_var_mean(lay: M.Lay, data: Tensor, hidden: Tuple[int, ...], correction: int = 1, want_var: bool = True,
+                    want_mean: bool = True, mean_acc: bool = False) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+    """rua_segment_var_mean: (var, mean), each [B, *hidden] of the payload dtype, from ONE read of the payload.
+    mean_acc: `mean` comes unrounded, in the accumulator type (RUA_NORM_MEAN_ACC) — what autograd keeps for bf16 / f16."""
+    dev, lib, H, ws = _norm_args(lay, data, hidden, correction)
+    data = data.contiguous()
+    shape = (lay.B,) + tuple(hidden)
+    mean_dtype = _pool_acc(data.dtype) if mean_acc else data.dtype
+    if lay.B == 0 or lay.n_rows == 0 or H == 0:
+        # (the entry point returns without a launch: every sequence is empty)
+        return (torch.full(shape, float('nan'), dtype=data.dtype, device=dev) if want_var else None,
+                torch.full(shape, float('nan'), dtype=mean_dtype, device=dev) if want_mean else None)
+    var = torch.empty(shape, dtype=data.dtype, device=dev) if want_var else None
+    mean = torch.empty(shape, dtype=mean_dtype, device=dev) if want_mean else None
+    if _kernel_hook:
+        _kernel_hook('var_mean', True)
+    L.check(lib.rua_segment_var_mean(lay.ref(), L.ptr(data), L.ptr(var), L.ptr(mean), H,
+                                     L.DTYPES[data.dtype] | (L.NORM_MEAN_ACC if mean_acc else 0), correction,
+                                     L.ptr(ws), L.stream_ptr(dev)), 'rua_segment_var_mean')
+    if _kernel_hook:
+        _kernel_hook('var_mean', False)
+    return var, mean
+
+
+def launch_var_mean_backward(lay: M.Lay, data: Tensor, mean: Tensor, grad_var: Optional[Tensor],
+                             grad_mean: Optional[Tensor], hidden: Tuple[int, ...], correction: int = 1,
+                             out: Optional[Tensor] = None) -> Tensor:
+    """rua_segment_var_mean_backward: one token-parallel launch; `mean` in the payload or the accumulator dtype."""
+    dev, lib, H, _ = _norm_args(lay, data, hidden, correction, cut=False)
+    L.require_device(mean, grad_var, grad_mean)
+    mean_acc = mean.dtype != data.dtype
+    shape = (lay.B,) + tuple(hidden)
+    if mean.dtype not in (data.dtype, _pool_acc(data.dtype)) or tuple(mean.shape) != shape:
+        raise L.RuaError('var_mean backward: `mean` is the forward\'s [B, *hidden], in the payload or accumulator dtype')
+    for g in (grad_var, grad_mean):
+        if g is not None and (g.dtype != data.dtype or tuple(g.shape) != shape):
+            raise L.RuaError('var_mean backward: a cotangent must have the dtype and shape of its output')
+    data, mean = data.contiguous(), mean.contiguous()
+    grad_var = None if grad_var is None else grad_var.contiguous()
+    grad_mean = None if grad_mean is None else grad_mean.contiguous()
+    if out is None:
+        out = torch.empty(data.shape, dtype=data.dtype, device=dev)      # padding rows: zeroed by the call
+    elif not out.is_contiguous() or out.dtype != data.dtype or out.shape != data.shape:
+        raise L.RuaError('var_mean backward target must be contiguous, of the payload dtype and of the payload shape')
+    if _kernel_hook:
+        _kernel_hook('var_mean_bwd', True)
+    L.check(lib.rua_segment_var_mean_backward(lay.ref(), L.ptr(data), L.ptr(mean), L.ptr(grad_var), L.ptr(grad_mean),
+                                              L.ptr(out), H, L.DTYPES[data.dtype] | (L.NORM_MEAN_ACC if mean_acc else 0),
+                                              correction, L.stream_ptr(dev)), 'rua_segment_var_mean_backward')
+    if _kernel_hook:
+        _kernel_hook('var_mean_bwd', False)
+    return out
+
+
+def launch_standardize(lay: M.Lay, data: Tensor, hidden: Tuple[int, ...], eps: float = 1e-5, correction: int = 0,
+                       out: Optional[Tensor] = None, want_rstd: bool = False) -> Tuple[Tensor, Optional[Tensor]]:
+    """rua_segment_standardize: (y, rstd [B, *hidden] in the accumulator type or None); one launch (two for cut
+    sequences), no [N, H] temporary.  `out` may be `data` itself."""
+    dev, lib, H, ws = _norm_args(lay, data, hidden, correction, eps)
+    data = data.contiguous()
+    if out is None:
+        out = torch.empty(data.shape, dtype=data.dtype, device=dev)      # padding rows: zeroed by the call
+    elif not out.is_contiguous() or out.dtype != data.dtype or out.shape != data.shape:
+        raise L.RuaError('standardize target must be contiguous, of the payload dtype and of the payload shape')
+    rstd = None
+    if want_rstd:
+        shape, acc = (lay.B,) + tuple(hidden), _pool_acc(data.dtype)
+        if lay.B == 0 or lay.n_rows == 0 or H == 0:                      # (no launch then: every sequence is empty)
+            rstd = torch.full(shape, float('nan'), dtype=acc, device=dev)
+        else:
+            rstd = torch.empty(shape, dtype=acc, device=dev)
+    if _kernel_hook:
+        _kernel_hook('standardize', True)
+    L.check(lib.rua_segment_standardize(lay.ref(), L.ptr(data), L.ptr(out), L.ptr(rstd), H, L.DTYPES[data.dtype],
+                                        correction, float(eps), L.ptr(ws), L.stream_ptr(dev)), 'rua_segment_standardize')
+    if _kernel_hook:
+        _kernel_hook('standardize', False)
+    return out, rstd
+
+
+def launch_standardize_backward(lay: M.Lay, y: Tensor, rstd: Tensor, grad: Tensor, hidden: Tuple[int, ...],
+                                correction: int = 0, out: Optional[Tensor] = None) -> Tensor:
+    """rua_segment_standardize_backward: the gradient from the forward's output and rstd alone.  `out` may be `grad`."""
+    dev, lib, H, ws = _norm_args(lay, y, hidden, correction)
+    L.require_device(grad, rstd)
+    if grad.dtype != y.dtype or grad.shape != y.shape:
+        raise L.RuaError('standardize backward: the cotangent must have the dtype and shape of the output')
+    if rstd.dtype != _pool_acc(y.dtype) or tuple(rstd.shape) != (lay.B,) + tuple(hidden):
+        raise L.RuaError('standardize backward: `rstd` is the forward\'s [B, *hidden] in the accumulator dtype')
+    y, grad, rstd = y.contiguous(), grad.contiguous(), rstd.contiguous()
+    if out is None:
+        out = torch.empty(y.shape, dtype=y.dtype, device=dev)
+    elif not out.is_contiguous() or out.dtype != y.dtype or out.shape != y.shape:
+        raise L.RuaError('standardize backward target must be contiguous, of the payload dtype and of the payload shape')
+    if _kernel_hook:
+        _kernel_hook('standardize_bwd', True)
+    L.check(lib.rua_segment_standardize_backward(lay.ref(), L.ptr(y), L.ptr(rstd), L.ptr(grad), L.ptr(out), H,
+                                                 L.DTYPES[y.dtype], correction, L.ptr(ws), L.stream_ptr(dev)),
+            'rua_segment_standardize_backward')
+    if _kernel_hook:
+        _kernel_hook('standardize_bwd', False)
+    return out
+
+
+def _norm_pieces(ref: Tensor, lay: M.Lay, hidden, correction: int):
+    """What the composed (twice differentiable) gradients share: the per-sequence broadcast, the mask of live rows and
+    the [B, *hidden] counts n and n - c (NaN where n - c <= 0, as the kernels give)."""
+    def spread(v: Tensor) -> Tensor:                 # every sequence's row of `v` over the sequence's storage rows
+        return _ReduceBwd.apply(v.contiguous(), ref.detach(), v.detach(), lay, L.SUM, None)
+
+    ones = torch.ones((lay.B,) + tuple(hidden), dtype=ref.dtype, device=ref.device)
+    live = spread(ones) != 0
+    n = launch_reduce(lay, live.to(ref.dtype), L.SUM, hidden=tuple(hidden), reference_initial=False)
+    dof = n - correction
+    dof = torch.where(dof > 0, dof, torch.full_like(dof, float('nan')))
+    return spread, live, n, dof
+
+
+class _Standardize(torch.autograd.Function):
+    """(y, rstd) = standardize of every sequence.  Saves ONLY y and the [B, H] rstd — both outputs of this node, so a
+    recorded backward (create_graph=True) differentiates through them; the caller keeps y alone."""
+
+    @staticmethod
+    def forward(ctx, data: Tensor, lay: M.Lay, hidden, eps: float, correction: int):
+        y, rstd = launch_standardize(lay, data, hidden, eps, correction, want_rstd=True)
+        ctx.lay, ctx.hidden, ctx.correction = lay, tuple(hidden), correction
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(y, rstd)
+        return y, rstd
+
+    @staticmethod
+    def backward(ctx, grad: Optional[Tensor], grad_rstd: Optional[Tensor]):
+        y, rstd = ctx.saved_tensors
+        if grad is None and grad_rstd is None:
+            return None, None, None, None, None
+        if torch.is_grad_enabled() or grad_rstd is not None or grad is None:
+            # a graph of this backward is being recorded (create_graph=True), or rstd itself carries a cotangent (it
+            # only does inside such a graph): the gradient spelled with the library's differentiable pieces, as
+            # _composed_softmax_grad does; [N, H] temporaries, paid only by callers who ask for second derivatives
+            return _composed_standardize_grad(grad, grad_rstd, y, rstd, ctx.lay, ctx.hidden, ctx.correction), None, None, None, None
+        return launch_standardize_backward(ctx.lay, y, rstd, grad, ctx.hidden, ctx.correction), None, None, None, None
+
+
+def _composed_standardize_grad(grad: Optional[Tensor], grad_rstd: Optional[Tensor], y: Tensor, rstd: Tensor, lay: M.Lay,
+                               hidden, correction: int) -> Tensor:
+    """d standardize / d data as a differentiable function of (grad, grad_rstd, y, rstd):
+    rstd * (g - mean_t g - y * sum_t(g y) / (n - c))  -  y * grad_rstd * rstd^2 / (n - c)."""
+    spread, live, n, dof = _norm_pieces(y, lay, hidden, correction)
+    zero = torch.zeros_like(y)
+    r = rstd.to(y.dtype)
+    yl = torch.where(live, y, zero)
+    total = zero
+    if grad is not None:
+        # padding rows of a padded layout: the cotangent may hold anything (inf, NaN) — masked BEFORE it is used
+        g = torch.where(live, grad, zero)
+        s1 = reduce(g.contiguous(), lay, L.SUM, hidden, None) / n
+        s2 = reduce((g * yl).contiguous(), lay, L.SUM, hidden, None) / dof
+        total = total + spread(r) * (g - spread(s1) - yl * spread(s2))
+    if grad_rstd is not None:
+        total = total - yl * spread(grad_rstd.to(y.dtype) * r * r / dof)
+    return torch.where(live, total, zero)
+
+
+class _VarMean(torch.autograd.Function):
+    """(var, mean) of every sequence.  Saves the input and the [B, H] mean — for a bf16 / f16 payload the unrounded fp32
+    mean the kernel hands out (x - mean is a difference; the result is its one rounding)."""
+
+    @staticmethod
+    def forward(ctx, data: Tensor, lay: M.Lay, hidden, correction: int):
+        half = data.dtype in (torch.bfloat16, torch.float16)
+        var, kept = launch_var_mean(lay, data, hidden, correction, mean_acc=half)
+        mean = kept.to(data.dtype) if half else kept
+        ctx.lay, ctx.hidden, ctx.correction = lay, tuple(hidden), correction
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(data, kept)
+        return var, mean
+
+    @staticmethod
+    def backward(ctx, grad_var: Optional[Tensor], grad_mean: Optional[Tensor]):
+        data, mean = ctx.saved_tensors
+        if grad_var is None and grad_mean is None:
+            return None, None, None, None
+        if torch.is_grad_enabled():
+            return _composed_var_mean_grad(grad_var, grad_mean, data, ctx.lay, ctx.hidden, ctx.correction), None, None, None
+        return launch_var_mean_backward(ctx.lay, data, mean, grad_var, grad_mean, ctx.hidden, ctx.correction), None, None, None
+
+
+def _composed_var_mean_grad(grad_var: Optional[Tensor], grad_mean: Optional[Tensor], data: Tensor, lay: M.Lay, hidden,
+                            correction: int) -> Tensor:
+    """d var_mean / d data as a differentiable function of (grad_var, grad_mean, data); the mean is recomputed with the
+    library's (twice differentiable) reduce_mean."""
+    spread, live, n, dof = _norm_pieces(data, lay, hidden, correction)
+    zero = torch.zeros_like(data)
+    total = zero
+    if grad_var is not None:
+        mean = reduce(data, lay, L.MEAN, hidden, None)
+        dev = torch.where(live, data - spread(mean), zero)      # (padding rows may hold anything)
+        total = total + spread(grad_var * 2 / dof) * dev
+    if grad_mean is not None:
+        total = total + spread(grad_mean / n)
+    return torch.where(live, total, zero)
+
+
+def _norm_refuse(data: Tensor) -> None:
+    if data.dtype not in L.DTYPES:
+        L.require_device(data)
+        raise L.RuaError(f'var_mean / standardize support {list(L.DTYPES)}; got {data.dtype}')
+
+
+def var_mean(data: Tensor, lay: M.Lay, hidden, correction: int = 1, want_var: bool = True,
+             want_mean: bool = True) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+    _norm_refuse(data)
+    if data.requires_grad and torch.is_grad_enabled():
+        # contiguous HERE, inside the graph (as in reduce()): a copy made inside forward() would carry no history
+        return _VarMean.apply(data.contiguous(), lay, tuple(hidden), correction)
+    return launch_var_mean(lay, data.detach() if data.requires_grad else data, tuple(hidden), correction,
+                           want_var=want_var, want_mean=want_mean)
+
+
+def standardize(data: Tensor, lay: M.Lay, hidden, eps: float = 1e-5, correction: int = 0) -> Tensor:
+    _norm_refuse(data)
+    if data.requires_grad and torch.is_grad_enabled():
+        return _Standardize.apply(data.contiguous(), lay, tuple(hidden), float(eps), correction)[0]
+    return launch_standardize(lay, data.detach() if data.requires_grad else data, tuple(hidden), eps, correction)[0]
+
+
 # ------------------------------------------------------------------ per-sequence cumsum (an extension)
 def _cumsum_dtype(data: Tensor) -> int:
     if data.dtype not in L.SCAN_DTYPES:
