@@ -23,6 +23,58 @@ def set_kernel_hook(fn) -> None:
     _kernel_hook = fn
 
 
+def _prod(shape) -> int:
+    n = 1
+    for d in shape:
+        n *= d
+    return n
+
+
+def _plain(t: Tensor) -> Tensor:
+    """`t` without its graph (no copy)."""
+    return t.detach() if t.requires_grad else t
+
+
+def _acc_dtype(dtype: torch.dtype) -> torch.dtype:
+    return torch.float64 if dtype == torch.float64 else torch.float32
+
+
+def _require_dtype(data: Tensor, table, what: str) -> int:
+    """The ABI code of the payload's dtype; a host tensor is refused first, then a dtype outside `table`."""
+    L.require_device(data)
+    if data.dtype not in table:
+        raise L.RuaError(f'{what} {list(table)}; got {data.dtype}')
+    return table[data.dtype]
+
+
+def _call(name: str, symbol: str, dev, *args) -> None:
+    """One named launch: the kernel hook opens, the entry point `symbol` runs on torch's current stream of `dev` (its
+    last argument, L.stream_ptr: evaluated right before the call) and is checked, the hook closes."""
+    if _kernel_hook:
+        _kernel_hook(name, True)
+    L.check(getattr(L.load(), symbol)(*args, L.stream_ptr(dev)), symbol)
+    if _kernel_hook:
+        _kernel_hook(name, False)
+
+
+_LIKE_PAYLOAD = ' target must be contiguous, of the payload dtype and of the payload shape'
+
+
+def _target(out: Optional[Tensor], like_shape, dtype: torch.dtype, dev, what: str) -> Tensor:
+    """`out`, or a new tensor where the caller gave none; `what` is the message that refuses an unfit one."""
+    if out is None:
+        return torch.empty(tuple(like_shape), dtype=dtype, device=dev)
+    if not out.is_contiguous() or out.dtype != dtype or tuple(out.shape) != tuple(like_shape):
+        raise L.RuaError(what)
+    return out
+
+
+def _workspace(ws_bytes_fn: str, lay: 'M.Lay', H: int, code: int, dev, cut: bool = True) -> Optional[Tensor]:
+    """What the cut form of a per-sequence operator needs (> 0 bytes: few but long sequences get cut), or None."""
+    nbytes = getattr(L.load(), ws_bytes_fn)(lay.ref(), H, code) if cut else 0
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+
+
 _fill_cache = {}
 
 
@@ -61,7 +113,6 @@ class MovePlan:
 
 def launch_move(plan: MovePlan, src_data: Tensor, out: Optional[Tensor] = None) -> Tensor:
     dev = L.require_device(src_data)
-    lib = L.load()
     src_data = src_data.contiguous()
     if out is None:
         out = torch.empty(plan.out_shape, dtype=src_data.dtype, device=dev)
@@ -71,12 +122,8 @@ def launch_move(plan: MovePlan, src_data: Tensor, out: Optional[Tensor] = None) 
     enumerated = src_data if (plan.flags & L.MOVE_SCATTER) else out
     rb = (enumerated.numel() // plan.dst.n_rows) * enumerated.element_size() if plan.dst.n_rows else 0
     fill = _fill16(plan.fill, src_data.dtype)
-    if _kernel_hook:
-        _kernel_hook(plan.name, True)
-    L.check(lib.rua_move_rows(plan.dst.ref(), plan.src.ref(), plan.tmap, plan.arg, L.ptr(out), L.ptr(src_data), rb,
-                              fill, plan.pad_row, plan.flags, L.stream_ptr(dev)), 'rua_move_rows')
-    if _kernel_hook:
-        _kernel_hook(plan.name, False)
+    _call(plan.name, 'rua_move_rows', dev, plan.dst.ref(), plan.src.ref(), plan.tmap, plan.arg, L.ptr(out),
+          L.ptr(src_data), rb, fill, plan.pad_row, plan.flags)
     return out
 
 
@@ -95,7 +142,7 @@ class _Move(torch.autograd.Function):
 def move(src_data: Tensor, plan: MovePlan) -> Tensor:
     if src_data.requires_grad and torch.is_grad_enabled():
         return _Move.apply(src_data, plan)
-    return launch_move(plan, src_data.detach() if src_data.requires_grad else src_data)
+    return launch_move(plan, _plain(src_data))
 
 
 class _ListGather(torch.autograd.Function):
@@ -118,9 +165,7 @@ class _ListGather(torch.autograd.Function):
         flat = ctx.flat_fn().reshape(-1)
         grad = grad.contiguous()
         hidden = tuple(ctx.src_shape[ctx.lead:])
-        n_rows = 1
-        for d in ctx.src_shape[:ctx.lead]:
-            n_rows *= d
+        n_rows = _prod(ctx.src_shape[:ctx.lead])
         flat = torch.where(flat < 0, flat + n_rows, flat)          # negative rows wrapped in the forward (like torch)
         g = scatter_sum(grad.reshape((flat.numel(),) + hidden), flat, n_rows)
         return g.reshape(ctx.src_shape), None, None, None
@@ -204,18 +249,12 @@ def launch_reduce(lay: M.Lay, data: Tensor, op: int, out: Optional[Tensor] = Non
                   perm: Optional[Tensor] = None, hidden: Tuple[int, ...] = (), reference_initial: bool = True,
                   name: str = 'reduce', ties_out: Optional[Tensor] = None) -> Tensor:
     """rua_segment_reduce (+ rua_fill_empty for the reference's global-extreme `initial`)."""
-    dev = L.require_device(data)
-    lib = L.load()
-    if data.dtype not in L.DTYPES:
-        raise L.RuaError(f'reductions support {list(L.DTYPES)}; got {data.dtype}')
+    code = _require_dtype(data, L.DTYPES, 'reductions support')
+    dev = data.device
     data = data.contiguous()
-    H = 1
-    for d in hidden:
-        H *= d
-    if out is None:
-        out = torch.empty((lay.B,) + tuple(hidden), dtype=data.dtype, device=dev)
-    elif not out.is_contiguous() or out.dtype != data.dtype or out.numel() != lay.B * H:
-        raise L.RuaError('reduce target must be a contiguous [B, *hidden] tensor of the payload dtype')
+    H = _prod(hidden)
+    out = _target(out, (lay.B,) + tuple(hidden), data.dtype, dev,
+                  'reduce target must be a contiguous [B, *hidden] tensor of the payload dtype')
     extreme, op_bits = None, 0
     if reference_initial and op in (L.MAX, L.MIN, L.LOGSUMEXP) and include_self == 0:
         extreme, op_bits = extreme_scratch(dev)
@@ -225,22 +264,16 @@ def launch_reduce(lay: M.Lay, data: Tensor, op: int, out: Optional[Tensor] = Non
     # (the reduce leaves the global extreme in the scratch — every wave folds the opposite extreme of the rows it reads —
     # so the trailing rua_fill_empty needs no second walk: every workgroup patches its share of the batch, whether or
     # not the host knows how many sequences are empty)
-    if _kernel_hook:
-        _kernel_hook(name, True)
     paired = extreme is not None
     if paired:
         _scratch_pair.acquire()
     try:
-        L.check(lib.rua_segment_reduce(lay.ref(), L.ptr(perm), L.ptr(data), L.ptr(out), H, L.DTYPES[data.dtype],
-                                       op | op_bits | short | (L.OP_NO_EMPTY if extreme is not None and lay.no_empty else 0),
-                                       include_self,
-                                       _bits(_EMPTY[op], data.dtype), L.ptr(extreme), split, L.ptr(ws), L.ptr(ties_out),
-                                       L.stream_ptr(dev)), 'rua_segment_reduce')
-        if _kernel_hook:
-            _kernel_hook(name, False)
-        if extreme is not None:
-            L.check(lib.rua_fill_empty(lay.ref(), L.ptr(out), H, L.DTYPES[data.dtype], op | (op_bits & L.OP_SCRATCH_CLEAN),
-                                       L.ptr(extreme), L.stream_ptr(dev)), 'rua_fill_empty')
+        _call(name, 'rua_segment_reduce', dev, lay.ref(), L.ptr(perm), L.ptr(data), L.ptr(out), H, code,
+              op | op_bits | short | (L.OP_NO_EMPTY if extreme is not None and lay.no_empty else 0), include_self,
+              _bits(_EMPTY[op], data.dtype), L.ptr(extreme), split, L.ptr(ws), L.ptr(ties_out))
+        if extreme is not None:               # (outside the hook's bracket: the name times the reduce alone)
+            L.check(L.load().rua_fill_empty(lay.ref(), L.ptr(out), H, code, op | (op_bits & L.OP_SCRATCH_CLEAN),
+                                            L.ptr(extreme), L.stream_ptr(dev)), 'rua_fill_empty')
     except L.RuaError:
         forget_extreme_scratch(dev)        # a refused launch may have left the flags raised
         raise
@@ -257,8 +290,7 @@ class _Reduce(torch.autograd.Function):
         if op in (L.MAX, L.MIN):
             # the forward counts, per output element, the elements equal to it (free in the pass that reads the payload
             # anyway): the backward is then ONE walk instead of a counting walk plus an applying walk
-            acc = torch.float64 if data.dtype == torch.float64 else torch.float32
-            ties = torch.empty((lay.B,) + tuple(hidden), dtype=acc, device=data.device)
+            ties = torch.empty((lay.B,) + tuple(hidden), dtype=_acc_dtype(data.dtype), device=data.device)
         out = launch_reduce(lay, data, op, hidden=hidden, ties_out=ties)
         ctx.lay, ctx.op, ctx.lens, ctx.ties = lay, op, lens, ties
         ctx.save_for_backward(data, out)      # (reduce() hands a contiguous payload: the saved tensor IS the input)
@@ -279,13 +311,10 @@ class _Reduce(torch.autograd.Function):
 
 def _composed_reduce_grad(grad: Tensor, data: Tensor, out: Tensor, lay: M.Lay, op: int, ties: Optional[Tensor]) -> Tensor:
     """d reduce / d data as a differentiable function of (grad, data, out): max / min / logsumexp under create_graph."""
-    def spread(v: Tensor) -> Tensor:                 # every sequence's row of `v` over the sequence's storage rows
-        return _ReduceBwd.apply(v.contiguous(), data.detach(), out.detach(), lay, L.SUM, None)
-
+    spread, live = _spread_live(data, lay, out.shape[1:], want_live=op == L.LOGSUMEXP)
     if op == L.LOGSUMEXP:
         # padding rows of a padded layout may hold anything (inf, NaN, 1e9): exp(pad - 0) would turn their zero into
         # NaN, so the exponent is taken on live rows only (0 elsewhere — its gradient there is then exactly 0 as well)
-        live = spread(torch.ones_like(out.detach())) != 0
         return spread(grad) * torch.where(live, data - spread(out), torch.zeros_like(data)).exp()
     o = spread(out.detach())
     x = data.detach()
@@ -293,6 +322,20 @@ def _composed_reduce_grad(grad: Tensor, data: Tensor, out: Tensor, lay: M.Lay, o
     g32 = grad.to(ties.dtype)
     share = torch.where(g32 > 0, g32 / ties.clamp_min(1), g32).to(grad.dtype)     # torch.segment_reduce's tie rule
     return spread(share) * hit
+
+
+def _spread_live(ref: Tensor, lay: M.Lay, hidden, want_live: bool = True):
+    """What the composed (twice differentiable) gradients share: spread(v) lays every sequence's row of a [B, *hidden]
+    `v` over the sequence's storage rows (the backward of the per-sequence sum: differentiable, its adjoint is the sum),
+    and `live` is the mask of the storage rows of `ref` that hold a token."""
+    ref = ref.detach()
+
+    def spread(v: Tensor) -> Tensor:
+        return _ReduceBwd.apply(v.contiguous(), ref, v.detach(), lay, L.SUM, None)
+
+    if not want_live:
+        return spread, None
+    return spread, spread(torch.ones((lay.B,) + tuple(hidden), dtype=ref.dtype, device=ref.device)) != 0
 
 
 class _ReduceBwd(torch.autograd.Function):
@@ -311,9 +354,7 @@ class _ReduceBwd(torch.autograd.Function):
         lib = L.load()
         grad = grad.contiguous()
         g = torch.empty(data.shape, dtype=data.dtype, device=dev)   # padding rows: zeroed by the call (BWD_FILL_PADDING)
-        H = 1
-        for d in out.shape[1:]:
-            H *= d
+        H = _prod(out.shape[1:])
         split, ws = split_workspace(lay, H, data.dtype, dev, team_ok=False)      # (the backward walk has no wave teams)
         # max/min: `ties` counted by the forward -> apply only (TIES_FINAL).  segment_max/min are torch.segment_reduce in
         # the reference (reduce.py:34-41), whose backward lets tied extrema share a positive gradient and hands each of
@@ -340,59 +381,38 @@ def reduce(data: Tensor, lay: M.Lay, op: int, hidden, lens: Optional[Tensor]) ->
         # contiguous HERE, inside the graph: the Function saves its own input, so a second derivative (create_graph)
         # reaches d/d data through it — a copy made inside forward() would carry no history
         return _Reduce.apply(data.contiguous(), lay, op, tuple(hidden), lens)
-    return launch_reduce(lay, data.detach() if data.requires_grad else data, op, hidden=tuple(hidden))
+    return launch_reduce(lay, _plain(data), op, hidden=tuple(hidden))
 
 
 # ------------------------------------------------------------------ per-sequence softmax / log_softmax (an extension)
-def _softmax_args(lay: M.Lay, data: Tensor, hidden):
-    dev = L.require_device(data)
-    if data.dtype not in L.DTYPES:
-        raise L.RuaError(f'softmax / log_softmax support {list(L.DTYPES)}; got {data.dtype}')
-    H = _prod(hidden)
-    lib = L.load()
-    nbytes = lib.rua_softmax_ws_bytes(lay.ref(), H, L.DTYPES[data.dtype])      # > 0: few but long sequences get cut
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
-    return dev, lib, H, ws
+_SOFTMAX_SUPPORT = 'softmax / log_softmax support'
 
 
 def launch_softmax(lay: M.Lay, data: Tensor, log: bool, hidden: Tuple[int, ...], out: Optional[Tensor] = None) -> Tensor:
     """rua_segment_softmax: one launch (two for cut sequences), no [N, H] temporary.  `out` may be `data` itself."""
-    dev, lib, H, ws = _softmax_args(lay, data, hidden)
+    code = _require_dtype(data, L.DTYPES, _SOFTMAX_SUPPORT)
+    dev, H = data.device, _prod(hidden)
+    ws = _workspace('rua_softmax_ws_bytes', lay, H, code, dev)
     data = data.contiguous()
-    if out is None:
-        out = torch.empty(data.shape, dtype=data.dtype, device=dev)      # padding rows: zeroed by the call
-    elif not out.is_contiguous() or out.dtype != data.dtype or out.shape != data.shape:
-        raise L.RuaError('softmax target must be contiguous, of the payload dtype and of the payload shape')
-    name = 'log_softmax' if log else 'softmax'
-    if _kernel_hook:
-        _kernel_hook(name, True)
-    L.check(lib.rua_segment_softmax(lay.ref(), L.ptr(data), L.ptr(out), H, L.DTYPES[data.dtype], int(bool(log)),
-                                    L.ptr(ws), L.stream_ptr(dev)), 'rua_segment_softmax')
-    if _kernel_hook:
-        _kernel_hook(name, False)
+    out = _target(out, data.shape, data.dtype, dev, 'softmax' + _LIKE_PAYLOAD)      # padding rows: zeroed by the call
+    _call('log_softmax' if log else 'softmax', 'rua_segment_softmax', dev, lay.ref(), L.ptr(data), L.ptr(out), H, code,
+          int(bool(log)), L.ptr(ws))
     return out
 
 
 def launch_softmax_backward(lay: M.Lay, y: Tensor, grad: Tensor, log: bool, hidden: Tuple[int, ...],
                             out: Optional[Tensor] = None) -> Tensor:
     """rua_segment_softmax_backward: the gradient from the forward's output alone.  `out` may be `grad` itself."""
-    dev, lib, H, ws = _softmax_args(lay, y, hidden)
+    code = _require_dtype(y, L.DTYPES, _SOFTMAX_SUPPORT)
+    dev, H = y.device, _prod(hidden)
+    ws = _workspace('rua_softmax_ws_bytes', lay, H, code, dev)
     L.require_device(grad)
     if grad.dtype != y.dtype or grad.shape != y.shape:
         raise L.RuaError('softmax backward: the cotangent must have the dtype and shape of the output')
     y, grad = y.contiguous(), grad.contiguous()
-    if out is None:
-        out = torch.empty(y.shape, dtype=y.dtype, device=dev)
-    elif not out.is_contiguous() or out.dtype != y.dtype or out.shape != y.shape:
-        raise L.RuaError('softmax backward target must be contiguous, of the payload dtype and of the payload shape')
-    name = 'log_softmax_bwd' if log else 'softmax_bwd'
-    if _kernel_hook:
-        _kernel_hook(name, True)
-    L.check(lib.rua_segment_softmax_backward(lay.ref(), L.ptr(y), L.ptr(grad), L.ptr(out), H, L.DTYPES[y.dtype],
-                                             int(bool(log)), L.ptr(ws), L.stream_ptr(dev)),
-            'rua_segment_softmax_backward')
-    if _kernel_hook:
-        _kernel_hook(name, False)
+    out = _target(out, y.shape, y.dtype, dev, 'softmax backward' + _LIKE_PAYLOAD)
+    _call('log_softmax_bwd' if log else 'softmax_bwd', 'rua_segment_softmax_backward', dev, lay.ref(), L.ptr(y),
+          L.ptr(grad), L.ptr(out), H, code, int(bool(log)), L.ptr(ws))
     return out
 
 
@@ -419,12 +439,7 @@ class _Softmax(torch.autograd.Function):
 
 def _composed_softmax_grad(grad: Tensor, y: Tensor, lay: M.Lay, log: bool, hidden) -> Tensor:
     """d softmax / d data as a differentiable function of (grad, y)."""
-    def spread(v: Tensor) -> Tensor:                 # every sequence's row of `v` over the sequence's storage rows
-        return _ReduceBwd.apply(v.contiguous(), y.detach(), v.detach(), lay, L.SUM, None)
-
-    B = lay.B
-    ones = torch.ones((B,) + tuple(hidden), dtype=y.dtype, device=y.device)
-    live = spread(ones) != 0
+    spread, live = _spread_live(y, lay, hidden)
     zero = torch.zeros_like(y)
     # padding rows of a padded layout: y is 0 there, but the cotangent may hold anything (inf, NaN) and exp(0) is 1 —
     # both variants are evaluated on live rows only and are exactly 0 elsewhere (the mask comes BEFORE the exp)
@@ -436,24 +451,17 @@ def _composed_softmax_grad(grad: Tensor, y: Tensor, lay: M.Lay, log: bool, hidde
 
 
 def softmax(data: Tensor, lay: M.Lay, log: bool, hidden) -> Tensor:
-    if data.dtype not in L.DTYPES:
-        L.require_device(data)
-        raise L.RuaError(f'softmax / log_softmax support {list(L.DTYPES)}; got {data.dtype}')
+    _require_dtype(data, L.DTYPES, _SOFTMAX_SUPPORT)
     if data.requires_grad and torch.is_grad_enabled():
         # contiguous HERE, inside the graph (as in reduce()): a copy made inside forward() would carry no history
         return _Softmax.apply(data.contiguous(), lay, bool(log), tuple(hidden))
-    return launch_softmax(lay, data.detach() if data.requires_grad else data, bool(log), tuple(hidden))
+    return launch_softmax(lay, _plain(data), bool(log), tuple(hidden))
 
 
 # ------------------------------------------------------------------ per-sequence softmax-weighted sum (an extension)
-def _pool_acc(dtype: torch.dtype) -> torch.dtype:
-    return torch.float64 if dtype == torch.float64 else torch.float32
-
-
 def _pool_check(values: Tensor, scores: Tensor) -> torch.device:
     dev = L.require_device(values, scores)
-    if values.dtype not in L.DTYPES:
-        raise L.RuaError(f'softmax_pool supports {list(L.DTYPES)}; got {values.dtype}')
+    _require_dtype(values, L.DTYPES, 'softmax_pool supports')
     if scores.dtype != values.dtype:
         raise L.RuaError(f'softmax_pool: the scores have dtype {scores.dtype}, the values {values.dtype}')
     if scores.device != values.device:
@@ -467,11 +475,10 @@ def launch_softmax_pool(lay: M.Lay, values: Tensor, scores: Tensor, hidden: Tupl
     read once, no [N, H] temporary exists.  out_acc: `out` comes unrounded, in the accumulator type (RUA_POOL_OUT_ACC) —
     what autograd keeps for a bf16 / f16 payload."""
     dev = _pool_check(values, scores)
-    lib = L.load()
     H = _prod(hidden)
     D = H // G if G else 1
     values, scores = values.contiguous(), scores.contiguous()
-    acc = _pool_acc(values.dtype)
+    acc = _acc_dtype(values.dtype)
     out_dtype = acc if out_acc else values.dtype
     if lay.B == 0 or lay.n_rows == 0 or H == 0:
         # (the entry point returns without a launch: every sequence is empty)
@@ -479,13 +486,8 @@ def launch_softmax_pool(lay: M.Lay, values: Tensor, scores: Tensor, hidden: Tupl
                 torch.full((lay.B, G), float('-inf'), dtype=acc, device=dev))
     out = torch.empty((lay.B,) + tuple(hidden), dtype=out_dtype, device=dev)
     lse = torch.empty((lay.B, G), dtype=acc, device=dev)
-    if _kernel_hook:
-        _kernel_hook('softmax_pool', True)
-    L.check(lib.rua_segment_softmax_pool(lay.ref(), L.ptr(values), L.ptr(scores), L.ptr(out), L.ptr(lse), H, D,
-                                         L.DTYPES[values.dtype] | (L.POOL_OUT_ACC if out_acc else 0), None,
-                                         L.stream_ptr(dev)), 'rua_segment_softmax_pool')
-    if _kernel_hook:
-        _kernel_hook('softmax_pool', False)
+    _call('softmax_pool', 'rua_segment_softmax_pool', dev, lay.ref(), L.ptr(values), L.ptr(scores), L.ptr(out),
+          L.ptr(lse), H, D, L.DTYPES[values.dtype] | (L.POOL_OUT_ACC if out_acc else 0), None)
     return out, lse
 
 
@@ -498,11 +500,10 @@ def launch_softmax_pool_backward(lay: M.Lay, grad: Tensor, values: Tensor, score
     dev = _pool_check(values, scores)
     L.require_device(grad, out, lse)
     out_acc = out.dtype != values.dtype
-    if out.dtype not in (values.dtype, _pool_acc(values.dtype)) or not out.is_contiguous() or not lse.is_contiguous():
+    if out.dtype not in (values.dtype, _acc_dtype(values.dtype)) or not out.is_contiguous() or not lse.is_contiguous():
         raise L.RuaError('softmax_pool backward: `out` is the contiguous forward output, in the payload or accumulator dtype')
     if grad.dtype != values.dtype or grad.shape != out.shape:
         raise L.RuaError('softmax_pool backward: the cotangent must have the dtype and shape of the output')
-    lib = L.load()
     H = _prod(hidden)
     D = H // G if G else 1
     grad, values, scores = grad.contiguous(), values.contiguous(), scores.contiguous()
@@ -512,14 +513,9 @@ def launch_softmax_pool_backward(lay: M.Lay, grad: Tensor, values: Tensor, score
                 torch.zeros(scores.shape, dtype=scores.dtype, device=dev) if want_scores else None)
     gv = torch.empty(values.shape, dtype=values.dtype, device=dev) if want_values else None
     gs = torch.empty(scores.shape, dtype=scores.dtype, device=dev) if want_scores else None
-    if _kernel_hook:
-        _kernel_hook('softmax_pool_bwd', True)
-    L.check(lib.rua_segment_softmax_pool_backward(lay.ref(), L.ptr(grad), L.ptr(values), L.ptr(scores), L.ptr(out),
-                                                  L.ptr(lse), L.ptr(gv), L.ptr(gs), H, D,
-                                                  L.DTYPES[values.dtype] | (L.POOL_OUT_ACC if out_acc else 0), None,
-                                                  L.stream_ptr(dev)), 'rua_segment_softmax_pool_backward')
-    if _kernel_hook:
-        _kernel_hook('softmax_pool_bwd', False)
+    _call('softmax_pool_bwd', 'rua_segment_softmax_pool_backward', dev, lay.ref(), L.ptr(grad), L.ptr(values),
+          L.ptr(scores), L.ptr(out), L.ptr(lse), L.ptr(gv), L.ptr(gs), H, D,
+          L.DTYPES[values.dtype] | (L.POOL_OUT_ACC if out_acc else 0), None)
     return gv, gs
 
 
@@ -552,48 +548,39 @@ def softmax_pool(values: Tensor, scores: Tensor, lay: M.Lay, hidden, G: int) -> 
     if torch.is_grad_enabled() and (values.requires_grad or scores.requires_grad):
         # contiguous HERE, before the Function (as in reduce()): a copy made inside forward() would carry no history
         return _SoftmaxPool.apply(values.contiguous(), scores.contiguous(), lay, tuple(hidden), int(G))
-    values = values.detach() if values.requires_grad else values
-    scores = scores.detach() if scores.requires_grad else scores
-    return launch_softmax_pool(lay, values, scores, tuple(hidden), int(G))[0]
+    return launch_softmax_pool(lay, _plain(values), _plain(scores), tuple(hidden), int(G))[0]
 
 
 # ------------------------------------------------------------------ per-sequence var_mean / standardize (an extension)
+_NORM_SUPPORT = 'var_mean / standardize support'
+
+
 def _norm_args(lay: M.Lay, data: Tensor, hidden, correction, eps=0.0, cut: bool = True):
-    dev = L.require_device(data)
-    if data.dtype not in L.DTYPES:
-        raise L.RuaError(f'var_mean / standardize support {list(L.DTYPES)}; got {data.dtype}')
+    code = _require_dtype(data, L.DTYPES, _NORM_SUPPORT)
     if isinstance(correction, bool) or not isinstance(correction, int) or correction < 0:
         raise L.RuaError(f'var_mean / standardize: correction is a non-negative integer; got {correction!r}')
     if not float(eps) >= 0.0:
         raise L.RuaError(f'standardize: eps is a non-negative float; got {eps!r}')
     H = _prod(hidden)
-    lib = L.load()
-    nbytes = lib.rua_norm_ws_bytes(lay.ref(), H, L.DTYPES[data.dtype]) if cut else 0    # > 0: few but long sequences get cut
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
-    return dev, lib, H, ws
+    return data.device, code, H, _workspace('rua_norm_ws_bytes', lay, H, code, data.device, cut)
 
 
 def launch_var_mean(lay: M.Lay, data: Tensor, hidden: Tuple[int, ...], correction: int = 1, want_var: bool = True,
                     want_mean: bool = True, mean_acc: bool = False) -> Tuple[Optional[Tensor], Optional[Tensor]]:
     """rua_segment_var_mean: (var, mean), each [B, *hidden] of the payload dtype, from ONE read of the payload.
     mean_acc: `mean` comes unrounded, in the accumulator type (RUA_NORM_MEAN_ACC) — what autograd keeps for bf16 / f16."""
-    dev, lib, H, ws = _norm_args(lay, data, hidden, correction)
+    dev, code, H, ws = _norm_args(lay, data, hidden, correction)
     data = data.contiguous()
     shape = (lay.B,) + tuple(hidden)
-    mean_dtype = _pool_acc(data.dtype) if mean_acc else data.dtype
+    mean_dtype = _acc_dtype(data.dtype) if mean_acc else data.dtype
     if lay.B == 0 or lay.n_rows == 0 or H == 0:
         # (the entry point returns without a launch: every sequence is empty)
         return (torch.full(shape, float('nan'), dtype=data.dtype, device=dev) if want_var else None,
                 torch.full(shape, float('nan'), dtype=mean_dtype, device=dev) if want_mean else None)
     var = torch.empty(shape, dtype=data.dtype, device=dev) if want_var else None
     mean = torch.empty(shape, dtype=mean_dtype, device=dev) if want_mean else None
-    if _kernel_hook:
-        _kernel_hook('var_mean', True)
-    L.check(lib.rua_segment_var_mean(lay.ref(), L.ptr(data), L.ptr(var), L.ptr(mean), H,
-                                     L.DTYPES[data.dtype] | (L.NORM_MEAN_ACC if mean_acc else 0), correction,
-                                     L.ptr(ws), L.stream_ptr(dev)), 'rua_segment_var_mean')
-    if _kernel_hook:
-        _kernel_hook('var_mean', False)
+    _call('var_mean', 'rua_segment_var_mean', dev, lay.ref(), L.ptr(data), L.ptr(var), L.ptr(mean), H,
+          code | (L.NORM_MEAN_ACC if mean_acc else 0), correction, L.ptr(ws))
     return var, mean
 
 
@@ -601,11 +588,11 @@ def launch_var_mean_backward(lay: M.Lay, data: Tensor, mean: Tensor, grad_var: O
                              grad_mean: Optional[Tensor], hidden: Tuple[int, ...], correction: int = 1,
                              out: Optional[Tensor] = None) -> Tensor:
     """rua_segment_var_mean_backward: one token-parallel launch; `mean` in the payload or the accumulator dtype."""
-    dev, lib, H, _ = _norm_args(lay, data, hidden, correction, cut=False)
+    dev, code, H, _ = _norm_args(lay, data, hidden, correction, cut=False)
     L.require_device(mean, grad_var, grad_mean)
     mean_acc = mean.dtype != data.dtype
     shape = (lay.B,) + tuple(hidden)
-    if mean.dtype not in (data.dtype, _pool_acc(data.dtype)) or tuple(mean.shape) != shape:
+    if mean.dtype not in (data.dtype, _acc_dtype(data.dtype)) or tuple(mean.shape) != shape:
         raise L.RuaError('var_mean backward: `mean` is the forward\'s [B, *hidden], in the payload or accumulator dtype')
     for g in (grad_var, grad_mean):
         if g is not None and (g.dtype != data.dtype or tuple(g.shape) != shape):
@@ -613,17 +600,9 @@ def launch_var_mean_backward(lay: M.Lay, data: Tensor, mean: Tensor, grad_var: O
     data, mean = data.contiguous(), mean.contiguous()
     grad_var = None if grad_var is None else grad_var.contiguous()
     grad_mean = None if grad_mean is None else grad_mean.contiguous()
-    if out is None:
-        out = torch.empty(data.shape, dtype=data.dtype, device=dev)      # padding rows: zeroed by the call
-    elif not out.is_contiguous() or out.dtype != data.dtype or out.shape != data.shape:
-        raise L.RuaError('var_mean backward target must be contiguous, of the payload dtype and of the payload shape')
-    if _kernel_hook:
-        _kernel_hook('var_mean_bwd', True)
-    L.check(lib.rua_segment_var_mean_backward(lay.ref(), L.ptr(data), L.ptr(mean), L.ptr(grad_var), L.ptr(grad_mean),
-                                              L.ptr(out), H, L.DTYPES[data.dtype] | (L.NORM_MEAN_ACC if mean_acc else 0),
-                                              correction, L.stream_ptr(dev)), 'rua_segment_var_mean_backward')
-    if _kernel_hook:
-        _kernel_hook('var_mean_bwd', False)
+    out = _target(out, data.shape, data.dtype, dev, 'var_mean backward' + _LIKE_PAYLOAD)     # padding rows: zeroed by the call
+    _call('var_mean_bwd', 'rua_segment_var_mean_backward', dev, lay.ref(), L.ptr(data), L.ptr(mean), L.ptr(grad_var),
+          L.ptr(grad_mean), L.ptr(out), H, code | (L.NORM_MEAN_ACC if mean_acc else 0), correction)
     return out
 
 
@@ -631,60 +610,40 @@ def launch_standardize(lay: M.Lay, data: Tensor, hidden: Tuple[int, ...], eps: f
                        out: Optional[Tensor] = None, want_rstd: bool = False) -> Tuple[Tensor, Optional[Tensor]]:
     """rua_segment_standardize: (y, rstd [B, *hidden] in the accumulator type or None); one launch (two for cut
     sequences), no [N, H] temporary.  `out` may be `data` itself."""
-    dev, lib, H, ws = _norm_args(lay, data, hidden, correction, eps)
+    dev, code, H, ws = _norm_args(lay, data, hidden, correction, eps)
     data = data.contiguous()
-    if out is None:
-        out = torch.empty(data.shape, dtype=data.dtype, device=dev)      # padding rows: zeroed by the call
-    elif not out.is_contiguous() or out.dtype != data.dtype or out.shape != data.shape:
-        raise L.RuaError('standardize target must be contiguous, of the payload dtype and of the payload shape')
+    out = _target(out, data.shape, data.dtype, dev, 'standardize' + _LIKE_PAYLOAD)      # padding rows: zeroed by the call
     rstd = None
     if want_rstd:
-        shape, acc = (lay.B,) + tuple(hidden), _pool_acc(data.dtype)
+        shape, acc = (lay.B,) + tuple(hidden), _acc_dtype(data.dtype)
         if lay.B == 0 or lay.n_rows == 0 or H == 0:                      # (no launch then: every sequence is empty)
             rstd = torch.full(shape, float('nan'), dtype=acc, device=dev)
         else:
             rstd = torch.empty(shape, dtype=acc, device=dev)
-    if _kernel_hook:
-        _kernel_hook('standardize', True)
-    L.check(lib.rua_segment_standardize(lay.ref(), L.ptr(data), L.ptr(out), L.ptr(rstd), H, L.DTYPES[data.dtype],
-                                        correction, float(eps), L.ptr(ws), L.stream_ptr(dev)), 'rua_segment_standardize')
-    if _kernel_hook:
-        _kernel_hook('standardize', False)
+    _call('standardize', 'rua_segment_standardize', dev, lay.ref(), L.ptr(data), L.ptr(out), L.ptr(rstd), H, code,
+          correction, float(eps), L.ptr(ws))
     return out, rstd
 
 
 def launch_standardize_backward(lay: M.Lay, y: Tensor, rstd: Tensor, grad: Tensor, hidden: Tuple[int, ...],
                                 correction: int = 0, out: Optional[Tensor] = None) -> Tensor:
     """rua_segment_standardize_backward: the gradient from the forward's output and rstd alone.  `out` may be `grad`."""
-    dev, lib, H, ws = _norm_args(lay, y, hidden, correction)
+    dev, code, H, ws = _norm_args(lay, y, hidden, correction)
     L.require_device(grad, rstd)
     if grad.dtype != y.dtype or grad.shape != y.shape:
         raise L.RuaError('standardize backward: the cotangent must have the dtype and shape of the output')
-    if rstd.dtype != _pool_acc(y.dtype) or tuple(rstd.shape) != (lay.B,) + tuple(hidden):
+    if rstd.dtype != _acc_dtype(y.dtype) or tuple(rstd.shape) != (lay.B,) + tuple(hidden):
         raise L.RuaError('standardize backward: `rstd` is the forward\'s [B, *hidden] in the accumulator dtype')
     y, grad, rstd = y.contiguous(), grad.contiguous(), rstd.contiguous()
-    if out is None:
-        out = torch.empty(y.shape, dtype=y.dtype, device=dev)
-    elif not out.is_contiguous() or out.dtype != y.dtype or out.shape != y.shape:
-        raise L.RuaError('standardize backward target must be contiguous, of the payload dtype and of the payload shape')
-    if _kernel_hook:
-        _kernel_hook('standardize_bwd', True)
-    L.check(lib.rua_segment_standardize_backward(lay.ref(), L.ptr(y), L.ptr(rstd), L.ptr(grad), L.ptr(out), H,
-                                                 L.DTYPES[y.dtype], correction, L.ptr(ws), L.stream_ptr(dev)),
-            'rua_segment_standardize_backward')
-    if _kernel_hook:
-        _kernel_hook('standardize_bwd', False)
+    out = _target(out, y.shape, y.dtype, dev, 'standardize backward' + _LIKE_PAYLOAD)
+    _call('standardize_bwd', 'rua_segment_standardize_backward', dev, lay.ref(), L.ptr(y), L.ptr(rstd), L.ptr(grad),
+          L.ptr(out), H, code, correction, L.ptr(ws))
     return out
 
 
 def _norm_pieces(ref: Tensor, lay: M.Lay, hidden, correction: int):
-    """What the composed (twice differentiable) gradients share: the per-sequence broadcast, the mask of live rows and
-    the [B, *hidden] counts n and n - c (NaN where n - c <= 0, as the kernels give)."""
-    def spread(v: Tensor) -> Tensor:                 # every sequence's row of `v` over the sequence's storage rows
-        return _ReduceBwd.apply(v.contiguous(), ref.detach(), v.detach(), lay, L.SUM, None)
-
-    ones = torch.ones((lay.B,) + tuple(hidden), dtype=ref.dtype, device=ref.device)
-    live = spread(ones) != 0
+    """_spread_live, and the [B, *hidden] counts n and n - c (NaN where n - c <= 0, as the kernels give)."""
+    spread, live = _spread_live(ref, lay, hidden)
     n = launch_reduce(lay, live.to(ref.dtype), L.SUM, hidden=tuple(hidden), reference_initial=False)
     dof = n - correction
     dof = torch.where(dof > 0, dof, torch.full_like(dof, float('nan')))
@@ -776,59 +735,34 @@ def _composed_var_mean_grad(grad_var: Optional[Tensor], grad_mean: Optional[Tens
     return torch.where(live, total, zero)
 
 
-def _norm_refuse(data: Tensor) -> None:
-    if data.dtype not in L.DTYPES:
-        L.require_device(data)
-        raise L.RuaError(f'var_mean / standardize support {list(L.DTYPES)}; got {data.dtype}')
-
-
 def var_mean(data: Tensor, lay: M.Lay, hidden, correction: int = 1, want_var: bool = True,
              want_mean: bool = True) -> Tuple[Optional[Tensor], Optional[Tensor]]:
-    _norm_refuse(data)
+    _require_dtype(data, L.DTYPES, _NORM_SUPPORT)
     if data.requires_grad and torch.is_grad_enabled():
         # contiguous HERE, inside the graph (as in reduce()): a copy made inside forward() would carry no history
         return _VarMean.apply(data.contiguous(), lay, tuple(hidden), correction)
-    return launch_var_mean(lay, data.detach() if data.requires_grad else data, tuple(hidden), correction,
-                           want_var=want_var, want_mean=want_mean)
+    return launch_var_mean(lay, _plain(data), tuple(hidden), correction, want_var=want_var, want_mean=want_mean)
 
 
 def standardize(data: Tensor, lay: M.Lay, hidden, eps: float = 1e-5, correction: int = 0) -> Tensor:
-    _norm_refuse(data)
+    _require_dtype(data, L.DTYPES, _NORM_SUPPORT)
     if data.requires_grad and torch.is_grad_enabled():
         return _Standardize.apply(data.contiguous(), lay, tuple(hidden), float(eps), correction)[0]
-    return launch_standardize(lay, data.detach() if data.requires_grad else data, tuple(hidden), eps, correction)[0]
+    return launch_standardize(lay, _plain(data), tuple(hidden), eps, correction)[0]
 
 
 # ------------------------------------------------------------------ per-sequence cumsum (an extension)
-def _cumsum_dtype(data: Tensor) -> int:
-    if data.dtype not in L.SCAN_DTYPES:
-        L.require_device(data)
-        raise L.RuaError(f'cumsum supports {list(L.SCAN_DTYPES)}; got {data.dtype}')
-    return L.SCAN_DTYPES[data.dtype]
-
-
 def launch_cumsum(lay: M.Lay, data: Tensor, reverse: bool, hidden: Tuple[int, ...], out: Optional[Tensor] = None,
                   cut: bool = True) -> Tensor:
     """rua_segment_cumsum: one launch (two for cut sequences), one read and one write of the payload.  `out` may be
     `data` itself.  cut=False withholds the workspace (the same bits from one workgroup per unit: a developer A/B)."""
-    dev = L.require_device(data)
-    code = _cumsum_dtype(data)
-    lib = L.load()
-    H = _prod(hidden)
-    nbytes = lib.rua_cumsum_ws_bytes(lay.ref(), H, code) if cut else 0      # > 0: few but long sequences get cut
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    code = _require_dtype(data, L.SCAN_DTYPES, 'cumsum supports')
+    dev, H = data.device, _prod(hidden)
+    ws = _workspace('rua_cumsum_ws_bytes', lay, H, code, dev, cut)
     data = data.contiguous()
-    if out is None:
-        out = torch.empty(data.shape, dtype=data.dtype, device=dev)      # padding rows: zeroed by the call
-    elif not out.is_contiguous() or out.dtype != data.dtype or out.shape != data.shape:
-        raise L.RuaError('cumsum target must be contiguous, of the payload dtype and of the payload shape')
-    name = 'cumsum_rev' if reverse else 'cumsum'
-    if _kernel_hook:
-        _kernel_hook(name, True)
-    L.check(lib.rua_segment_cumsum(lay.ref(), L.ptr(data), L.ptr(out), H, code, int(bool(reverse)), L.ptr(ws),
-                                   L.stream_ptr(dev)), 'rua_segment_cumsum')
-    if _kernel_hook:
-        _kernel_hook(name, False)
+    out = _target(out, data.shape, data.dtype, dev, 'cumsum' + _LIKE_PAYLOAD)      # padding rows: zeroed by the call
+    _call('cumsum_rev' if reverse else 'cumsum', 'rua_segment_cumsum', dev, lay.ref(), L.ptr(data), L.ptr(out), H, code,
+          int(bool(reverse)), L.ptr(ws))
     return out
 
 
@@ -847,21 +781,14 @@ class _Cumsum(torch.autograd.Function):
 
 
 def cumsum(data: Tensor, lay: M.Lay, reverse: bool, hidden) -> Tensor:
-    _cumsum_dtype(data)
+    _require_dtype(data, L.SCAN_DTYPES, 'cumsum supports')
     if data.is_floating_point() and data.requires_grad and torch.is_grad_enabled():
         # contiguous HERE, before the Function (as in reduce()): a copy made inside forward() would carry no history
         return _Cumsum.apply(data.contiguous(), lay, bool(reverse), tuple(hidden))
-    return launch_cumsum(lay, data.detach() if data.requires_grad else data, bool(reverse), tuple(hidden))
+    return launch_cumsum(lay, _plain(data), bool(reverse), tuple(hidden))
 
 
 # ------------------------------------------------------------------ per-sequence gated linear recurrence (an extension)
-def _linear_scan_dtype(data: Tensor) -> int:
-    if data.dtype not in L.DTYPES:
-        L.require_device(data)
-        raise L.RuaError(f'linear_scan supports {list(L.DTYPES)}; got {data.dtype}')
-    return L.DTYPES[data.dtype]
-
-
 def _gate_arg(data: Tensor, gate) -> Tuple[Optional[Tensor], float]:
     """(the gate tensor or None, the scalar gate): a tensor of the payload's storage shape, dtype and device, or ONE
     Python number — checked before any launch."""
@@ -885,26 +812,15 @@ def launch_linear_scan(lay: M.Lay, data: Tensor, gate, reverse: bool, hidden: Tu
     read once, the result is written once.  `gate` is a tensor or a Python float (passed by value: no gate tensor
     exists).  `out` may be `data` itself, never the gate.  cut=False withholds the workspace (the same bits from one
     workgroup per unit: a developer A/B)."""
-    dev = L.require_device(data)
-    code = _linear_scan_dtype(data)
+    code = _require_dtype(data, L.DTYPES, 'linear_scan supports')
     gt, gs = _gate_arg(data, gate)
-    lib = L.load()
-    H = _prod(hidden)
-    nbytes = lib.rua_linear_scan_ws_bytes(lay.ref(), H, code) if cut else 0      # > 0: few but long sequences get cut
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    dev, H = data.device, _prod(hidden)
+    ws = _workspace('rua_linear_scan_ws_bytes', lay, H, code, dev, cut)
     data = data.contiguous()
     gt = None if gt is None else gt.contiguous()
-    if out is None:
-        out = torch.empty(data.shape, dtype=data.dtype, device=dev)      # padding rows: zeroed by the call
-    elif not out.is_contiguous() or out.dtype != data.dtype or out.shape != data.shape:
-        raise L.RuaError('linear_scan target must be contiguous, of the payload dtype and of the payload shape')
-    name = 'linear_scan_rev' if reverse else 'linear_scan'
-    if _kernel_hook:
-        _kernel_hook(name, True)
-    L.check(lib.rua_segment_linear_scan(lay.ref(), L.ptr(data), L.ptr(gt), gs, L.ptr(out), H, code, int(bool(reverse)),
-                                        L.ptr(ws), L.stream_ptr(dev)), 'rua_segment_linear_scan')
-    if _kernel_hook:
-        _kernel_hook(name, False)
+    out = _target(out, data.shape, data.dtype, dev, 'linear_scan' + _LIKE_PAYLOAD)      # padding rows: zeroed by the call
+    _call('linear_scan_rev' if reverse else 'linear_scan', 'rua_segment_linear_scan', dev, lay.ref(), L.ptr(data),
+          L.ptr(gt), gs, L.ptr(out), H, code, int(bool(reverse)), L.ptr(ws))
     return out
 
 
@@ -913,8 +829,8 @@ def launch_linear_scan_backward(lay: M.Lay, grad: Tensor, gate, h: Optional[Tens
                                 cut: bool = True) -> Tuple[Tensor, Optional[Tensor]]:
     """rua_segment_linear_scan_backward: (grad_x, grad_gate or None) of the scan whose direction was `reverse`, from the
     cotangent, the gate and the saved output `h` — one launch (two for cut sequences).  Padding rows of both are zeros."""
-    dev = L.require_device(grad)
-    code = _linear_scan_dtype(grad)
+    code = _require_dtype(grad, L.DTYPES, 'linear_scan supports')
+    dev = grad.device
     gt, gs = _gate_arg(grad, gate)
     want_gate = bool(want_gate) and gt is not None
     if want_gate:
@@ -922,22 +838,15 @@ def launch_linear_scan_backward(lay: M.Lay, grad: Tensor, gate, h: Optional[Tens
         if h is None or h.dtype != grad.dtype or h.shape != grad.shape:
             raise L.RuaError('linear_scan backward: the saved output must have the dtype and shape of the cotangent')
         h = h.contiguous()
-    lib = L.load()
     H = _prod(hidden)
-    nbytes = lib.rua_linear_scan_ws_bytes(lay.ref(), H, code) if cut else 0
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    ws = _workspace('rua_linear_scan_ws_bytes', lay, H, code, dev, cut)
     grad = grad.contiguous()
     gt = None if gt is None else gt.contiguous()
     gx = torch.empty(grad.shape, dtype=grad.dtype, device=dev)
     ga = torch.empty(grad.shape, dtype=grad.dtype, device=dev) if want_gate else None
-    name = 'linear_scan_rev_bwd' if reverse else 'linear_scan_bwd'
-    if _kernel_hook:
-        _kernel_hook(name, True)
-    L.check(lib.rua_segment_linear_scan_backward(lay.ref(), L.ptr(grad), L.ptr(gt), gs, L.ptr(h if want_gate else None),
-                                                 L.ptr(gx), L.ptr(ga), H, code, int(bool(reverse)), L.ptr(ws),
-                                                 L.stream_ptr(dev)), 'rua_segment_linear_scan_backward')
-    if _kernel_hook:
-        _kernel_hook(name, False)
+    _call('linear_scan_rev_bwd' if reverse else 'linear_scan_bwd', 'rua_segment_linear_scan_backward', dev, lay.ref(),
+          L.ptr(grad), L.ptr(gt), gs, L.ptr(h if want_gate else None), L.ptr(gx), L.ptr(ga), H, code, int(bool(reverse)),
+          L.ptr(ws))
     return gx, ga
 
 
@@ -995,24 +904,17 @@ def _composed_linear_scan_grad(grad: Tensor, gate: Optional[Tensor], gate_scalar
 
 
 def linear_scan(data: Tensor, gate, lay: M.Lay, reverse: bool, hidden) -> Tensor:
-    _linear_scan_dtype(data)
+    _require_dtype(data, L.DTYPES, 'linear_scan supports')
     gt, gs = _gate_arg(data, gate)
     if torch.is_grad_enabled() and (data.requires_grad or (gt is not None and gt.requires_grad)):
         # contiguous HERE, before the Function (as in reduce()): a copy made inside forward() would carry no history
         return _LinearScan.apply(data.contiguous(), None if gt is None else gt.contiguous(), gs, lay, bool(reverse),
                                  tuple(hidden))
-    data = data.detach() if data.requires_grad else data
-    if gt is not None and gt.requires_grad:
-        gt = gt.detach()
-    return launch_linear_scan(lay, data, gs if gt is None else gt, bool(reverse), tuple(hidden))
+    return launch_linear_scan(lay, _plain(data), gs if gt is None else _plain(gt), bool(reverse), tuple(hidden))
 
 
 # ------------------------------------------------------------------ per-sequence argmax / argmin (an extension)
-def _argreduce_dtype(data: Tensor) -> int:
-    if data.dtype not in L.SCAN_DTYPES:
-        L.require_device(data)
-        raise L.RuaError(f'argmax / argmin support {list(L.SCAN_DTYPES)}; got {data.dtype}')
-    return L.SCAN_DTYPES[data.dtype]
+_ARG_SUPPORT = 'argmax / argmin support'
 
 
 def launch_argreduce(lay: M.Lay, data: Tensor, op: int, hidden: Tuple[int, ...], want_values: bool = True,
@@ -1020,25 +922,17 @@ def launch_argreduce(lay: M.Lay, data: Tensor, op: int, hidden: Tuple[int, ...],
     """rua_segment_argreduce: (values or None, index), both [B, *hidden] and written completely by the call — one launch
     (two for cut sequences), one read of the payload.  cut=False withholds the workspace (the same bits from one
     workgroup per unit: a developer A/B)."""
-    dev = L.require_device(data)
-    code = _argreduce_dtype(data)
+    code = _require_dtype(data, L.SCAN_DTYPES, _ARG_SUPPORT)
     if op not in (L.MAX, L.MIN):
         raise L.RuaError('argreduce: the operator is MAX or MIN')
-    lib = L.load()
-    H = _prod(hidden)
-    nbytes = lib.rua_argreduce_ws_bytes(lay.ref(), H, code) if cut else 0    # > 0: few but long sequences get cut
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    dev, H = data.device, _prod(hidden)
+    ws = _workspace('rua_argreduce_ws_bytes', lay, H, code, dev, cut)
     data = data.contiguous()
     shape = (lay.B,) + tuple(hidden)
     index = torch.empty(shape, dtype=torch.int64, device=dev)
     values = torch.empty(shape, dtype=data.dtype, device=dev) if want_values else None
     name = ('seq_max' if op == L.MAX else 'seq_min') if want_values else ('argmax' if op == L.MAX else 'argmin')
-    if _kernel_hook:
-        _kernel_hook(name, True)
-    L.check(lib.rua_segment_argreduce(lay.ref(), L.ptr(data), L.ptr(values), L.ptr(index), H, code, op, L.ptr(ws),
-                                      L.stream_ptr(dev)), 'rua_segment_argreduce')
-    if _kernel_hook:
-        _kernel_hook(name, False)
+    _call(name, 'rua_segment_argreduce', dev, lay.ref(), L.ptr(data), L.ptr(values), L.ptr(index), H, code, op, L.ptr(ws))
     return values, index
 
 
@@ -1051,18 +945,12 @@ def _index_arg(lay: M.Lay, index: Tensor, hidden: Tuple[int, ...], dev) -> Tenso
 
 def launch_take(lay: M.Lay, data: Tensor, index: Tensor, hidden: Tuple[int, ...]) -> Tensor:
     """rua_segment_take: out[b, h] = data[row(b, index[b, h]), h], 0 where the position names no token of b."""
-    dev = L.require_device(data)
-    code = _argreduce_dtype(data)
-    lib = L.load()
+    code = _require_dtype(data, L.SCAN_DTYPES, _ARG_SUPPORT)
+    dev = data.device
     index = _index_arg(lay, index, hidden, dev)
     data = data.contiguous()
     out = torch.empty((lay.B,) + tuple(hidden), dtype=data.dtype, device=dev)
-    if _kernel_hook:
-        _kernel_hook('take', True)
-    L.check(lib.rua_segment_take(lay.ref(), L.ptr(data), L.ptr(index), L.ptr(out), _prod(hidden), code,
-                                 L.stream_ptr(dev)), 'rua_segment_take')
-    if _kernel_hook:
-        _kernel_hook('take', False)
+    _call('take', 'rua_segment_take', dev, lay.ref(), L.ptr(data), L.ptr(index), L.ptr(out), _prod(hidden), code)
     return out
 
 
@@ -1070,23 +958,14 @@ def launch_put(lay: M.Lay, src: Tensor, index: Tensor, hidden: Tuple[int, ...], 
                out: Optional[Tensor] = None) -> Tensor:
     """rua_segment_put: a payload of storage shape `shape` that holds src[b, h] at token index[b, h] of sequence b and
     zeros everywhere else, padding rows included — written completely by the call (no pre-zeroing)."""
-    dev = L.require_device(src)
-    code = _argreduce_dtype(src)
-    lib = L.load()
+    code = _require_dtype(src, L.SCAN_DTYPES, _ARG_SUPPORT)
+    dev = src.device
     index = _index_arg(lay, index, hidden, dev)
     if tuple(src.shape) != (lay.B,) + tuple(hidden):
         raise L.RuaError('put: the source is a [B, *hidden] tensor')
     src = src.contiguous()
-    if out is None:
-        out = torch.empty(tuple(shape), dtype=src.dtype, device=dev)
-    elif not out.is_contiguous() or out.dtype != src.dtype or tuple(out.shape) != tuple(shape):
-        raise L.RuaError('put target must be contiguous, of the source dtype and of the payload shape')
-    if _kernel_hook:
-        _kernel_hook('put', True)
-    L.check(lib.rua_segment_put(lay.ref(), L.ptr(src), L.ptr(index), L.ptr(out), _prod(hidden), code,
-                                L.stream_ptr(dev)), 'rua_segment_put')
-    if _kernel_hook:
-        _kernel_hook('put', False)
+    out = _target(out, shape, src.dtype, dev, 'put target must be contiguous, of the source dtype and of the payload shape')
+    _call('put', 'rua_segment_put', dev, lay.ref(), L.ptr(src), L.ptr(index), L.ptr(out), _prod(hidden), code)
     return out
 
 
@@ -1143,25 +1022,25 @@ def _wants_grad(t: Tensor) -> bool:
 
 
 def argreduce(data: Tensor, lay: M.Lay, op: int, hidden, want_values: bool = True) -> Tuple[Optional[Tensor], Tensor]:
-    _argreduce_dtype(data)
+    _require_dtype(data, L.SCAN_DTYPES, _ARG_SUPPORT)
     if want_values and _wants_grad(data):
         # contiguous HERE, before the Function (as in reduce()): a copy made inside forward() would carry no history
         return _ArgReduce.apply(data.contiguous(), lay, op, tuple(hidden))
-    return launch_argreduce(lay, data.detach() if data.requires_grad else data, op, tuple(hidden), want_values)
+    return launch_argreduce(lay, _plain(data), op, tuple(hidden), want_values)
 
 
 def put(src: Tensor, index: Tensor, lay: M.Lay, hidden, shape) -> Tensor:
-    _argreduce_dtype(src)
+    _require_dtype(src, L.SCAN_DTYPES, _ARG_SUPPORT)
     if _wants_grad(src):
         return _Put.apply(src.contiguous(), index, lay, tuple(hidden), tuple(shape))
-    return launch_put(lay, src.detach() if src.requires_grad else src, index, tuple(hidden), tuple(shape))
+    return launch_put(lay, _plain(src), index, tuple(hidden), tuple(shape))
 
 
 def take(data: Tensor, index: Tensor, lay: M.Lay, hidden) -> Tensor:
-    _argreduce_dtype(data)
+    _require_dtype(data, L.SCAN_DTYPES, _ARG_SUPPORT)
     if _wants_grad(data):
         return _Take.apply(data.contiguous(), index, lay, tuple(hidden))
-    return launch_take(lay, data.detach() if data.requires_grad else data, index, tuple(hidden))
+    return launch_take(lay, _plain(data), index, tuple(hidden))
 
 
 # ------------------------------------------------------------------ scatter-sum of rows (adjoint of a row gather)
@@ -1242,9 +1121,7 @@ def scatter_sum_rows(rows: Tensor, index: Tensor, n_out: int) -> Tensor:
     lay.heavy_tail = True
     if rows.dtype in L.INT_DTYPES:        # (integer payloads carry no gradient: the integer reducer, for completeness)
         out = torch.empty((n_out,) + hidden, dtype=rows.dtype, device=rows.device)
-        H = 1
-        for d in hidden:
-            H *= d
+        H = _prod(hidden)
         split, ws = int_split_workspace(int(rows.size(0)), H, rows.dtype, rows.device)
         L.check(L.load().rua_segment_reduce(lay.ref(), L.ptr(perm), L.ptr(rows.contiguous()), L.ptr(out), H,
                                             L.INT_DTYPES[rows.dtype], L.SUM, 0, 0, None, split, L.ptr(ws), None,
@@ -1254,13 +1131,6 @@ def scatter_sum_rows(rows: Tensor, index: Tensor, n_out: int) -> Tensor:
 
 
 # ------------------------------------------------------------------ a row scatter autograd sees (core/set.py)
-def _prod(shape) -> int:
-    n = 1
-    for d in shape:
-        n *= d
-    return n
-
-
 def setitem_backward(plan: MovePlan, grad: Tensor, hidden: Tuple[int, ...], want_value: bool, want_raw: bool):
     """rua_setitem_backward for the scatter `plan` describes: (grad_value [M, *hidden] or None, grad_raw or None)."""
     dev = L.require_device(grad)
@@ -1271,12 +1141,8 @@ def setitem_backward(plan: MovePlan, grad: Tensor, hidden: Tuple[int, ...], want
     g_raw = torch.empty_like(grad) if want_raw else None
     if rb == 0 or (m == 0 and not want_raw):
         return (g_value.zero_() if want_value and g_value.numel() else g_value), g_raw
-    if _kernel_hook:
-        _kernel_hook(plan.name + '_bwd', True)
-    L.check(L.load().rua_setitem_backward(plan.dst.ref(), plan.src.ref(), L.ptr(grad), L.ptr(g_value), L.ptr(g_raw), rb,
-                                          0, L.stream_ptr(dev)), 'rua_setitem_backward')
-    if _kernel_hook:
-        _kernel_hook(plan.name + '_bwd', False)
+    _call(plan.name + '_bwd', 'rua_setitem_backward', dev, plan.dst.ref(), plan.src.ref(), L.ptr(grad), L.ptr(g_value),
+          L.ptr(g_raw), rb, 0)
     return g_value, g_raw
 
 

@@ -22,12 +22,11 @@ The values of `seq_max` / `seq_min` are differentiable: the gradient goes to the
 rule, where `reduce_max` splits it among ties as `torch.segment_reduce` does.  Autograd saves only the [B, *H] index; the
 backward is rua_segment_put, whose own backward is rua_segment_take and so on: derivatives of any order.
 """
-from typing import NamedTuple, Tuple
+from typing import NamedTuple
 
 from torchrua_amd import _lib as K
-from torchrua_amd import _meta as M
 from torchrua_amd import _ops as O
-from torchrua_amd.layout import C, L, P, R, T, Z, describe
+from torchrua_amd.layout import C, L, P, R, T, Z, cat_lay, lay_hidden
 
 __all__ = ['segment_argmax', 'segment_argmin', 'argmax', 'argmin', 'seq_max', 'seq_min']
 
@@ -39,9 +38,7 @@ class SeqExtreme(NamedTuple):
 
 
 def _segment(tensor: T, segment_sizes: T, op: int) -> T:
-    K.require_device(tensor, segment_sizes)
-    lay = M.lay_cat(segment_sizes, segment_sizes.numel(), int(tensor.size(0)))
-    return O.argreduce(tensor, lay, op, tuple(tensor.shape[1:]), want_values=False)[1]
+    return O.argreduce(tensor, cat_lay(tensor, segment_sizes), op, tuple(tensor.shape[1:]), want_values=False)[1]
 
 
 def segment_argmax(tensor: T, segment_sizes: T) -> T:
@@ -55,35 +52,27 @@ def segment_argmin(tensor: T, segment_sizes: T) -> T:
     return _segment(tensor, segment_sizes, K.MIN)
 
 
-def _lay_hidden(sequence: Z) -> Tuple[M.Lay, Tuple[int, ...]]:
-    data = sequence.data
-    K.require_device(data)
-    if isinstance(sequence, P):
-        return M.lay_pack(sequence), tuple(data.shape[1:])
-    return describe(sequence), tuple(data.shape[1:]) if isinstance(sequence, C) else tuple(data.shape[2:])
-
-
 def argmax(sequence: Z) -> T:
     """The token position of every sequence's largest element, per column: LongTensor [B, *H]; -1 where empty."""
-    lay, hidden = _lay_hidden(sequence)
+    lay, hidden = lay_hidden(sequence)
     return O.argreduce(sequence.data, lay, K.MAX, hidden, want_values=False)[1]
 
 
 def argmin(sequence: Z) -> T:
     """The token position of every sequence's smallest element, per column: LongTensor [B, *H]; -1 where empty."""
-    lay, hidden = _lay_hidden(sequence)
+    lay, hidden = lay_hidden(sequence)
     return O.argreduce(sequence.data, lay, K.MIN, hidden, want_values=False)[1]
 
 
 def seq_max(sequence: Z) -> SeqExtreme:
     """(values, indices) of every sequence's largest element, like torch.max(dim); the values are differentiable."""
-    lay, hidden = _lay_hidden(sequence)
+    lay, hidden = lay_hidden(sequence)
     return SeqExtreme(*O.argreduce(sequence.data, lay, K.MAX, hidden))
 
 
 def seq_min(sequence: Z) -> SeqExtreme:
     """(values, indices) of every sequence's smallest element, like torch.min(dim); the values are differentiable."""
-    lay, hidden = _lay_hidden(sequence)
+    lay, hidden = lay_hidden(sequence)
     return SeqExtreme(*O.argreduce(sequence.data, lay, K.MIN, hidden))
 
 

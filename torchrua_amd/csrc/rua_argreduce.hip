@@ -31,12 +31,10 @@ extern std::atomic<int> g_trace_on;        // the dispatch trace (rua_reduce.hip
 void trace_add(const char* rec);
 
 constexpr int AR_SLOTS = 32;               // tokens a step of a sequence puts side by side
-constexpr int AR_BLOCK_TOK = 2048;         // tokens per block: 32-bit offsets inside, a 64-bit base outside
+constexpr int AR_BLOCK_TOK = SEG_BLOCK_TOK; // tokens per block: 32-bit offsets inside, a 64-bit base outside
 constexpr int AR_LPR = 8;                  // rows form: 16-byte lanes per row chunk (128 bytes)
 constexpr int AR_ROWS_UNR = 4;             // rows form: rows in flight per thread
 constexpr int AR_LANES_UNR = 8;            // lanes form: tokens in flight per lane
-constexpr int64_t AR_CUT_MAX_UNITS = 1024; // fewer (sequence x chunk) units than this leave the chip idle ...
-constexpr int64_t AR_CUT_MIN_LEN = 4 * AR_BLOCK_TOK;   // ... when the sequences are this long: cut them across workgroups
 enum { AR_FULL = 0, AR_PARTIAL = 1, AR_FINISH = 2 };
 static_assert(AR_SLOTS * AR_LPR == RUA_BLOCK, "a step of the rows form is a workgroup");
 
@@ -378,38 +376,10 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_put_kernel(rua_layout L, const 
 }
 
 // ---------------------------------------------------------------- host side
-static int ar_esize(int32_t dtype) {
-  switch (dtype) {
-    case RUA_F32: return 4;
-    case RUA_BF16: case RUA_F16: return 2;
-    case RUA_F64: case RUA_I64: return 8;
-  }
-  return 0;
-}
-
-struct ar_plan {
-  int n_chunks;       // 128-byte column chunks of a row
-  int maxblk;         // > 0: the cut form, with this many blocks per sequence
-  int64_t ws_bytes;   // what the cut form needs: a position and a value per block and (padded) column
-};
-
-static ar_plan ar_make_plan(const rua_layout& L, int64_t H, int32_t dtype) {
-  ar_plan p = {0, 0, 0};
-  const int es = ar_esize(dtype);
-  if (!es || H <= 0 || L.B <= 0) return p;
-  const int64_t row_bytes = H * es;
-  if ((row_bytes + 127) / 128 > 0x7fffffff) return p;
-  p.n_chunks = (int)((row_bytes + 127) / 128);
-  if (row_bytes <= 16) return p;
-  const int64_t bound = sm_len_bound(L);
-  if (L.B * p.n_chunks < AR_CUT_MAX_UNITS && bound >= AR_CUT_MIN_LEN) {
-    const int64_t mb = (bound + AR_BLOCK_TOK - 1) / AR_BLOCK_TOK;
-    if (mb <= 0x7fffffff / AR_CUT_MAX_UNITS) {
-      p.maxblk = (int)mb;
-      p.ws_bytes = L.B * mb * p.n_chunks * (128 / es) * (8 + (es == 8 ? 8 : 4));
-    }
-  }
-  return p;
+// the cut form keeps a position (8 bytes) and a value (one accumulator) per block and (padded) column
+static seg_plan ar_make_plan(const rua_layout& L, int64_t H, int32_t dtype) {
+  const int es = seg_esize(dtype, true);
+  return seg_make_plan(L, H, es, 8 + (es == 8 ? 8 : 4));
 }
 
 template <typename E, int OP>
@@ -424,11 +394,10 @@ static int ar_launch(const rua_layout& L, const void* x, void* values, int64_t* 
     return RUA_EALIGN;                                         // (elements themselves are always aligned)
 
   if (row_bytes <= 16) {
-    const uint64_t mix = (uint64_t)row_bytes | base | 16u;
-    const int W = (int)(mix & (~mix + 1));
-    const int64_t waves = (L.B + 1) / 2;
-    const int64_t grid = (waves + RUA_WAVES_PER_BLOCK - 1) / RUA_WAVES_PER_BLOCK;
-    if (grid > 0x7fffffffLL) return RUA_ERANGE;
+    const seg_lanes ln = seg_lanes_geometry(row_bytes, base, L.B);
+    const int W = ln.W;
+    const int64_t grid = ln.grid;
+    if (!grid) return RUA_ERANGE;
     if (g_trace_on.load(std::memory_order_relaxed)) {
       snprintf(rec, sizeof rec, "seg_argreduce_lanes_kernel T=%s op=%s W=%d H=%d values=%d kind=%d", E::name(), opn, W,
                (int)H, (int)(values != nullptr), L.kind);
@@ -439,14 +408,14 @@ static int ar_launch(const rua_layout& L, const void* x, void* values, int64_t* 
     return (int)hipGetLastError();
   }
 
-  const ar_plan p = ar_make_plan(L, H, dtype);
+  const seg_plan p = ar_make_plan(L, H, dtype);
   if (p.n_chunks <= 0) return RUA_ERANGE;
   const bool al = row_bytes % 16 == 0 && base % 16 == 0;
   const bool cut = ws != nullptr && p.maxblk > 0;
   if (cut && (uint64_t)(uintptr_t)ws % 8) return RUA_EALIGN;
   const int64_t units = L.B * (int64_t)p.n_chunks;
-  const int64_t grid = units * (cut ? p.maxblk : 1);
-  if (grid > 0x7fffffffLL) return RUA_ERANGE;
+  const int64_t grid = seg_rows_grid(L, p, cut);
+  if (!grid) return RUA_ERANGE;
 
 #define RUA_AR_ROWS(ALV, MODE, GRID)                                                                                   \
   hipLaunchKernelGGL((seg_argreduce_rows_kernel<E, OP, ALV>), dim3((unsigned)(GRID)), dim3(RUA_BLOCK), 0, s, L,        \
@@ -486,12 +455,13 @@ static int ar_launch_op(const rua_layout& L, const void* x, void* values, int64_
 
 static int ar_dispatch(const rua_layout* lay, const void* x, void* values, int64_t* index, int64_t H, int32_t dtype,
                        int32_t op, void* ws, void* stream) {
+  const int es = seg_esize(dtype, true);
   int e;
-  if ((e = sm_check_layout(lay)) != 0) return e;
-  if (H < 0 || !ar_esize(dtype) || (op != RUA_MAX && op != RUA_MIN)) return RUA_EINVAL;
+  if ((e = seg_check_entry(lay, H, es)) != 0) return e;
+  if (op != RUA_MAX && op != RUA_MIN) return RUA_EINVAL;
   if (lay->B == 0 || H == 0) return 0;
   if (!index || (!x && lay->n_rows > 0)) return RUA_EINVAL;    // (an empty storage still owes every sequence its -1)
-  if ((double)lay->n_rows * (double)H * ar_esize(dtype) >= 9.0e18 || (double)lay->B * (double)H >= 1.0e18)
+  if (seg_too_large(lay, H, es) || (double)lay->B * (double)H >= 1.0e18)
     return RUA_ERANGE;
   hipStream_t s = (hipStream_t)stream;
   switch (dtype) {
@@ -505,13 +475,6 @@ static int ar_dispatch(const rua_layout* lay, const void* x, void* values, int64
 }
 
 // take / put move elements as bits: one instantiation per element size
-static int ar_check_rows(const rua_layout* lay, int64_t H, int32_t dtype) {
-  int e;
-  if ((e = sm_check_layout(lay)) != 0) return e;
-  if (H < 0 || !ar_esize(dtype)) return RUA_EINVAL;
-  return 0;
-}
-
 template <typename U>
 static int take_launch(const rua_layout& L, const void* data, const int64_t* index, void* out, int64_t H, hipStream_t s) {
   if (((uint64_t)(uintptr_t)data | (uint64_t)(uintptr_t)out) % sizeof(U) || (uint64_t)(uintptr_t)index % 8) return RUA_EALIGN;
@@ -540,10 +503,9 @@ static int put_launch(const rua_layout& L, const void* src, const int64_t* index
   if (chunks > 0x7fffffff) return RUA_ERANGE;
   const bool al = row_bytes % 16 == 0 && (uint64_t)(uintptr_t)out % 16 == 0;
   const int64_t units = L.B * chunks;
-  const int64_t bound = sm_len_bound(L);
-  int64_t nblk = 1;
-  if (units < AR_CUT_MAX_UNITS && bound >= AR_CUT_MIN_LEN) nblk = (bound + AR_BLOCK_TOK - 1) / AR_BLOCK_TOK;
-  if (nblk > 0x7fffffff / AR_CUT_MAX_UNITS) return RUA_ERANGE;
+  const int64_t cutblk = seg_cut_blocks(L, units);             // (rows of one vector are cut too: a row per thread)
+  const int64_t nblk = cutblk > 0 ? cutblk : 1;
+  if (nblk > SEG_CUT_MAX_BLOCKS) return RUA_ERANGE;
   const int64_t grid = units * nblk;
   if (grid > 0x7fffffffLL) return RUA_ERANGE;
   if (g_trace_on.load(std::memory_order_relaxed)) {
@@ -575,15 +537,16 @@ extern "C" int rua_segment_argreduce(const rua_layout* lay, const void* data, vo
 
 extern "C" int rua_segment_take(const rua_layout* lay, const void* data, const int64_t* index, void* out, int64_t H,
                                 int32_t dtype, void* stream) {
+  const int es = rua::seg_esize(dtype, true);
   int e;
-  if ((e = rua::ar_check_rows(lay, H, dtype)) != 0) return e;
+  if ((e = rua::seg_check_entry(lay, H, es)) != 0) return e;
   if (lay->B == 0 || H == 0) return 0;
   if (!index || !out || (!data && lay->n_rows > 0)) return RUA_EINVAL;
   if (data && data == out) return RUA_EINVAL;
-  if ((double)lay->n_rows * (double)H * rua::ar_esize(dtype) >= 9.0e18 || (double)lay->B * (double)H >= 1.0e18)
+  if (rua::seg_too_large(lay, H, es) || (double)lay->B * (double)H >= 1.0e18)
     return RUA_ERANGE;
   hipStream_t s = (hipStream_t)stream;
-  switch (rua::ar_esize(dtype)) {
+  switch (es) {
     case 2: return rua::take_launch<uint16_t>(*lay, data, index, out, H, s);
     case 4: return rua::take_launch<uint32_t>(*lay, data, index, out, H, s);
     case 8: return rua::take_launch<uint64_t>(*lay, data, index, out, H, s);
@@ -593,14 +556,15 @@ extern "C" int rua_segment_take(const rua_layout* lay, const void* data, const i
 
 extern "C" int rua_segment_put(const rua_layout* lay, const void* src, const int64_t* index, void* out, int64_t H,
                                int32_t dtype, void* stream) {
+  const int es = rua::seg_esize(dtype, true);
   int e;
-  if ((e = rua::ar_check_rows(lay, H, dtype)) != 0) return e;
+  if ((e = rua::seg_check_entry(lay, H, es)) != 0) return e;
   if (lay->B == 0 || lay->n_rows == 0 || H == 0) return 0;
   if (!src || !index || !out || src == out) return RUA_EINVAL;
-  if ((double)lay->n_rows * (double)H * rua::ar_esize(dtype) >= 9.0e18 || (double)lay->B * (double)H >= 1.0e18)
+  if (rua::seg_too_large(lay, H, es) || (double)lay->B * (double)H >= 1.0e18)
     return RUA_ERANGE;
   hipStream_t s = (hipStream_t)stream;
-  switch (rua::ar_esize(dtype)) {
+  switch (es) {
     case 2: return rua::put_launch<uint16_t>(*lay, src, index, out, H, s);
     case 4: return rua::put_launch<uint32_t>(*lay, src, index, out, H, s);
     case 8: return rua::put_launch<uint64_t>(*lay, src, index, out, H, s);

@@ -45,13 +45,11 @@ void trace_add(const char* rec);
 // of 1 reproduces the cumsum bit for bit only while these agree with SC_* there
 constexpr int LS_GROUP = 8;                // positions scanned by doubling steps
 constexpr int LS_SLOTS = 32;               // positions of a tile = 4 groups
-constexpr int LS_BLOCK_TOK = 2048;         // positions of a block = 64 tiles
+constexpr int LS_BLOCK_TOK = SEG_BLOCK_TOK; // positions of a block = 64 tiles
 constexpr int LS_TILES = LS_BLOCK_TOK / LS_SLOTS;
 constexpr int LS_LPR = 8;                  // rows form: 16-byte lanes per row chunk (128 bytes)
 constexpr int LS_ROWS_UNR = 2;             // rows form: tiles in flight per workgroup (two accumulators per element)
 constexpr int LS_LANES_UNR = 2;            // lanes form: tiles in flight per half wave
-constexpr int64_t LS_CUT_MAX_UNITS = 1024; // the cut rule of the cumsum: fewer (sequence x chunk) units than this ...
-constexpr int64_t LS_CUT_MIN_LEN = 4 * LS_BLOCK_TOK;   // ... of sequences this long
 enum { LS_FULL = 0, LS_PARTIAL = 1, LS_FINISH = 2 };
 static_assert(LS_GROUP == 8 && LS_SLOTS == 32 && LS_BLOCK_TOK == 2048 && LS_TILES == 64,
               "the association order of rua_scan.hip: groups of 8, tiles of 32, blocks of 2 048");
@@ -398,37 +396,10 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_linear_scan_rows_kernel(rua_lay
 }
 
 // ---------------------------------------------------------------- host side
-static int ls_esize(int32_t dtype) {
-  switch (dtype) {
-    case RUA_F32: return 4;
-    case RUA_BF16: case RUA_F16: return 2;
-    case RUA_F64: return 8;
-  }
-  return 0;
-}
-
-struct ls_plan {
-  int n_chunks;       // 128-byte column chunks of a row
-  int maxblk;         // > 0: the cut form, with this many blocks per sequence
-  int64_t ws_bytes;   // what the cut form needs: one PAIR of accumulators per block and (padded) column
-};
-
-static ls_plan ls_make_plan(const rua_layout& L, int64_t H, int32_t dtype) {
-  ls_plan p = {0, 0, 0};
-  const int es = ls_esize(dtype);
-  if (!es || H <= 0 || L.B <= 0) return p;
-  const int64_t row_bytes = H * es;
-  p.n_chunks = (int)((row_bytes + 127) / 128);
-  if (row_bytes <= 16) return p;
-  const int64_t bound = sm_len_bound(L);
-  if (L.B * p.n_chunks < LS_CUT_MAX_UNITS && bound >= LS_CUT_MIN_LEN) {
-    const int64_t mb = (bound + LS_BLOCK_TOK - 1) / LS_BLOCK_TOK;
-    if (mb <= 0x7fffffff / LS_CUT_MAX_UNITS) {
-      p.maxblk = (int)mb;
-      p.ws_bytes = 2 * L.B * mb * p.n_chunks * (128 / es) * (es == 8 ? 8 : 4);
-    }
-  }
-  return p;
+// the cut form keeps one PAIR of accumulators per block and (padded) column
+static seg_plan ls_make_plan(const rua_layout& L, int64_t H, int32_t dtype) {
+  const int es = seg_esize(dtype, false);
+  return seg_make_plan(L, H, es, 2 * (es == 8 ? 8 : 4));
 }
 
 template <typename E, bool BWD>
@@ -445,11 +416,10 @@ static int ls_launch(const rua_layout& L, const void* x, const void* gate, doubl
   const bool tr = g_trace_on.load(std::memory_order_relaxed) != 0;
 
   if (row_bytes <= 16) {
-    const uint64_t mix = (uint64_t)row_bytes | bases | 16u;
-    const int W = (int)(mix & (~mix + 1));
-    const int64_t waves = (L.B + 1) / 2;
-    const int64_t grid = (waves + RUA_WAVES_PER_BLOCK - 1) / RUA_WAVES_PER_BLOCK;
-    if (grid > 0x7fffffffLL) return RUA_ERANGE;
+    const seg_lanes ln = seg_lanes_geometry(row_bytes, bases, L.B);
+    const int W = ln.W;
+    const int64_t grid = ln.grid;
+    if (!grid) return RUA_ERANGE;
     if (tr) {
       const uint64_t own = (uint64_t)row_bytes | 16u;           // AL: the bases did not narrow the row's own access width
       snprintf(rec, sizeof rec, "seg_linear_scan_lanes_kernel T=%s W=%d H=%d AL=%d rev=%d kind=%d gate=%s bwd=%d cut=0",
@@ -461,11 +431,11 @@ static int ls_launch(const rua_layout& L, const void* x, const void* gate, doubl
     return (int)hipGetLastError();
   }
 
-  const ls_plan p = ls_make_plan(L, H, dtype);
+  const seg_plan p = ls_make_plan(L, H, dtype);
   const bool al = row_bytes % 16 == 0 && bases % 16 == 0;
   const bool cut = ws != nullptr && p.maxblk > 0;
-  const int64_t grid = L.B * (int64_t)p.n_chunks * (cut ? p.maxblk : 1);
-  if (grid > 0x7fffffffLL) return RUA_ERANGE;
+  const int64_t grid = seg_rows_grid(L, p, cut);
+  if (!grid) return RUA_ERANGE;
 
 #define RUA_LS_ROWS(ALV, MODE)                                                                                         \
   hipLaunchKernelGGL((seg_linear_scan_rows_kernel<E, ALV, BWD>), dim3((unsigned)grid), dim3(RUA_BLOCK), 0, s, L,       \
@@ -499,14 +469,14 @@ static int ls_launch(const rua_layout& L, const void* x, const void* gate, doubl
 template <bool BWD>
 static int ls_dispatch(const rua_layout* lay, const void* x, const void* gate, double gs, const void* h, void* out,
                        void* gout, int64_t H, int32_t dtype, int32_t reverse, void* ws, void* stream) {
+  const int es = seg_esize(dtype, false);
   int e;
-  if ((e = sm_check_layout(lay)) != 0) return e;
-  if (H < 0 || !ls_esize(dtype)) return RUA_EINVAL;
+  if ((e = seg_check_entry(lay, H, es)) != 0) return e;
   if (lay->B == 0 || lay->n_rows == 0 || H == 0) return 0;
   if (!x || !out) return RUA_EINVAL;
   if (out == gate || (BWD && h && out == h)) return RUA_EINVAL;
   if (BWD && gout && (!h || !gate || gout == x || gout == gate || gout == h || gout == out)) return RUA_EINVAL;
-  if ((double)lay->n_rows * (double)H * ls_esize(dtype) >= 9.0e18) return RUA_ERANGE;
+  if (seg_too_large(lay, H, es)) return RUA_ERANGE;
   hipStream_t s = (hipStream_t)stream;
   // the backward runs the scan the other way
   const int rev = (reverse ? 1 : 0) ^ (BWD ? 1 : 0);

@@ -33,22 +33,16 @@ extern std::atomic<int> g_trace_on;        // the dispatch trace (rua_reduce.hip
 void trace_add(const char* rec);
 
 constexpr int NM_SLOTS = 32;               // parallel fold chains per (sequence, column)
-constexpr int NM_BLOCK_TOK = 2048;         // tokens per block = 64 per slot
+constexpr int NM_BLOCK_TOK = SEG_BLOCK_TOK; // tokens per block = 64 per slot
 constexpr int NM_LPR = 8;                  // row forms: 16-byte lanes per row chunk (128 bytes)
 constexpr int NM_ROWS_UNR = 4;             // row forms: rows in flight per thread
 constexpr int NM_LANES_UNR = 8;            // lanes form: tokens a lane keeps in registers (sequences up to 256 tokens)
 constexpr int NM_LDS_BUDGET = 64 * 1024;   // per workgroup: two workgroups per CU, no opt-in for large dynamic LDS
-constexpr int64_t NM_CUT_MAX_UNITS = 1024; // fewer (sequence x chunk) units than this leave the chip idle ...
-constexpr int64_t NM_CUT_MIN_LEN = 4 * NM_BLOCK_TOK;   // ... when the sequences are this long: cut them across workgroups
 enum { NM_FULL = 0, NM_PARTIAL = 1, NM_FINISH = 2 };
 enum { NM_STD = 0, NM_VM = 1, NM_BWD = 2 };  // standardize forward, var_mean (its first walk alone), standardize backward
 
 __device__ __forceinline__ float nm_sqrt(float v) { return sqrtf(v); }
 __device__ __forceinline__ double nm_sqrt(double v) { return sqrt(v); }
-template <typename A> __device__ __forceinline__ A nm_nan();
-template <> __device__ __forceinline__ float nm_nan<float>() { return __builtin_nanf(""); }
-template <> __device__ __forceinline__ double nm_nan<double>() { return __builtin_nan(""); }
-template <typename A> __device__ __forceinline__ A nm_shfl_xor(A v, int mask) { return __shfl_xor(v, mask, RUA_WAVE); }
 
 // ---------------------------------------------------------------- the fold
 // Welford, rk = 1 / (tokens of the chain so far, this one included).  A NaN poisons (mean, M2); an infinity makes the
@@ -103,8 +97,8 @@ template <typename A> __device__ __forceinline__ void nm_stats(A n, A m2, A corr
     var = m2 / dof;
     rstd = (A)1 / nm_sqrt(var + eps);
   } else {
-    var = nm_nan<A>();
-    rstd = nm_nan<A>();
+    var = seg_nan<A>();
+    rstd = seg_nan<A>();
   }
 }
 
@@ -117,8 +111,8 @@ template <int OP, typename A> __device__ __forceinline__ A nm_finish(A v, A g, A
 // the per-(sequence, column) factors of the backward from its two sums
 template <typename A> __device__ __forceinline__ void nm_bwd_factors(A n, A corr, A& s1, A& s2) {
   const A dof = n - corr;
-  s1 = n > (A)0 ? s1 / n : nm_nan<A>();
-  s2 = dof > (A)0 ? s2 / dof : nm_nan<A>();
+  s1 = n > (A)0 ? s1 / n : seg_nan<A>();
+  s2 = dof > (A)0 ? s2 / dof : seg_nan<A>();
 }
 
 // ---------------------------------------------------------------- lanes along time: rows of one vector (<= 16 bytes)
@@ -195,12 +189,12 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_norm_lanes_kernel(rua_layout L,
     for (int k = 1; k < NM_SLOTS; k <<= 1) {
       A p2[VE], s2[VE];
 #pragma unroll
-      for (int e = 0; e < VE; ++e) { p2[e] = nm_shfl_xor(p[e], k); s2[e] = nm_shfl_xor(s[e], k); }
+      for (int e = 0; e < VE; ++e) { p2[e] = seg_shfl_xor(p[e], k); s2[e] = seg_shfl_xor(s[e], k); }
       if constexpr (BWD) {
 #pragma unroll
         for (int e = 0; e < VE; ++e) { p[e] = p[e] + p2[e]; s[e] = s[e] + s2[e]; }
       } else {
-        const A n2 = nm_shfl_xor(n, k);
+        const A n2 = seg_shfl_xor(n, k);
         nm_join<A, VE>((q & k) == 0, n, p, s, n2, p2, s2);
       }
     }
@@ -231,7 +225,7 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_norm_lanes_kernel(rua_layout L,
       nm_stats(N, S[e], corr, eps, var, R[e]);
       if (q != 0) continue;
       if constexpr (OP == NM_VM) {
-        const A mean = N > (A)0 ? P[e] : nm_nan<A>();
+        const A mean = N > (A)0 ? P[e] : seg_nan<A>();
         if (o1) ((raw*)o1)[b * H + e] = E::down(var);
         if (o2) { if (mean_acc) ((A*)o2)[b * H + e] = mean; else ((raw*)o2)[b * H + e] = E::down(mean); }
       } else {
@@ -416,12 +410,12 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_norm_rows_kernel(rua_layout L, 
       for (int k = NM_LPR; k < RUA_WAVE; k <<= 1) {
         A p2[VE], s2[VE];
 #pragma unroll
-        for (int e = 0; e < VE; ++e) { p2[e] = nm_shfl_xor(p[e], k); s2[e] = nm_shfl_xor(s[e], k); }
+        for (int e = 0; e < VE; ++e) { p2[e] = seg_shfl_xor(p[e], k); s2[e] = seg_shfl_xor(s[e], k); }
         if constexpr (BWD) {
 #pragma unroll
           for (int e = 0; e < VE; ++e) { p[e] = p[e] + p2[e]; s[e] = s[e] + s2[e]; }
         } else {
-          const A n2 = nm_shfl_xor(n, k);
+          const A n2 = seg_shfl_xor(n, k);
           nm_join<A, VE>((lane & k) == 0, n, p, s, n2, p2, s2);
         }
       }
@@ -494,7 +488,7 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_norm_rows_kernel(rua_layout L, 
       if (!writer || e >= nval) continue;
       const int64_t at = b * H + col0 + e;
       if constexpr (OP == NM_VM) {
-        const A mean = N > (A)0 ? P[e] : nm_nan<A>();
+        const A mean = N > (A)0 ? P[e] : seg_nan<A>();
         if (o1) ((raw*)o1)[at] = E::down(var);
         if (o2) { if (mean_acc) ((A*)o2)[at] = mean; else ((raw*)o2)[at] = E::down(mean); }
       } else {
@@ -575,7 +569,7 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_var_mean_backward_kernel(rua_la
     A v = (A)0;
     if (gvar) {
       const A mu = mean_acc ? ((const A*)mean)[at] : E::up(((const typename E::raw*)mean)[at]);
-      v = dof > (A)0 ? E::up(gvar[at]) * ((A)2 * (E::up(x[row * H + h]) - mu)) / dof : nm_nan<A>();
+      v = dof > (A)0 ? E::up(gvar[at]) * ((A)2 * (E::up(x[row * H + h]) - mu)) / dof : seg_nan<A>();
     }
     if (gmean) v = v + E::up(gmean[at]) / n;
     out[row * H + h] = E::down(v);
@@ -592,37 +586,10 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_var_mean_backward_kernel(rua_la
 }
 
 // ---------------------------------------------------------------- host side
-static int nm_esize(int32_t dtype) {
-  switch (dtype) {
-    case RUA_F32: return 4;
-    case RUA_BF16: case RUA_F16: return 2;
-    case RUA_F64: return 8;
-  }
-  return 0;
-}
-
-struct nm_plan {
-  int n_chunks;       // 128-byte column chunks of a row
-  int maxblk;         // > 0: the cut form, with this many blocks per sequence
-  int64_t ws_bytes;   // what the cut form needs: two accumulator values per block and padded column
-};
-
-static nm_plan nm_make_plan(const rua_layout& L, int64_t H, int32_t dtype) {
-  nm_plan p = {0, 0, 0};
-  const int es = nm_esize(dtype);
-  if (!es || H <= 0 || L.B <= 0) return p;
-  const int64_t row_bytes = H * es;
-  p.n_chunks = (int)((row_bytes + 127) / 128);
-  if (row_bytes <= 16) return p;
-  const int64_t bound = sm_len_bound(L);
-  if (L.B * p.n_chunks < NM_CUT_MAX_UNITS && bound >= NM_CUT_MIN_LEN) {
-    const int64_t mb = (bound + NM_BLOCK_TOK - 1) / NM_BLOCK_TOK;
-    if (mb <= 0x7fffffff / NM_CUT_MAX_UNITS) {
-      p.maxblk = (int)mb;
-      p.ws_bytes = L.B * mb * p.n_chunks * 128 / es * 2 * (es == 8 ? 8 : 4);
-    }
-  }
-  return p;
+// the cut form keeps (mean, M2), or the backward's two sums, per block and padded column: two accumulators
+static seg_plan nm_make_plan(const rua_layout& L, int64_t H, int32_t dtype) {
+  const int es = seg_esize(dtype, false);
+  return seg_make_plan(L, H, es, 2 * (es == 8 ? 8 : 4));
 }
 
 static const char* nm_opname(int op) { return op == NM_VM ? "var_mean" : "standardize"; }
@@ -645,11 +612,10 @@ static int nm_launch(const rua_layout& L, const void* x, const void* g, void* ou
     return RUA_EALIGN;
 
   if (row_bytes <= 16) {
-    const uint64_t mix = (uint64_t)row_bytes | bases | 16u;
-    const int W = (int)(mix & (~mix + 1));
-    const int64_t waves = (L.B + 1) / 2;
-    const int64_t grid = (waves + RUA_WAVES_PER_BLOCK - 1) / RUA_WAVES_PER_BLOCK;
-    if (grid > 0x7fffffffLL) return RUA_ERANGE;
+    const seg_lanes ln = seg_lanes_geometry(row_bytes, bases, L.B);
+    const int W = ln.W;
+    const int64_t grid = ln.grid;
+    if (!grid) return RUA_ERANGE;
     if (g_trace_on.load(std::memory_order_relaxed)) {
       snprintf(rec, sizeof rec, "seg_norm%s_lanes_kernel T=%s AL=%d W=%d H=%d kind=%d cut=0 op=%s", dir, E::name(),
                (int)(W == 16), W, (int)H, L.kind, nm_opname(OP));
@@ -660,7 +626,7 @@ static int nm_launch(const rua_layout& L, const void* x, const void* g, void* ou
     return (int)hipGetLastError();
   }
 
-  const nm_plan p = nm_make_plan(L, H, dtype);
+  const seg_plan p = nm_make_plan(L, H, dtype);
   const bool al = row_bytes % 16 == 0 && bases % 16 == 0;
   const bool cut = ws != nullptr && p.maxblk > 0;
   constexpr int XCH_BYTES = (RUA_WAVES_PER_BLOCK * NM_LPR * (2 * VE + 1) * (int)sizeof(A) + 15) / 16 * 16;
@@ -677,8 +643,8 @@ static int nm_launch(const rua_layout& L, const void* x, const void* g, void* ou
     cap = (int)(need < CAP ? need : CAP);
   }
   const size_t lds = XCH_BYTES + (size_t)cap * 128 * (BWD ? 2 : 1);
-  const int64_t grid = L.B * (int64_t)p.n_chunks * (cut ? p.maxblk : 1);
-  if (grid > 0x7fffffffLL) return RUA_ERANGE;
+  const int64_t grid = seg_rows_grid(L, p, cut);
+  if (!grid) return RUA_ERANGE;
 
 #define RUA_NM_ROWS(ALV, MODE, GRIDBLK)                                                                                \
   hipLaunchKernelGGL((seg_norm_rows_kernel<E, OP, ALV>), dim3((unsigned)(L.B * (int64_t)p.n_chunks * (GRIDBLK))),      \
@@ -738,12 +704,11 @@ static int nm_launch_vm_backward(const rua_layout& L, const void* x, const void*
 
 // the checks every entry shares; `dtype` loses its RUA_NORM_MEAN_ACC bit
 static int nm_check(const rua_layout* lay, int64_t H, int32_t& dtype, int64_t correction, double eps, int& mean_acc) {
-  int e;
   mean_acc = (dtype >= 0 && (dtype & RUA_NORM_MEAN_ACC)) ? 1 : 0;
   if (dtype >= 0) dtype &= ~RUA_NORM_MEAN_ACC;
-  if ((e = sm_check_layout(lay)) != 0) return e;
-  if (H < 0 || !nm_esize(dtype) || correction < 0 || !(eps >= 0.0)) return RUA_EINVAL;
-  return 0;
+  const int e = seg_check_entry(lay, H, seg_esize(dtype, false));
+  if (e != 0) return e;
+  return correction < 0 || !(eps >= 0.0) ? RUA_EINVAL : 0;
 }
 
 template <int OP>
@@ -751,7 +716,7 @@ static int nm_dispatch(const rua_layout* lay, const void* x, const void* g, void
                        int32_t dtype, int64_t correction, double eps, int mean_acc, void* ws, void* stream) {
   if (lay->B == 0 || lay->n_rows == 0 || H == 0) return 0;
   if (!x || (OP != NM_VM && !out) || (OP == NM_BWD && (!g || !o1))) return RUA_EINVAL;
-  if ((double)lay->n_rows * (double)H * nm_esize(dtype) >= 9.0e18) return RUA_ERANGE;
+  if (seg_too_large(lay, H, seg_esize(dtype, false))) return RUA_ERANGE;
   hipStream_t s = (hipStream_t)stream;
   switch (dtype) {
     case RUA_F32:  return nm_launch<sm_f32, OP>(*lay, x, g, out, o1, o2, H, dtype, correction, eps, mean_acc, ws, s);
@@ -789,7 +754,7 @@ extern "C" int rua_segment_var_mean_backward(const rua_layout* lay, const void* 
   if (grad_in && (grad_in == mean || grad_in == grad_var || grad_in == grad_mean)) return RUA_EINVAL;
   if (lay->B == 0 || lay->n_rows == 0 || H == 0) return 0;
   if (!data || !mean || !grad_in) return RUA_EINVAL;
-  if ((double)lay->n_rows * (double)H * nm_esize(dtype) >= 9.0e18) return RUA_ERANGE;
+  if (seg_too_large(lay, H, seg_esize(dtype, false))) return RUA_ERANGE;
   hipStream_t s = (hipStream_t)stream;
   switch (dtype) {
     case RUA_F32:  return nm_launch_vm_backward<sm_f32>(*lay, data, mean, macc, grad_var, grad_mean, grad_in, H, correction, s);

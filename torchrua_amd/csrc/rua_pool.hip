@@ -37,40 +37,28 @@ extern std::atomic<int> g_trace_on;        // the dispatch trace (rua_reduce.hip
 void trace_add(const char* rec);
 
 constexpr int PL_SLOTS = 32;               // parallel fold chains per (sequence, column)
-constexpr int PL_BLOCK_TOK = 2048;         // tokens per block = 64 per slot
+constexpr int PL_BLOCK_TOK = SEG_BLOCK_TOK; // tokens per block = 64 per slot
 constexpr int PL_LPR = 8;                  // rows form: 16-byte lanes per row chunk (128 bytes)
 constexpr int PL_ROWS_UNR = 4;             // rows form: rows in flight per thread
 constexpr int PL_LANES_UNR = 4;            // lanes form: tokens in flight per lane
-
-__device__ __forceinline__ float pl_exp(float v) { return expf(v); }
-__device__ __forceinline__ double pl_exp(double v) { return exp(v); }
-__device__ __forceinline__ float pl_log(float v) { return logf(v); }
-__device__ __forceinline__ double pl_log(double v) { return log(v); }
-template <typename A> __device__ __forceinline__ A pl_inf();
-template <> __device__ __forceinline__ float pl_inf<float>() { return __builtin_inff(); }
-template <> __device__ __forceinline__ double pl_inf<double>() { return __builtin_inf(); }
-template <typename A> __device__ __forceinline__ A pl_nan();
-template <> __device__ __forceinline__ float pl_nan<float>() { return __builtin_nanf(""); }
-template <> __device__ __forceinline__ double pl_nan<double>() { return __builtin_nan(""); }
-template <typename A> __device__ __forceinline__ A pl_shfl_xor(A v, int mask) { return __shfl_xor(v, mask, RUA_WAVE); }
 
 // ---------------------------------------------------------------- the fold
 // online (max, sum) with one exp per score; the caller then updates acc = acc * scale + p * v.  NaN and +inf poison the
 // sum (the whole score column of the sequence is NaN); a -inf score has weight 0 — and 0 * v still poisons acc where v is
 // not finite, as torch's softmax * values does.
 template <typename A> __device__ __forceinline__ void pl_fold(A& m, A& l, A x, A& scale, A& p) {
-  const A inf = pl_inf<A>();
+  const A inf = seg_inf<A>();
   scale = (A)1;
   p = (A)0;
   if (!(x < inf)) {
-    l = pl_nan<A>();
+    l = seg_nan<A>();
   } else if (x > m) {
-    scale = pl_exp(m - x);
+    scale = seg_exp(m - x);
     l = l * scale + (A)1;
     p = (A)1;
     m = x;
   } else if (x > -inf) {
-    p = pl_exp(x - m);
+    p = seg_exp(x - m);
     l = l + p;
   }
 }
@@ -78,12 +66,12 @@ template <typename A> __device__ __forceinline__ void pl_fold(A& m, A& l, A x, A
 // the factors that bring two states to their common max: symmetric (pl_factors(m2, m, M, fb, fa) gives the same bits)
 template <typename A> __device__ __forceinline__ void pl_factors(A m, A m2, A& M, A& fa, A& fb) {
   M = m > m2 ? m : m2;
-  if (M == -pl_inf<A>()) {
+  if (M == -seg_inf<A>()) {
     fa = (A)1;
     fb = (A)1;
   } else {
-    fa = pl_exp(m - M);
-    fb = pl_exp(m2 - M);
+    fa = seg_exp(m - M);
+    fb = seg_exp(m2 - M);
   }
 }
 
@@ -119,12 +107,12 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_pool_lanes_kernel(rua_layout L,
   struct alignas(16) Row { raw e[VE]; };
   A M[VE], S[VE], ACC[VE];
 #pragma unroll
-  for (int e = 0; e < VE; ++e) { M[e] = -pl_inf<A>(); S[e] = (A)0; ACC[e] = (A)0; }
+  for (int e = 0; e < VE; ++e) { M[e] = -seg_inf<A>(); S[e] = (A)0; ACC[e] = (A)0; }
 
   for (int64_t t0 = 0; t0 < maxlen; t0 += PL_BLOCK_TOK) {
     A m[VE], s[VE], acc[VE];
 #pragma unroll
-    for (int e = 0; e < VE; ++e) { m[e] = -pl_inf<A>(); s[e] = (A)0; acc[e] = (A)0; }
+    for (int e = 0; e < VE; ++e) { m[e] = -seg_inf<A>(); s[e] = (A)0; acc[e] = (A)0; }
     const int64_t t1 = len < t0 + PL_BLOCK_TOK ? len : t0 + PL_BLOCK_TOK;
     const int64_t t1w = maxlen < t0 + PL_BLOCK_TOK ? maxlen : t0 + PL_BLOCK_TOK;
     for (int64_t tt = t0; tt < t1w; tt += (int64_t)PL_SLOTS * UNR) {
@@ -169,9 +157,9 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_pool_lanes_kernel(rua_layout L,
 #pragma unroll
       for (int e = 0; e < VE; ++e) {
         if (e >= H) continue;
-        const A a2 = pl_shfl_xor(acc[e], k);
+        const A a2 = seg_shfl_xor(acc[e], k);
         if (first[e]) {
-          const A m2 = pl_shfl_xor(m[e], k), s2 = pl_shfl_xor(s[e], k);
+          const A m2 = seg_shfl_xor(m[e], k), s2 = seg_shfl_xor(s[e], k);
           pl_factors(m[e], m2, Mx, fa, fb);
           s[e] = s[e] * fa + s2 * fb;
           m[e] = Mx;
@@ -205,7 +193,7 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_pool_lanes_kernel(rua_layout L,
     if (e >= H) continue;
     const A o = len > 0 ? ACC[e] / S[e] : (A)0;
     if (out_acc) ((A*)out)[b * H + e] = o; else ((raw*)out)[b * H + e] = E::down(o);
-    if (lse && first[e]) lse[b * G + gc[e]] = M[e] + pl_log(S[e]);
+    if (lse && first[e]) lse[b * G + gc[e]] = M[e] + seg_log(S[e]);
   }
 }
 
@@ -259,14 +247,14 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_pool_rows_kernel(rua_layout L, 
 
   A M[NS], S[NS], ACC[VE];
 #pragma unroll
-  for (int i = 0; i < NS; ++i) { M[i] = -pl_inf<A>(); S[i] = (A)0; }
+  for (int i = 0; i < NS; ++i) { M[i] = -seg_inf<A>(); S[i] = (A)0; }
 #pragma unroll
   for (int e = 0; e < VE; ++e) ACC[e] = (A)0;
 
   for (int64_t t0 = 0; t0 < len; t0 += PL_BLOCK_TOK) {
     A m[NS], s[NS], acc[VE];
 #pragma unroll
-    for (int i = 0; i < NS; ++i) { m[i] = -pl_inf<A>(); s[i] = (A)0; }
+    for (int i = 0; i < NS; ++i) { m[i] = -seg_inf<A>(); s[i] = (A)0; }
 #pragma unroll
     for (int e = 0; e < VE; ++e) acc[e] = (A)0;
     const int64_t t1 = len < t0 + PL_BLOCK_TOK ? len : t0 + PL_BLOCK_TOK;
@@ -342,9 +330,9 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_pool_rows_kernel(rua_layout L, 
     for (int k = PL_LPR; k < RUA_WAVE; k <<= 1) {
       A m2[NS], s2[NS], a2[VE];
 #pragma unroll
-      for (int i = 0; i < NS; ++i) { m2[i] = pl_shfl_xor(m[i], k); s2[i] = pl_shfl_xor(s[i], k); }
+      for (int i = 0; i < NS; ++i) { m2[i] = seg_shfl_xor(m[i], k); s2[i] = seg_shfl_xor(s[i], k); }
 #pragma unroll
-      for (int e = 0; e < VE; ++e) a2[e] = pl_shfl_xor(acc[e], k);
+      for (int e = 0; e < VE; ++e) a2[e] = seg_shfl_xor(acc[e], k);
       join(m, s, acc, [&](int i) { return m2[i]; }, [&](int i) { return s2[i]; }, [&](int e) { return a2[e]; });
     }
     // xor 8, 16 of the slot number = xor 1, 2 of the wave number, through LDS
@@ -400,7 +388,7 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_pool_rows_kernel(rua_layout L, 
   if (lse) {
 #pragma unroll
     for (int i = 0; i < NS; ++i)
-      if (i < nval && (col0 + i) % D == 0) lse[b * G + gc[i]] = M[i] + pl_log(S[i]);
+      if (i < nval && (col0 + i) % D == 0) lse[b * G + gc[i]] = M[i] + seg_log(S[i]);
   }
 }
 
@@ -455,7 +443,7 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_pool_backward_lanes_kernel(
     for (int e = 0; e < VE; ++e) {
       o.e[e] = E::down((A)0);
       if (e >= H) continue;
-      if (first[e]) p = pl_exp(E::up(sin[row * G + gc[e]]) - ls[e]);
+      if (first[e]) p = seg_exp(E::up(sin[row * G + gc[e]]) - ls[e]);
       const A pr = E::up(v.e[e]) * g[e];
       cur = first[e] ? pr : cur + pr;
       o.e[e] = E::down(p * g[e]);
@@ -538,7 +526,7 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_pool_backward_kernel(
           delta = delta + (out_acc ? oua[k * UE + e] : E::up(oo.e[e])) * E::up(gg.e[e]);
       }
     }
-    for (int k = 1; k < S; k <<= 1) delta = delta + pl_shfl_xor(delta, k);
+    for (int k = 1; k < S; k <<= 1) delta = delta + seg_shfl_xor(delta, k);
     const A ls = valid ? lse[b * G + g] : (A)0;
 
     for (int64_t t = w; t < len; t += RUA_WAVES_PER_BLOCK) { // wave-uniform
@@ -546,7 +534,7 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_pool_backward_kernel(
       if (row < 0 || row >= L.n_rows) continue;               // wave-uniform
       A p = (A)0, dot = (A)0;
       if (valid) {
-        p = pl_exp(E::up(sin[row * G + g]) - ls);
+        p = seg_exp(E::up(sin[row * G + g]) - ls);
         const raw* vb = vin + row * H + g * D;
         raw* gvb = gv ? gv + row * H + g * D : nullptr;
         int i = 0;
@@ -563,7 +551,7 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_pool_backward_kernel(
           if (gvb) stu(gvb + k * UE, oo);
         }
       }
-      for (int k = 1; k < S; k <<= 1) dot = dot + pl_shfl_xor(dot, k);
+      for (int k = 1; k < S; k <<= 1) dot = dot + seg_shfl_xor(dot, k);
       if (valid && slot == 0 && gs) gs[row * G + g] = E::down(p * (dot - delta));
     }
   }
@@ -580,15 +568,6 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_pool_backward_kernel(
 }
 
 // ---------------------------------------------------------------- host side
-static int pl_esize(int32_t dtype) {
-  switch (dtype) {
-    case RUA_F32: return 4;
-    case RUA_BF16: case RUA_F16: return 2;
-    case RUA_F64: return 8;
-  }
-  return 0;
-}
-
 static bool pl_trace() { return g_trace_on.load(std::memory_order_relaxed) != 0; }
 
 template <typename E>
@@ -606,11 +585,10 @@ static int pl_forward(const rua_layout& L, const void* v, const void* sc, void* 
   char rec[200];
 
   if (row_bytes <= 16) {
-    const uint64_t mix = (uint64_t)row_bytes | (uint64_t)(uintptr_t)v | 16u;
-    const int W = (int)(mix & (~mix + 1));
-    const int64_t waves = (L.B + 1) / 2;
-    const int64_t grid = (waves + RUA_WAVES_PER_BLOCK - 1) / RUA_WAVES_PER_BLOCK;
-    if (grid > 0x7fffffffLL) return RUA_ERANGE;
+    const seg_lanes ln = seg_lanes_geometry(row_bytes, (uint64_t)(uintptr_t)v, L.B);
+    const int W = ln.W;
+    const int64_t grid = ln.grid;
+    if (!grid) return RUA_ERANGE;
     if (pl_trace()) {
       snprintf(rec, sizeof rec, "seg_pool_lanes_kernel T=%s AL=%d W=%d H=%d D=%d kind=%d", E::name(), (int)(W == 16), W,
                (int)H, (int)D, L.kind);
@@ -656,11 +634,10 @@ static int pl_backward(const rua_layout& L, const void* go, const void* v, const
   char rec[200];
 
   if (row_bytes <= 16) {
-    const uint64_t mix = (uint64_t)row_bytes | wide | 16u;
-    const int W = (int)(mix & (~mix + 1));
-    const int64_t waves = (L.B + 1) / 2;
-    const int64_t grid = (waves + RUA_WAVES_PER_BLOCK - 1) / RUA_WAVES_PER_BLOCK;
-    if (grid > 0x7fffffffLL) return RUA_ERANGE;
+    const seg_lanes ln = seg_lanes_geometry(row_bytes, wide, L.B);
+    const int W = ln.W;
+    const int64_t grid = ln.grid;
+    if (!grid) return RUA_ERANGE;
     if (pl_trace()) {
       snprintf(rec, sizeof rec, "seg_pool_backward_kernel T=%s AL=%d form=lanes W=%d H=%d D=%d kind=%d", E::name(),
                (int)(W == 16), W, (int)H, (int)D, L.kind);
@@ -696,12 +673,11 @@ static int pl_backward(const rua_layout& L, const void* go, const void* v, const
 
 // the checks both directions share; > 0: nothing to do
 static int pl_check(const rua_layout* lay, int64_t H, int64_t D, int32_t& dtype, int& oacc) {
-  int e;
   oacc = (dtype & RUA_POOL_OUT_ACC) ? 1 : 0;
   if (dtype >= 0) dtype &= ~RUA_POOL_OUT_ACC;
-  if ((e = sm_check_layout(lay)) != 0) return e;
-  if (!pl_esize(dtype) || H < 0 || D <= 0 || H % D) return RUA_EINVAL;
-  return 0;
+  const int e = seg_check_entry(lay, H, seg_esize(dtype, false));
+  if (e != 0) return e;
+  return D <= 0 || H % D ? RUA_EINVAL : 0;
 }
 
 }  // namespace rua
@@ -721,7 +697,7 @@ extern "C" int rua_segment_softmax_pool(const rua_layout* lay, const void* value
   if (lse && (lse == values || lse == scores)) return RUA_EINVAL;
   if (lay->B == 0 || lay->n_rows == 0 || H == 0) return 0;
   if (!values || !scores || !out) return RUA_EINVAL;
-  if ((double)lay->n_rows * (double)H * pl_esize(dtype) >= 9.0e18) return RUA_ERANGE;
+  if (seg_too_large(lay, H, seg_esize(dtype, false))) return RUA_ERANGE;
   hipStream_t s = (hipStream_t)stream;
   switch (dtype) {
     case RUA_F32:  return pl_forward<sm_f32>(*lay, values, scores, out, oacc, lse, H, D, s);
@@ -747,7 +723,7 @@ extern "C" int rua_segment_softmax_pool_backward(const rua_layout* lay, const vo
   if (lay->B == 0 || lay->n_rows == 0 || H == 0) return 0;
   if (!grad_values && !grad_scores) return 0;
   if (!grad_out || !values || !scores || !out || !lse) return RUA_EINVAL;
-  if ((double)lay->n_rows * (double)H * pl_esize(dtype) >= 9.0e18) return RUA_ERANGE;
+  if (seg_too_large(lay, H, seg_esize(dtype, false))) return RUA_ERANGE;
   hipStream_t s = (hipStream_t)stream;
   switch (dtype) {
     case RUA_F32:  return pl_backward<sm_f32>(*lay, grad_out, values, scores, out, oacc, lse, grad_values, grad_scores, H, D, s);

@@ -41,13 +41,11 @@ void trace_add(const char* rec);
 
 constexpr int SC_GROUP = 8;                // positions scanned by doubling steps
 constexpr int SC_SLOTS = 32;               // positions of a tile = 4 groups
-constexpr int SC_BLOCK_TOK = 2048;         // positions of a block = 64 tiles
+constexpr int SC_BLOCK_TOK = SEG_BLOCK_TOK; // positions of a block = 64 tiles
 constexpr int SC_TILES = SC_BLOCK_TOK / SC_SLOTS;
 constexpr int SC_LPR = 8;                  // rows form: 16-byte lanes per row chunk (128 bytes)
 constexpr int SC_ROWS_UNR = 4;             // rows form: tiles in flight per workgroup (one barrier for the four)
 constexpr int SC_LANES_UNR = 4;            // lanes form: tiles in flight per half wave
-constexpr int64_t SC_CUT_MAX_UNITS = 1024; // fewer (sequence x chunk) units than this leave the chip idle ...
-constexpr int64_t SC_CUT_MIN_LEN = 4 * SC_BLOCK_TOK;   // ... when the sequences are this long: cut them across workgroups
 enum { SC_FULL = 0, SC_PARTIAL = 1, SC_FINISH = 2 };
 static_assert(SC_SLOTS == 4 * SC_GROUP && SC_SLOTS * SC_LPR == RUA_BLOCK && SC_GROUP * SC_LPR == RUA_WAVE,
               "a group is a wave of the rows form, a tile is its workgroup");
@@ -325,37 +323,10 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_cumsum_rows_kernel(rua_layout L
 }
 
 // ---------------------------------------------------------------- host side
-static int sc_esize(int32_t dtype) {
-  switch (dtype) {
-    case RUA_F32: return 4;
-    case RUA_BF16: case RUA_F16: return 2;
-    case RUA_F64: case RUA_I64: return 8;
-  }
-  return 0;
-}
-
-struct sc_plan {
-  int n_chunks;       // 128-byte column chunks of a row
-  int maxblk;         // > 0: the cut form, with this many blocks per sequence
-  int64_t ws_bytes;   // what the cut form needs: one accumulator per block and (padded) column
-};
-
-static sc_plan sc_make_plan(const rua_layout& L, int64_t H, int32_t dtype) {
-  sc_plan p = {0, 0, 0};
-  const int es = sc_esize(dtype);
-  if (!es || H <= 0 || L.B <= 0) return p;
-  const int64_t row_bytes = H * es;
-  p.n_chunks = (int)((row_bytes + 127) / 128);
-  if (row_bytes <= 16) return p;
-  const int64_t bound = sm_len_bound(L);
-  if (L.B * p.n_chunks < SC_CUT_MAX_UNITS && bound >= SC_CUT_MIN_LEN) {
-    const int64_t mb = (bound + SC_BLOCK_TOK - 1) / SC_BLOCK_TOK;
-    if (mb <= 0x7fffffff / SC_CUT_MAX_UNITS) {
-      p.maxblk = (int)mb;
-      p.ws_bytes = L.B * mb * p.n_chunks * (128 / es) * (es == 8 ? 8 : 4);
-    }
-  }
-  return p;
+// the cut form keeps a block's total per (padded) column: one accumulator
+static seg_plan sc_make_plan(const rua_layout& L, int64_t H, int32_t dtype) {
+  const int es = seg_esize(dtype, true);
+  return seg_make_plan(L, H, es, es == 8 ? 8 : 4);
 }
 
 template <typename E>
@@ -369,11 +340,10 @@ static int sc_launch(const rua_layout& L, const void* x, void* out, int64_t H, i
   if (bases % sizeof(raw)) return RUA_EALIGN;                 // (elements themselves are always aligned)
 
   if (row_bytes <= 16) {
-    const uint64_t mix = (uint64_t)row_bytes | bases | 16u;
-    const int W = (int)(mix & (~mix + 1));
-    const int64_t waves = (L.B + 1) / 2;
-    const int64_t grid = (waves + RUA_WAVES_PER_BLOCK - 1) / RUA_WAVES_PER_BLOCK;
-    if (grid > 0x7fffffffLL) return RUA_ERANGE;
+    const seg_lanes ln = seg_lanes_geometry(row_bytes, bases, L.B);
+    const int W = ln.W;
+    const int64_t grid = ln.grid;
+    if (!grid) return RUA_ERANGE;
     if (g_trace_on.load(std::memory_order_relaxed)) {
       const uint64_t own = (uint64_t)row_bytes | 16u;           // AL: the bases did not narrow the row's own access width
       snprintf(rec, sizeof rec, "seg_cumsum_lanes_kernel T=%s W=%d H=%d AL=%d rev=%d kind=%d", E::name(), W, (int)H,
@@ -385,11 +355,11 @@ static int sc_launch(const rua_layout& L, const void* x, void* out, int64_t H, i
     return (int)hipGetLastError();
   }
 
-  const sc_plan p = sc_make_plan(L, H, dtype);
+  const seg_plan p = sc_make_plan(L, H, dtype);
   const bool al = row_bytes % 16 == 0 && bases % 16 == 0;
   const bool cut = ws != nullptr && p.maxblk > 0;
-  const int64_t grid = L.B * (int64_t)p.n_chunks * (cut ? p.maxblk : 1);
-  if (grid > 0x7fffffffLL) return RUA_ERANGE;
+  const int64_t grid = seg_rows_grid(L, p, cut);
+  if (!grid) return RUA_ERANGE;
 
 #define RUA_SC_ROWS(ALV, MODE)                                                                                         \
   hipLaunchKernelGGL((seg_cumsum_rows_kernel<E, ALV>), dim3((unsigned)grid), dim3(RUA_BLOCK), 0, s, L, (const raw*)x,   \
@@ -422,12 +392,12 @@ static int sc_launch(const rua_layout& L, const void* x, void* out, int64_t H, i
 
 static int sc_dispatch(const rua_layout* lay, const void* x, void* out, int64_t H, int32_t dtype, int32_t reverse,
                        void* ws, void* stream) {
+  const int es = seg_esize(dtype, true);
   int e;
-  if ((e = sm_check_layout(lay)) != 0) return e;
-  if (H < 0 || !sc_esize(dtype)) return RUA_EINVAL;
+  if ((e = seg_check_entry(lay, H, es)) != 0) return e;
   if (lay->B == 0 || lay->n_rows == 0 || H == 0) return 0;
   if (!x || !out) return RUA_EINVAL;
-  if ((double)lay->n_rows * (double)H * sc_esize(dtype) >= 9.0e18) return RUA_ERANGE;
+  if (seg_too_large(lay, H, es)) return RUA_ERANGE;
   hipStream_t s = (hipStream_t)stream;
   const int rev = reverse ? 1 : 0;
   switch (dtype) {

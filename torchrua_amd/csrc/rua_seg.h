@@ -1,9 +1,14 @@
-// rua_seg.h — what the per-sequence operators (rua_softmax.hip, rua_scan.hip) share: the element types, the clamped
-// sequence length, the padding test, narrow-row accesses and the host-side layout checks.
+// rua_seg.h — what the kernels of the per-sequence operators (rua_softmax.hip, rua_scan.hip, rua_argreduce.hip,
+// rua_linear_scan.hip, rua_pool.hip, rua_norm.hip) share: the element types, the clamped sequence length, the padding
+// test, narrow-row accesses and the exp / log / inf / nan / shuffle one-liners.  Their host side — checks, cut plan,
+// lanes geometry — is rua_seg_plan.h.
 #pragma once
 #include "rua_dev.h"
+#include "rua_seg_plan.h"
 
 namespace rua {
+
+static_assert(SEG_WAVES_PER_BLOCK == RUA_WAVES_PER_BLOCK, "the lanes geometry of rua_seg_plan.h counts waves per workgroup");
 
 // ---------------------------------------------------------------- element types
 struct sm_f32 {
@@ -93,27 +98,17 @@ __device__ __forceinline__ void st_row_w(char* p, int nb, int W, const void* src
   for (int i = 0; i < 8; ++i) if (i * 2 < nb) ((uint16_t*)p)[i] = ((const uint16_t*)src)[i];
 }
 
-// ---------------------------------------------------------------- host side
-static int sm_check_layout(const rua_layout* L) {
-  if (!L || L->B < 0 || L->n_rows < 0) return RUA_EINVAL;
-  switch (L->kind) {
-    case RUA_CAT:   return (L->lens && !L->off) ? RUA_EINVAL : 0;
-    case RUA_LEFT:
-    case RUA_RIGHT: return (L->T_phys >= 0 && L->n_rows <= L->B * L->T_phys) ? 0 : RUA_EINVAL;
-    case RUA_PACK:  return (L->T < 0 || (L->T > 0 && !L->boff)) ? RUA_EINVAL : 0;
-  }
-  return RUA_EINVAL;
-}
-
-// an upper bound of the longest sequence that needs no look at the device
-static int64_t sm_len_bound(const rua_layout& L) {
-  switch (L.kind) {
-    case RUA_CAT:   return L.T_log > 0 && L.T_log < L.n_rows ? L.T_log : L.n_rows;
-    case RUA_LEFT:
-    case RUA_RIGHT: return L.T_phys;
-    case RUA_PACK:  return L.T;
-  }
-  return 0;
-}
+// ---------------------------------------------------------------- one-liners over the accumulator type
+__device__ __forceinline__ float seg_exp(float v) { return expf(v); }
+__device__ __forceinline__ double seg_exp(double v) { return exp(v); }
+__device__ __forceinline__ float seg_log(float v) { return logf(v); }
+__device__ __forceinline__ double seg_log(double v) { return log(v); }
+template <typename A> __device__ __forceinline__ A seg_inf();
+template <> __device__ __forceinline__ float seg_inf<float>() { return __builtin_inff(); }
+template <> __device__ __forceinline__ double seg_inf<double>() { return __builtin_inf(); }
+template <typename A> __device__ __forceinline__ A seg_nan();
+template <> __device__ __forceinline__ float seg_nan<float>() { return __builtin_nanf(""); }
+template <> __device__ __forceinline__ double seg_nan<double>() { return __builtin_nan(""); }
+template <typename A> __device__ __forceinline__ A seg_shfl_xor(A v, int mask) { return __shfl_xor(v, mask, RUA_WAVE); }
 
 }  // namespace rua

@@ -1,0 +1,106 @@
+// rua_seg_plan.h — what the per-sequence operators (softmax, cumsum, argreduce, linear_scan, softmax_pool, norm)
+// decide BEFORE their first HIP call, as plain host C++ (no HIP header): the element size, the layout and entry checks,
+// the cut plan and the launch geometry of the lanes form.  One place for all of them: a new operator of the family
+// takes these and adds only its kernels, its pointer checks and the bytes it keeps per (block, padded column).
+#pragma once
+#include <stdint.h>
+#include "rua.h"
+
+namespace rua {
+
+constexpr int SEG_BLOCK_TOK = 2048;             // tokens per block: the unit of every fold order and of the cut form
+constexpr int64_t SEG_CUT_MAX_UNITS = 1024;     // fewer (sequence x chunk) units than this leave the chip idle ...
+constexpr int64_t SEG_CUT_MIN_LEN = 4 * SEG_BLOCK_TOK;   // ... when the sequences are this long: cut them across workgroups
+constexpr int64_t SEG_CUT_MAX_BLOCKS = 0x7fffffff / SEG_CUT_MAX_UNITS;   // units x blocks has to fit a grid
+constexpr int SEG_WAVES_PER_BLOCK = 4;          // (rua_seg.h checks it against RUA_WAVES_PER_BLOCK)
+
+// bytes of an element; 0 = the family does not take the dtype (`allow_i64`: the operators that only add or compare)
+static int seg_esize(int32_t dtype, bool allow_i64) {
+  switch (dtype) {
+    case RUA_F32: return 4;
+    case RUA_BF16: case RUA_F16: return 2;
+    case RUA_F64: return 8;
+    case RUA_I64: return allow_i64 ? 8 : 0;
+  }
+  return 0;
+}
+
+static int sm_check_layout(const rua_layout* L) {
+  if (!L || L->B < 0 || L->n_rows < 0) return RUA_EINVAL;
+  switch (L->kind) {
+    case RUA_CAT:   return (L->lens && !L->off) ? RUA_EINVAL : 0;
+    case RUA_LEFT:
+    case RUA_RIGHT: return (L->T_phys >= 0 && L->n_rows <= L->B * L->T_phys) ? 0 : RUA_EINVAL;
+    case RUA_PACK:  return (L->T < 0 || (L->T > 0 && !L->boff)) ? RUA_EINVAL : 0;
+  }
+  return RUA_EINVAL;
+}
+
+// an upper bound of the longest sequence that needs no look at the device
+static int64_t sm_len_bound(const rua_layout& L) {
+  switch (L.kind) {
+    case RUA_CAT:   return L.T_log > 0 && L.T_log < L.n_rows ? L.T_log : L.n_rows;
+    case RUA_LEFT:
+    case RUA_RIGHT: return L.T_phys;
+    case RUA_PACK:  return L.T;
+  }
+  return 0;
+}
+
+// what every entry point checks first, in this order: the layout, then H and the dtype (`es` = seg_esize of it)
+static int seg_check_entry(const rua_layout* lay, int64_t H, int es) {
+  const int e = sm_check_layout(lay);
+  if (e != 0) return e;
+  return H < 0 || !es ? RUA_EINVAL : 0;
+}
+
+// a payload whose byte offsets would not fit 64 bits is refused (RUA_ERANGE), after the operator's own pointer checks
+static bool seg_too_large(const rua_layout* lay, int64_t H, int es) {
+  return (double)lay->n_rows * (double)H * es >= 9.0e18;
+}
+
+// blocks per sequence when `units` (sequence x chunk) workgroups of sequences this long leave the chip idle; 0 = no cut
+static int64_t seg_cut_blocks(const rua_layout& L, int64_t units) {
+  const int64_t bound = sm_len_bound(L);
+  return units < SEG_CUT_MAX_UNITS && bound >= SEG_CUT_MIN_LEN ? (bound + SEG_BLOCK_TOK - 1) / SEG_BLOCK_TOK : 0;
+}
+
+struct seg_plan {
+  int n_chunks;       // 128-byte column chunks of a row (0: the row is wider than a grid has chunks)
+  int maxblk;         // > 0: the cut form, with this many blocks per sequence
+  int64_t ws_bytes;   // what the cut form needs: `ws_bytes_per_column` per block and (padded) column
+};
+
+// rows of one vector (<= 16 bytes) take the lanes form and are never cut
+static seg_plan seg_make_plan(const rua_layout& L, int64_t H, int es, int ws_bytes_per_column) {
+  seg_plan p = {0, 0, 0};
+  if (!es || H <= 0 || L.B <= 0) return p;
+  const int64_t row_bytes = H * es;
+  if ((row_bytes + 127) / 128 > 0x7fffffff) return p;
+  p.n_chunks = (int)((row_bytes + 127) / 128);
+  if (row_bytes <= 16) return p;
+  const int64_t mb = seg_cut_blocks(L, L.B * p.n_chunks);
+  if (mb > 0 && mb <= SEG_CUT_MAX_BLOCKS) {
+    p.maxblk = (int)mb;
+    p.ws_bytes = L.B * mb * p.n_chunks * (128 / es) * ws_bytes_per_column;
+  }
+  return p;
+}
+
+// the grid of a rows-form launch: a workgroup per (sequence, chunk) and, when cut, block; 0 = it does not fit (RUA_ERANGE)
+static int64_t seg_rows_grid(const rua_layout& L, const seg_plan& p, bool cut) {
+  const int64_t grid = L.B * (int64_t)p.n_chunks * (cut ? p.maxblk : 1);
+  return p.n_chunks <= 0 || grid > 0x7fffffffLL ? 0 : grid;
+}
+
+// the lanes form (rows of one vector): two sequences per wave; W = the widest power of two, up to 16 bytes, that
+// divides the row and every base address.  grid == 0: B does not fit (RUA_ERANGE)
+struct seg_lanes { int W; int64_t grid; };
+static seg_lanes seg_lanes_geometry(int64_t row_bytes, uint64_t bases, int64_t B) {
+  const uint64_t mix = (uint64_t)row_bytes | bases | 16u;
+  const int64_t waves = (B + 1) / 2;
+  const int64_t grid = (waves + SEG_WAVES_PER_BLOCK - 1) / SEG_WAVES_PER_BLOCK;
+  return {(int)(mix & (~mix + 1)), grid > 0x7fffffffLL ? 0 : grid};
+}
+
+}  // namespace rua

@@ -31,63 +31,48 @@ extern std::atomic<int> g_trace_on;        // the dispatch trace (rua_reduce.hip
 void trace_add(const char* rec);
 
 constexpr int SM_SLOTS = 32;               // parallel fold chains per (sequence, column)
-constexpr int SM_BLOCK_TOK = 2048;         // tokens per block = 64 per slot
+constexpr int SM_BLOCK_TOK = SEG_BLOCK_TOK; // tokens per block = 64 per slot
 constexpr int SM_LPR = 8;                  // row forms: 16-byte lanes per row chunk (128 bytes)
 constexpr int SM_ROWS_UNR = 4;             // row forms: rows in flight per thread
 constexpr int SM_LANES_UNR = 8;            // lanes form: tokens a lane keeps in registers (sequences up to 256 tokens)
 constexpr int SM_CAP_FWD = 512;            // resident rows of a slab: 512 x 128 B = 64 KiB, two workgroups per CU
 constexpr int SM_CAP_BWD = 256;            // the backward keeps y AND g
-constexpr int64_t SM_CUT_MAX_UNITS = 1024; // fewer (sequence x chunk) units than this leave the chip idle ...
-constexpr int64_t SM_CUT_MIN_LEN = 4 * SM_BLOCK_TOK;   // ... when the sequences are this long: cut them across workgroups
 enum { SM_FULL = 0, SM_PARTIAL = 1, SM_FINISH = 2 };
-
-__device__ __forceinline__ float sm_exp(float v) { return expf(v); }
-__device__ __forceinline__ double sm_exp(double v) { return exp(v); }
-__device__ __forceinline__ float sm_log(float v) { return logf(v); }
-__device__ __forceinline__ double sm_log(double v) { return log(v); }
-template <typename A> __device__ __forceinline__ A sm_inf();
-template <> __device__ __forceinline__ float sm_inf<float>() { return __builtin_inff(); }
-template <> __device__ __forceinline__ double sm_inf<double>() { return __builtin_inf(); }
-template <typename A> __device__ __forceinline__ A sm_nan();
-template <> __device__ __forceinline__ float sm_nan<float>() { return __builtin_nanf(""); }
-template <> __device__ __forceinline__ double sm_nan<double>() { return __builtin_nan(""); }
 
 // ---------------------------------------------------------------- the fold
 // online (max, sum): one exp per element.  NaN and +inf poison the sum (torch: the whole column of the sequence is NaN);
 // -inf adds nothing; the max itself is never NaN.
 template <typename A> __device__ __forceinline__ void fold(A& m, A& s, A x) {
-  const A inf = sm_inf<A>();
+  const A inf = seg_inf<A>();
   if (!(x < inf)) {
-    s = sm_nan<A>();
+    s = seg_nan<A>();
   } else if (x > m) {
-    s = s * sm_exp(m - x) + (A)1;
+    s = s * seg_exp(m - x) + (A)1;
     m = x;
   } else if (x > -inf) {
-    s = s + sm_exp(x - m);
+    s = s + seg_exp(x - m);
   }
 }
 
 // symmetric: combine(a, b) and combine(b, a) are the same bits
 template <typename A> __device__ __forceinline__ void combine(A& m, A& s, A m2, A s2) {
   const A M = m > m2 ? m : m2;
-  if (M == -sm_inf<A>()) {
+  if (M == -seg_inf<A>()) {
     s = s + s2;
   } else {
-    const A a = s * sm_exp(m - M), b = s2 * sm_exp(m2 - M);
+    const A a = s * seg_exp(m - M), b = s2 * seg_exp(m2 - M);
     s = a + b;
   }
   m = M;
 }
 
-template <typename A> __device__ __forceinline__ A shfl_xor_acc(A v, int mask) { return __shfl_xor(v, mask, RUA_WAVE); }
-
 // what walk 2 writes.  forward: (m, s) hold max and 1 / sum (softmax) or log(sum) (log_softmax);
 // backward: s is the sequence's sum of g * y (softmax) or of g (log_softmax), v = y
 template <bool BWD, typename A> __device__ __forceinline__ A finish(A v, A g, A m, A s, int lg) {
   if constexpr (BWD) {
-    return lg ? g - sm_exp(v) * s : v * (g - s);
+    return lg ? g - seg_exp(v) * s : v * (g - s);
   } else {
-    return lg ? (v - m) - s : sm_exp(v - m) * s;
+    return lg ? (v - m) - s : seg_exp(v - m) * s;
   }
 }
 
@@ -117,12 +102,12 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_softmax_lanes_kernel(rua_layout
   Row vx[UNR], vg[UNR];
   A M[VE], S[VE];
 #pragma unroll
-  for (int e = 0; e < VE; ++e) { M[e] = -sm_inf<A>(); S[e] = (A)0; }
+  for (int e = 0; e < VE; ++e) { M[e] = -seg_inf<A>(); S[e] = (A)0; }
 
   for (int64_t t0 = 0; t0 < maxlen; t0 += SM_BLOCK_TOK) {
     A m[VE], s[VE];
 #pragma unroll
-    for (int e = 0; e < VE; ++e) { m[e] = -sm_inf<A>(); s[e] = (A)0; }
+    for (int e = 0; e < VE; ++e) { m[e] = -seg_inf<A>(); s[e] = (A)0; }
     const int64_t t1 = len < t0 + SM_BLOCK_TOK ? len : t0 + SM_BLOCK_TOK;
     const int64_t t1w = maxlen < t0 + SM_BLOCK_TOK ? maxlen : t0 + SM_BLOCK_TOK;
     for (int64_t tt = t0; tt < t1w; tt += (int64_t)SM_SLOTS * UNR) {
@@ -159,11 +144,11 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_softmax_lanes_kernel(rua_layout
     for (int k = 1; k < SM_SLOTS; k <<= 1) {
 #pragma unroll
       for (int e = 0; e < VE; ++e) {
-        const A s2 = shfl_xor_acc(s[e], k);
+        const A s2 = seg_shfl_xor(s[e], k);
         if constexpr (BWD) {
           s[e] = s[e] + s2;
         } else {
-          const A m2 = shfl_xor_acc(m[e], k);
+          const A m2 = seg_shfl_xor(m[e], k);
           combine(m[e], s[e], m2, s2);
         }
       }
@@ -176,7 +161,7 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_softmax_lanes_kernel(rua_layout
   }
   if constexpr (!BWD) {
 #pragma unroll
-    for (int e = 0; e < VE; ++e) S[e] = lg ? sm_log(S[e]) : (A)1 / S[e];
+    for (int e = 0; e < VE; ++e) S[e] = lg ? seg_log(S[e]) : (A)1 / S[e];
   }
 
   // walk 2
@@ -281,7 +266,7 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_softmax_rows_kernel(rua_layout 
 
   A M[VE], S[VE];
 #pragma unroll
-  for (int e = 0; e < VE; ++e) { M[e] = -sm_inf<A>(); S[e] = (A)0; }
+  for (int e = 0; e < VE; ++e) { M[e] = -seg_inf<A>(); S[e] = (A)0; }
 
   if (mode == SM_FINISH) {
     for (int64_t k = 0; k < nblk; ++k) {
@@ -296,7 +281,7 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_softmax_rows_kernel(rua_layout 
     for (int64_t t0 = tb; t0 < te; t0 += SM_BLOCK_TOK) {
       A m[VE], s[VE];
 #pragma unroll
-      for (int e = 0; e < VE; ++e) { m[e] = -sm_inf<A>(); s[e] = (A)0; }
+      for (int e = 0; e < VE; ++e) { m[e] = -seg_inf<A>(); s[e] = (A)0; }
       const int64_t t1 = te < t0 + SM_BLOCK_TOK ? te : t0 + SM_BLOCK_TOK;
       if (active) {
         for (int64_t tt = t0 + q; tt < t1; tt += (int64_t)SM_SLOTS * UNR) {
@@ -340,11 +325,11 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_softmax_rows_kernel(rua_layout 
       for (int k = SM_LPR; k < RUA_WAVE; k <<= 1) {
 #pragma unroll
         for (int e = 0; e < VE; ++e) {
-          const A s2 = shfl_xor_acc(s[e], k);
+          const A s2 = seg_shfl_xor(s[e], k);
           if constexpr (BWD) {
             s[e] = s[e] + s2;
           } else {
-            const A m2 = shfl_xor_acc(m[e], k);
+            const A m2 = seg_shfl_xor(m[e], k);
             combine(m[e], s[e], m2, s2);
           }
         }
@@ -396,7 +381,7 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_softmax_rows_kernel(rua_layout 
   if (!active) return;
   if constexpr (!BWD) {
 #pragma unroll
-    for (int e = 0; e < VE; ++e) S[e] = lg ? sm_log(S[e]) : (A)1 / S[e];
+    for (int e = 0; e < VE; ++e) S[e] = lg ? seg_log(S[e]) : (A)1 / S[e];
   }
 
   // walk 2
@@ -444,37 +429,10 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_softmax_rows_kernel(rua_layout 
 }
 
 // ---------------------------------------------------------------- host side
-static int sm_esize(int32_t dtype) {
-  switch (dtype) {
-    case RUA_F32: return 4;
-    case RUA_BF16: case RUA_F16: return 2;
-    case RUA_F64: return 8;
-  }
-  return 0;
-}
-
-struct sm_plan {
-  int n_chunks;       // 128-byte column chunks of a row
-  int maxblk;         // > 0: the cut form, with this many blocks per sequence
-  int64_t ws_bytes;   // what the cut form needs
-};
-
-static sm_plan sm_make_plan(const rua_layout& L, int64_t H, int32_t dtype) {
-  sm_plan p = {0, 0, 0};
-  const int es = sm_esize(dtype);
-  if (!es || H <= 0 || L.B <= 0) return p;
-  const int64_t row_bytes = H * es;
-  p.n_chunks = (int)((row_bytes + 127) / 128);
-  if (row_bytes <= 16) return p;
-  const int64_t bound = sm_len_bound(L);
-  if (L.B * p.n_chunks < SM_CUT_MAX_UNITS && bound >= SM_CUT_MIN_LEN) {
-    const int64_t mb = (bound + SM_BLOCK_TOK - 1) / SM_BLOCK_TOK;
-    if (mb <= 0x7fffffff / SM_CUT_MAX_UNITS) {
-      p.maxblk = (int)mb;
-      p.ws_bytes = L.B * mb * p.n_chunks * 128 / es * 2 * (es == 8 ? 8 : 4);
-    }
-  }
-  return p;
+// the cut form keeps (max, sum) — the backward: (unused, sum) — per block and (padded) column: two accumulators
+static seg_plan sm_make_plan(const rua_layout& L, int64_t H, int32_t dtype) {
+  const int es = seg_esize(dtype, false);
+  return seg_make_plan(L, H, es, 2 * (es == 8 ? 8 : 4));
 }
 
 template <typename E, bool BWD>
@@ -490,11 +448,10 @@ static int sm_launch(const rua_layout& L, const void* x, const void* g, void* ou
   if (bases % sizeof(raw)) return RUA_EALIGN;                 // (elements themselves are always aligned)
 
   if (row_bytes <= 16) {
-    const uint64_t mix = (uint64_t)row_bytes | bases | 16u;
-    const int W = (int)(mix & (~mix + 1));
-    const int64_t waves = (L.B + 1) / 2;
-    const int64_t grid = (waves + RUA_WAVES_PER_BLOCK - 1) / RUA_WAVES_PER_BLOCK;
-    if (grid > 0x7fffffffLL) return RUA_ERANGE;
+    const seg_lanes ln = seg_lanes_geometry(row_bytes, bases, L.B);
+    const int W = ln.W;
+    const int64_t grid = ln.grid;
+    if (!grid) return RUA_ERANGE;
     if (g_trace_on.load(std::memory_order_relaxed)) {
       snprintf(rec, sizeof rec, "seg_softmax%s_lanes_kernel T=%s W=%d H=%d log=%d kind=%d", dir, E::name(), W, (int)H, lg,
                L.kind);
@@ -505,7 +462,7 @@ static int sm_launch(const rua_layout& L, const void* x, const void* g, void* ou
     return (int)hipGetLastError();
   }
 
-  const sm_plan p = sm_make_plan(L, H, dtype);
+  const seg_plan p = sm_make_plan(L, H, dtype);
   const bool al = row_bytes % 16 == 0 && bases % 16 == 0;
   const bool cut = ws != nullptr && p.maxblk > 0;
   constexpr int XCH_BYTES = RUA_WAVES_PER_BLOCK * SM_LPR * VE * 2 * (int)sizeof(A);
@@ -520,8 +477,8 @@ static int sm_launch(const rua_layout& L, const void* x, const void* g, void* ou
     cap = (int)(need < most ? need : most);
   }
   size_t lds = XCH_BYTES + (size_t)cap * 128 * (BWD ? 2 : 1);
-  const int64_t grid = L.B * (int64_t)p.n_chunks * (cut ? p.maxblk : 1);
-  if (grid > 0x7fffffffLL) return RUA_ERANGE;
+  const int64_t grid = seg_rows_grid(L, p, cut);
+  if (!grid) return RUA_ERANGE;
 
 #define RUA_SM_ROWS(ALV, MODE)                                                                                         \
   hipLaunchKernelGGL((seg_softmax_rows_kernel<E, BWD, ALV>), dim3((unsigned)grid), dim3(RUA_BLOCK), lds, s, L,          \
@@ -581,12 +538,12 @@ static int sm_launch(const rua_layout& L, const void* x, const void* g, void* ou
 template <bool BWD>
 static int sm_dispatch(const rua_layout* lay, const void* x, const void* g, void* out, int64_t H, int32_t dtype,
                        int32_t lg, void* ws, void* stream) {
+  const int es = seg_esize(dtype, false);
   int e;
-  if ((e = sm_check_layout(lay)) != 0) return e;
-  if (H < 0 || !sm_esize(dtype)) return RUA_EINVAL;
+  if ((e = seg_check_entry(lay, H, es)) != 0) return e;
   if (lay->B == 0 || lay->n_rows == 0 || H == 0) return 0;
   if (!x || !out || (BWD && !g)) return RUA_EINVAL;
-  if ((double)lay->n_rows * (double)H * sm_esize(dtype) >= 9.0e18) return RUA_ERANGE;
+  if (seg_too_large(lay, H, es)) return RUA_ERANGE;
   hipStream_t s = (hipStream_t)stream;
   const int l = lg ? 1 : 0;
   switch (dtype) {

@@ -18,34 +18,21 @@ padding rows of an L / R result are zeros.  The operator commutes with the casts
 z.cat().cumsum()) and `reverse` is the same association order on the mirrored token index (z.rev().cumsum().rev() ==
 z.cumsum(reverse=True)).  Autograd saves nothing: the backward is the scan in the other direction.
 """
-from torchrua_amd import _lib as K
-from torchrua_amd import _meta as M
 from torchrua_amd import _ops as O
-from torchrua_amd.layout import C, L, P, R, T, Z, describe
+from torchrua_amd.layout import C, L, P, R, T, Z, cat_lay, lay_hidden, rewrap
 
 __all__ = ['segment_cumsum', 'cumsum']
 
 
 def segment_cumsum(tensor: T, segment_sizes: T, reverse: bool = False) -> T:
     """cumsum over every run of `segment_sizes` rows of `tensor` (the signature of segment_sum); same shape."""
-    K.require_device(tensor, segment_sizes)
-    lay = M.lay_cat(segment_sizes, segment_sizes.numel(), int(tensor.size(0)))
-    return O.cumsum(tensor, lay, reverse, tuple(tensor.shape[1:]))
+    return O.cumsum(tensor, cat_lay(tensor, segment_sizes), reverse, tuple(tensor.shape[1:]))
 
 
 def cumsum(sequence: Z, reverse: bool = False) -> Z:
     """Inclusive prefix sums (suffix sums with `reverse`) over the tokens of every sequence; the same container type."""
-    data = sequence.data
-    K.require_device(data)
-    if isinstance(sequence, P):
-        lay = M.lay_pack(sequence)
-        y = O.cumsum(data, lay, reverse, tuple(data.shape[1:]))
-        out = P(data=y, batch_sizes=sequence.batch_sizes, sorted_indices=sequence.sorted_indices,
-                unsorted_indices=sequence.unsorted_indices)
-        M.adopt_pack(out, M.pack_lens(sequence), M.pack_boff(sequence), M.pack_bsz_dev(sequence))
-        return out
-    hidden = tuple(data.shape[1:]) if isinstance(sequence, C) else tuple(data.shape[2:])
-    return sequence._replace(data=O.cumsum(data, describe(sequence), reverse, hidden))
+    lay, hidden = lay_hidden(sequence)
+    return rewrap(sequence, O.cumsum(sequence.data, lay, reverse, hidden))
 
 
 for _cls in (C, L, P, R):

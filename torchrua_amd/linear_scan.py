@@ -40,9 +40,8 @@ the other way, grad_gate = grad_x * the neighbouring h — and second derivative
 from torch import Tensor
 
 from torchrua_amd import _lib as K
-from torchrua_amd import _meta as M
 from torchrua_amd import _ops as O
-from torchrua_amd.layout import C, L, P, R, T, Z, describe
+from torchrua_amd.layout import C, L, P, R, T, Z, cat_lay, lay_hidden, rewrap
 
 __all__ = ['segment_linear_scan', 'linear_scan']
 
@@ -50,9 +49,7 @@ __all__ = ['segment_linear_scan', 'linear_scan']
 def segment_linear_scan(tensor: T, gate, segment_sizes: T, reverse: bool = False) -> T:
     """The recurrence over every run of `segment_sizes` rows of `tensor` (the signature of segment_cumsum, plus the
     gate: a tensor of the shape of `tensor`, or a Python float); same shape."""
-    K.require_device(tensor, segment_sizes)
-    lay = M.lay_cat(segment_sizes, segment_sizes.numel(), int(tensor.size(0)))
-    return O.linear_scan(tensor, gate, lay, reverse, tuple(tensor.shape[1:]))
+    return O.linear_scan(tensor, gate, cat_lay(tensor, segment_sizes), reverse, tuple(tensor.shape[1:]))
 
 
 def _gate_data(sequence: Z, gate):
@@ -68,20 +65,12 @@ def _gate_data(sequence: Z, gate):
 def linear_scan(sequence: Z, gate, reverse: bool = False) -> Z:
     """h_t = gate_t * h_(t-1) + x_t over the tokens of every sequence (h_t = gate_t * h_(t+1) + x_t with `reverse`);
     the same container type.  See the module docstring for the gate forms and the documented limit."""
-    data = sequence.data
-    K.require_device(data)
+    K.require_device(sequence.data)
     gate = _gate_data(sequence, gate)
     if isinstance(gate, Tensor):
-        K.require_device(data, gate)
-    if isinstance(sequence, P):
-        lay = M.lay_pack(sequence)
-        y = O.linear_scan(data, gate, lay, reverse, tuple(data.shape[1:]))
-        out = P(data=y, batch_sizes=sequence.batch_sizes, sorted_indices=sequence.sorted_indices,
-                unsorted_indices=sequence.unsorted_indices)
-        M.adopt_pack(out, M.pack_lens(sequence), M.pack_boff(sequence), M.pack_bsz_dev(sequence))
-        return out
-    hidden = tuple(data.shape[1:]) if isinstance(sequence, C) else tuple(data.shape[2:])
-    return sequence._replace(data=O.linear_scan(data, gate, describe(sequence), reverse, hidden))
+        K.require_device(sequence.data, gate)
+    lay, hidden = lay_hidden(sequence)
+    return rewrap(sequence, O.linear_scan(sequence.data, gate, lay, reverse, hidden))
 
 
 for _cls in (C, L, P, R):

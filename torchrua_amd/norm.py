@@ -28,65 +28,44 @@ Out of scope: std (`var(z).sqrt()` on [B, H] is cheap), an affine weight and bia
 """
 from typing import Tuple
 
-from torchrua_amd import _lib as K
-from torchrua_amd import _meta as M
 from torchrua_amd import _ops as O
-from torchrua_amd.layout import C, L, P, R, T, Z, describe
+from torchrua_amd.layout import C, L, P, R, T, Z, cat_lay, lay_hidden, rewrap
 
 __all__ = ['segment_var_mean', 'segment_var', 'segment_standardize', 'var_mean', 'var', 'standardize']
-
-
-def _cat_lay(tensor: T, segment_sizes: T) -> M.Lay:
-    K.require_device(tensor, segment_sizes)
-    return M.lay_cat(segment_sizes, segment_sizes.numel(), int(tensor.size(0)))
 
 
 def segment_var_mean(tensor: T, segment_sizes: T, correction: int = 1) -> Tuple[T, T]:
     """(var, mean) over every run of `segment_sizes` rows of `tensor` [N, *hidden] (the signature of segment_mean);
     each [B, *hidden]."""
-    return O.var_mean(tensor, _cat_lay(tensor, segment_sizes), tuple(tensor.shape[1:]), correction)
+    return O.var_mean(tensor, cat_lay(tensor, segment_sizes), tuple(tensor.shape[1:]), correction)
 
 
 def segment_var(tensor: T, segment_sizes: T, correction: int = 1) -> T:
     """The variance over every run of `segment_sizes` rows of `tensor`; [B, *hidden]."""
-    return O.var_mean(tensor, _cat_lay(tensor, segment_sizes), tuple(tensor.shape[1:]), correction, want_mean=False)[0]
+    return O.var_mean(tensor, cat_lay(tensor, segment_sizes), tuple(tensor.shape[1:]), correction, want_mean=False)[0]
 
 
 def segment_standardize(tensor: T, segment_sizes: T, eps: float = 1e-5, correction: int = 0) -> T:
     """(x - mean) / sqrt(var + eps) over every run of `segment_sizes` rows of `tensor`; same shape."""
-    return O.standardize(tensor, _cat_lay(tensor, segment_sizes), tuple(tensor.shape[1:]), eps, correction)
-
-
-def _lay_hidden(sequence: Z):
-    data = sequence.data
-    K.require_device(data)
-    if isinstance(sequence, P):
-        return M.lay_pack(sequence), tuple(data.shape[1:])
-    return describe(sequence), tuple(data.shape[1:]) if isinstance(sequence, C) else tuple(data.shape[2:])
+    return O.standardize(tensor, cat_lay(tensor, segment_sizes), tuple(tensor.shape[1:]), eps, correction)
 
 
 def var_mean(sequence: Z, correction: int = 1) -> Tuple[T, T]:
     """(var, mean) over the tokens of every sequence -> two [B, *hidden] tensors in batch order."""
-    lay, hidden = _lay_hidden(sequence)
+    lay, hidden = lay_hidden(sequence)
     return O.var_mean(sequence.data, lay, hidden, correction)
 
 
 def var(sequence: Z, correction: int = 1) -> T:
     """The variance over the tokens of every sequence -> [B, *hidden] in batch order."""
-    lay, hidden = _lay_hidden(sequence)
+    lay, hidden = lay_hidden(sequence)
     return O.var_mean(sequence.data, lay, hidden, correction, want_mean=False)[0]
 
 
 def standardize(sequence: Z, eps: float = 1e-5, correction: int = 0) -> Z:
     """Every sequence minus its own mean, over its own standard deviation; returns the same container type."""
-    lay, hidden = _lay_hidden(sequence)
-    y = O.standardize(sequence.data, lay, hidden, eps, correction)
-    if isinstance(sequence, P):
-        out = P(data=y, batch_sizes=sequence.batch_sizes, sorted_indices=sequence.sorted_indices,
-                unsorted_indices=sequence.unsorted_indices)
-        M.adopt_pack(out, M.pack_lens(sequence), M.pack_boff(sequence), M.pack_bsz_dev(sequence))
-        return out
-    return sequence._replace(data=y)
+    lay, hidden = lay_hidden(sequence)
+    return rewrap(sequence, O.standardize(sequence.data, lay, hidden, eps, correction))
 
 
 for _cls in (C, L, P, R):

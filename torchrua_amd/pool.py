@@ -31,9 +31,8 @@ import torch
 from torch import Tensor
 
 from torchrua_amd import _lib as K
-from torchrua_amd import _meta as M
 from torchrua_amd import _ops as O
-from torchrua_amd.layout import C, L, P, R, T, Z, describe
+from torchrua_amd.layout import C, L, P, R, T, Z, cat_lay, lay_hidden
 
 __all__ = ['segment_softmax_pool', 'softmax_pool']
 
@@ -51,19 +50,14 @@ def _score_columns(values: Tensor, scores: Tensor, lead: int) -> int:
     if values.dim() < lead or len(ss) < lead or len(ss) > len(vs) or ss != vs[:len(ss)]:
         raise K.RuaError(f'softmax_pool: scores of shape {ss} do not fit values of storage shape {vs}: the token dims '
                          f'{vs[:lead]} followed by a prefix of the hidden dims {vs[lead:]}')
-    G = 1
-    for d in ss[lead:]:
-        G *= d
-    return G
+    return O._prod(ss[lead:])
 
 
 def segment_softmax_pool(tensor: T, scores: T, segment_sizes: T) -> T:
     """The softmax-weighted sum over every run of `segment_sizes` rows of `tensor` [N, *hidden] (the signature of
     segment_sum plus the scores [N, *prefix of hidden]); returns [B, *hidden]."""
-    K.require_device(tensor, segment_sizes)
-    G = _score_columns(tensor, scores, 1)
-    lay = M.lay_cat(segment_sizes, segment_sizes.numel(), int(tensor.size(0)))
-    return O.softmax_pool(tensor, scores, lay, tuple(tensor.shape[1:]), G)
+    lay = cat_lay(tensor, segment_sizes)
+    return O.softmax_pool(tensor, scores, lay, tuple(tensor.shape[1:]), _score_columns(tensor, scores, 1))
 
 
 def _scores_data(sequence: Z, scores) -> Tensor:
@@ -84,12 +78,9 @@ def softmax_pool(sequence: Z, scores) -> T:
     data = sequence.data
     K.require_device(data)
     scores = _scores_data(sequence, scores)
-    if isinstance(sequence, P):
-        G = _score_columns(data, scores, 1)
-        return O.softmax_pool(data, scores, M.lay_pack(sequence), tuple(data.shape[1:]), G)
-    lead = 1 if isinstance(sequence, C) else 2
-    G = _score_columns(data, scores, lead)
-    return O.softmax_pool(data, scores, describe(sequence), tuple(data.shape[lead:]), G)
+    G = _score_columns(data, scores, 1 if isinstance(sequence, (C, P)) else 2)
+    lay, hidden = lay_hidden(sequence)
+    return O.softmax_pool(data, scores, lay, hidden, G)
 
 
 for _cls in (C, L, P, R):

@@ -15,18 +15,14 @@ sequence and column; the global `initial` of segment_logsumexp is NOT inherited)
 storage shape and dtype of the input; padding rows of an L / R result are zeros.  The operator commutes with the casts
 bit for bit: z.softmax().cat() == z.cat().softmax().  Autograd saves only y.
 """
-from torchrua_amd import _lib as K
-from torchrua_amd import _meta as M
 from torchrua_amd import _ops as O
-from torchrua_amd.layout import C, L, P, R, T, Z, describe
+from torchrua_amd.layout import C, L, P, R, T, Z, cat_lay, lay_hidden, rewrap
 
 __all__ = ['segment_softmax', 'segment_log_softmax', 'softmax', 'log_softmax']
 
 
 def _segment(tensor: T, segment_sizes: T, log: bool) -> T:
-    K.require_device(tensor, segment_sizes)
-    lay = M.lay_cat(segment_sizes, segment_sizes.numel(), int(tensor.size(0)))
-    return O.softmax(tensor, lay, log, tuple(tensor.shape[1:]))
+    return O.softmax(tensor, cat_lay(tensor, segment_sizes), log, tuple(tensor.shape[1:]))
 
 
 def segment_softmax(tensor: T, segment_sizes: T) -> T:
@@ -40,17 +36,8 @@ def segment_log_softmax(tensor: T, segment_sizes: T) -> T:
 
 
 def _seq(sequence: Z, log: bool) -> Z:
-    data = sequence.data
-    K.require_device(data)
-    if isinstance(sequence, P):
-        lay = M.lay_pack(sequence)
-        y = O.softmax(data, lay, log, tuple(data.shape[1:]))
-        out = P(data=y, batch_sizes=sequence.batch_sizes, sorted_indices=sequence.sorted_indices,
-                unsorted_indices=sequence.unsorted_indices)
-        M.adopt_pack(out, M.pack_lens(sequence), M.pack_boff(sequence), M.pack_bsz_dev(sequence))
-        return out
-    hidden = tuple(data.shape[1:]) if isinstance(sequence, C) else tuple(data.shape[2:])
-    return sequence._replace(data=O.softmax(data, describe(sequence), log, hidden))
+    lay, hidden = lay_hidden(sequence)
+    return rewrap(sequence, O.softmax(sequence.data, lay, log, hidden))
 
 
 def softmax(sequence: Z) -> Z:
