@@ -558,6 +558,63 @@ int rua_segment_linear_scan_backward(const rua_layout* lay, const void* grad_out
                                      double gate_scalar, const void* h, void* grad_x, void* grad_gate /* NULL */,
                                      int64_t H, int32_t dtype, int32_t reverse, void* ws, void* stream);
 
+/* Per-sequence causal depthwise convolution over the tokens of a sequence (an EXTENSION, added to ABI 6 — the version
+ * number did not move: the reference has no convolution; its users pad, transpose, call a grouped conv1d, slice,
+ * transpose and cast back).  For every sequence b of `lay` (ANY layout), column h and token t < len[b]:
+ *   reverse == 0:  out[t] = bias[h] + sum_{k = 0 .. K-1, t - (K-1) + k >= 0}   weight[k,h] * data[t - (K-1) + k]
+ *   reverse != 0:  out[t] = bias[h] + sum_{k = 0 .. K-1, t + (K-1) - k < len}  weight[k,h] * data[t + (K-1) - k]
+ * `weight` is [K, H], tap-major (weight[K-1] multiplies the current token), `bias` is [H] or NULL, both in the payload
+ * dtype.  1 <= K <= RUA_CONV_MAX_TAPS (K < 1: RUA_EINVAL, K > RUA_CONV_MAX_TAPS: RUA_ERANGE).  For finite weights this
+ * is a zero-padded grouped conv1d of every sequence on its own; the ONE difference from zero padding: a tap that falls
+ * outside the sequence is NOT EVALUATED instead of being multiplied by zero, so a non-finite weight does not poison the
+ * first (last) K - 1 tokens.  `reverse` is the anti-causal mirror — the adjoint the backward needs.
+ * RUA_F32 / RUA_BF16 / RUA_F16 / RUA_F64 (anything else: RUA_EINVAL).  ONE evaluation order per (token, column),
+ * whatever the layout, kernel form, alignment or block boundary: the accumulator (fp32; fp64 for RUA_F64) starts at the
+ * bias (+0 without one), the taps that exist are added in ascending k with a fused multiply-add, the result is rounded
+ * once.  Hence, BIT FOR BIT: the operator commutes with the casts; `reverse` equals reversing every sequence, convolving
+ * forward and reversing back; K == 1 with weight 1 and no bias returns the payload (but for the sign of a zero).
+ * Padding rows of a LEFT / RIGHT payload are never read and are written as zeros in the same pass; an empty sequence
+ * contributes nothing; B == 0, n_rows == 0 and H == 0 return 0 without a launch.  Lengths are clamped to the storage
+ * and every row is range-checked.
+ * Kernel forms: rows of one vector (<= 16 bytes) put consecutive tokens on consecutive lanes, two sequences per wave,
+ * and take the K - 1 rows before a token from the lanes below by shuffle; wider rows give a workgroup per (sequence x
+ * 128-byte column chunk) whose 32 x 8 threads each walk a contiguous run of tokens with the previous K - 1 vectors, the
+ * K weight vectors and the bias in registers (the K - 1 rows in front of a run are loaded again); few but long sequences
+ * (the cut rule of rua_segment_softmax: fewer than 1 024 units with a length bound of at least 8 192) always spread
+ * over workgroups per block of 2 048 tokens — blocks need nothing of each other but those K - 1 rows: no workspace,
+ * no second launch.  Every row is read once and written once.
+ * Aliasing: `out` may equal `data` (then a sequence stays with one workgroup); it must not be `weight` or `bias`
+ * (RUA_EINVAL).
+ * rua_segment_causal_conv_backward, for the convolution whose direction was `reverse`; each output may be NULL:
+ *   grad_in     = the convolution of grad_out by `weight` the OTHER way, no bias (the forward kernel: `data` is not
+ *                 read, no workspace);
+ *   grad_weight = [K, H]: sum over every token of grad_out[t] * data[the token tap k read];
+ *   grad_bias   = [H]: sum over every token of grad_out[t];
+ * all in the payload dtype, the sums accumulated in fp32 (fp64) and rounded once.  ONE walk computes all three: a
+ * workgroup keeps the sums of the units it walks in registers, folds them over its threads in a fixed tree and leaves
+ * one partial per (part, chunk) in `ws`; a finish launch adds the parts in part order.  No float atomics: grad_weight
+ * and grad_bias are bitwise reproducible from run to run for the same container; they are NOT the same bits across
+ * layouts (the order over the sequences follows the storage).  The workspace is bounded independently of n_rows:
+ *   rua_causal_conv_ws_bytes(lay, H, K, dtype) = parts * n_chunks * (128 / esize) * (K + 1) * sizeof(acc)
+ * with n_chunks = ceil(H * esize / 128), sizeof(acc) = 4 (8 for RUA_F64) and parts = min(1 024, units), units = B
+ * for rows wider than 16 bytes (B * ceil(bound / 2 048) when the cut rule applies), ceil(ceil(B / 2) / 4) for rows of
+ * one vector; 0 for arguments the entry points refuse and when there is nothing to do.  Needed only when grad_weight
+ * or grad_bias is wanted (then ws == NULL: RUA_EINVAL).  `data` may be NULL unless grad_weight is wanted, `weight` unless
+ * grad_in is.  grad_in must not alias grad_out, data or weight; grad_weight / grad_bias nothing that is read and no
+ * other output (RUA_EINVAL).  Padding rows of grad_in are zeros.
+ * While the dispatch trace is on (below) every launch records `seg_conv_lanes_kernel` or `seg_conv_rows_kernel` with
+ * key=value pairs (T=, K=, AL= / W=, rev= — the direction this launch walks in —, kind=, bwd= — 1 when it sums
+ * grad_weight / grad_bias —, cut=, parts=), and `seg_conv_finish_kernel` for the finish. */
+#define RUA_CONV_MAX_TAPS 8
+int64_t rua_causal_conv_ws_bytes(const rua_layout* lay, int64_t H, int32_t K, int32_t dtype);   /* backward only */
+int rua_segment_causal_conv(const rua_layout* lay, const void* data, const void* weight, const void* bias /* NULL */,
+                            void* out, int64_t H, int32_t K, int32_t dtype, int32_t reverse, void* stream);
+int rua_segment_causal_conv_backward(const rua_layout* lay, const void* grad_out,
+                                     const void* data /* NULL unless grad_weight */,
+                                     const void* weight /* NULL unless grad_in */, void* grad_in /* NULL */,
+                                     void* grad_weight /* NULL */, void* grad_bias /* NULL */, int64_t H, int32_t K,
+                                     int32_t dtype, int32_t reverse, void* ws, void* stream);
+
 /* Per-sequence argmax / argmin with the selected values (an EXTENSION, added to ABI 6 — the version number did not
  * move: the reference has no position-returning reduction; its users pad with -inf and call torch.argmax along dim 1).
  * For every sequence b of `lay` (ANY layout) and column h, over t < len[b] (op = RUA_MAX or RUA_MIN, anything else:

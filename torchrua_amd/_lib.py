@@ -30,6 +30,7 @@ EXTREME_WORDS = 1027                               # rua.h: RUA_EXTREME_WORDS
 POOL_OUT_ACC = 0x100       # rua.h: RUA_POOL_OUT_ACC, OR-ed into the dtype of rua_segment_softmax_pool[_backward]
 NORM_MEAN_ACC = 0x100      # rua.h: RUA_NORM_MEAN_ACC, OR-ed into the dtype of rua_segment_var_mean[_backward]
 OP_SHORT_SEQS = 0x400      # rua.h: a CattedSequence of short sequences, none far above the average (a hint)
+CONV_MAX_TAPS = 8          # rua.h: RUA_CONV_MAX_TAPS, the longest filter of rua_segment_causal_conv
 # enum rua_dtype / rua_op
 F32, BF16, F16, F64 = 0, 1, 2, 3
 SUM, MEAN, MAX, MIN, PROD, LOGSUMEXP = 0, 1, 2, 3, 4, 5
@@ -110,6 +111,11 @@ SYMBOLS = {
                                         c_int32, c_void_p, c_void_p]),
     'rua_segment_linear_scan_backward': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_double, c_void_p, c_void_p,
                                                  c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
+    'rua_causal_conv_ws_bytes': (c_int64, [POINTER(RuaLayout), c_int64, c_int32, c_int32]),
+    'rua_segment_causal_conv': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32,
+                                        c_int32, c_int32, c_void_p]),
+    'rua_segment_causal_conv_backward': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                 c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     'rua_argreduce_ws_bytes': (c_int64, [POINTER(RuaLayout), c_int64, c_int32]),
     'rua_segment_argreduce': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p,
                                       c_void_p]),

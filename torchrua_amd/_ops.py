@@ -69,9 +69,12 @@ def _target(out: Optional[Tensor], like_shape, dtype: torch.dtype, dev, what: st
     return out
 
 
-def _workspace(ws_bytes_fn: str, lay: 'M.Lay', H: int, code: int, dev, cut: bool = True) -> Optional[Tensor]:
-    """What the cut form of a per-sequence operator needs (> 0 bytes: few but long sequences get cut), or None."""
-    nbytes = getattr(L.load(), ws_bytes_fn)(lay.ref(), H, code) if cut else 0
+def _workspace(ws_bytes_fn: str, lay: 'M.Lay', H: int, code: int, dev, cut: bool = True,
+               taps: Optional[int] = None) -> Optional[Tensor]:
+    """What the cut form of a per-sequence operator needs (> 0 bytes: few but long sequences get cut), or None.
+    `taps`: the size function also takes a filter length (the causal conv's backward sums)."""
+    args = (lay.ref(), H, code) if taps is None else (lay.ref(), H, taps, code)
+    nbytes = getattr(L.load(), ws_bytes_fn)(*args) if cut else 0
     return torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
 
 
@@ -911,6 +914,158 @@ def linear_scan(data: Tensor, gate, lay: M.Lay, reverse: bool, hidden) -> Tensor
         return _LinearScan.apply(data.contiguous(), None if gt is None else gt.contiguous(), gs, lay, bool(reverse),
                                  tuple(hidden))
     return launch_linear_scan(lay, _plain(data), gs if gt is None else _plain(gt), bool(reverse), tuple(hidden))
+
+
+# ------------------------------------------------------------------ per-sequence causal depthwise conv (an extension)
+_CONV_SUPPORT = 'causal_conv supports'
+
+
+def _conv_args(data: Tensor, weight: Optional[Tensor], bias: Optional[Tensor], hidden: Tuple[int, ...],
+               taps: Optional[int] = None) -> int:
+    """K, after the checks that need no device — the filter is [K, *hidden] with 1 <= K <= CONV_MAX_TAPS, the bias
+    [*hidden], both of the payload's dtype — and then the one that does: everything on one HIP device."""
+    hidden = tuple(hidden)
+    if weight is not None:
+        if weight.dim() != 1 + len(hidden) or tuple(weight.shape[1:]) != hidden:
+            raise L.RuaError(f'causal_conv: the weight has shape {tuple(weight.shape)}, the payload\'s hidden dimensions '
+                             f'are {hidden}: it must be [K, *hidden] (tap-major)')
+        taps = int(weight.shape[0])
+    if taps is None or not 1 <= taps <= L.CONV_MAX_TAPS:
+        raise L.RuaError(f'causal_conv: 1 <= K <= {L.CONV_MAX_TAPS} taps; got {taps}')
+    if bias is not None and tuple(bias.shape) != hidden:
+        raise L.RuaError(f'causal_conv: the bias has shape {tuple(bias.shape)}, the payload\'s hidden dimensions are {hidden}')
+    for name, t in (('weight', weight), ('bias', bias)):
+        if t is not None and t.dtype != data.dtype:
+            raise L.RuaError(f'causal_conv: the {name} has dtype {t.dtype}, the payload {data.dtype}')
+    L.require_device(data, weight, bias)
+    return taps
+
+
+def launch_causal_conv(lay: M.Lay, data: Tensor, weight: Tensor, bias: Optional[Tensor], reverse: bool,
+                       hidden: Tuple[int, ...], out: Optional[Tensor] = None) -> Tensor:
+    """rua_segment_causal_conv: one launch, one read and one write of the payload; no workspace.  `out` may be `data`
+    itself, never the weight or the bias."""
+    taps = _conv_args(data, weight, bias, hidden)
+    code = _require_dtype(data, L.DTYPES, _CONV_SUPPORT)
+    dev, H = data.device, _prod(hidden)
+    data, weight = data.contiguous(), weight.contiguous()
+    bias = None if bias is None else bias.contiguous()
+    out = _target(out, data.shape, data.dtype, dev, 'causal_conv' + _LIKE_PAYLOAD)      # padding rows: zeroed by the call
+    _call('causal_conv_rev' if reverse else 'causal_conv', 'rua_segment_causal_conv', dev, lay.ref(), L.ptr(data),
+          L.ptr(weight), L.ptr(bias), L.ptr(out), H, taps, code, int(bool(reverse)))
+    return out
+
+
+def launch_causal_conv_backward(lay: M.Lay, grad: Tensor, data: Optional[Tensor], weight: Optional[Tensor],
+                                reverse: bool, hidden: Tuple[int, ...], taps: Optional[int] = None,
+                                want_input: bool = True, want_weight: bool = True,
+                                want_bias: bool = True) -> Tuple[Optional[Tensor], Optional[Tensor], Optional[Tensor]]:
+    """rua_segment_causal_conv_backward: (grad_input, grad_weight, grad_bias) — None where not wanted — of the
+    convolution whose direction was `reverse`: one walk, plus a small finish when a [K, H] / [H] sum is wanted.  With
+    only grad_input wanted `data` is not read and no workspace is allocated."""
+    want_input, want_weight, want_bias = bool(want_input), bool(want_weight), bool(want_bias)
+    data = data if want_weight else None
+    weight = weight if want_input or taps is None else None
+    taps = _conv_args(grad, weight, None, hidden, taps)
+    code = _require_dtype(grad, L.DTYPES, _CONV_SUPPORT)
+    dev, H = grad.device, _prod(hidden)
+    if want_weight:
+        L.require_device(grad, data)
+        if data is None or data.dtype != grad.dtype or data.shape != grad.shape:
+            raise L.RuaError('causal_conv backward: the saved payload must have the dtype and shape of the cotangent')
+        data = data.contiguous()
+    if want_input and weight is None:
+        raise L.RuaError('causal_conv backward: grad_input needs the weight')
+    grad = grad.contiguous()
+    weight = weight.contiguous() if want_input else None
+    # the partial sums of grad_weight / grad_bias: at most 1 024 parts per column chunk, whatever the number of tokens
+    ws = _workspace('rua_causal_conv_ws_bytes', lay, H, code, dev, want_weight or want_bias, taps)
+    gx = torch.empty(grad.shape, dtype=grad.dtype, device=dev) if want_input else None
+    # (nothing to walk: the entry point returns without a launch, and an empty sum is 0)
+    small = torch.zeros if lay.B == 0 or lay.n_rows == 0 or H == 0 else torch.empty
+    gw = small((taps,) + tuple(hidden), dtype=grad.dtype, device=dev) if want_weight else None
+    gb = small(tuple(hidden), dtype=grad.dtype, device=dev) if want_bias else None
+    _call('causal_conv_rev_bwd' if reverse else 'causal_conv_bwd', 'rua_segment_causal_conv_backward', dev, lay.ref(),
+          L.ptr(grad), L.ptr(data), L.ptr(weight), L.ptr(gx), L.ptr(gw), L.ptr(gb), H, taps, code, int(bool(reverse)),
+          L.ptr(ws))
+    return gx, gw, gb
+
+
+class _CausalConv(torch.autograd.Function):
+    """y = the causal depthwise convolution of every sequence.  Saves the weight, and the payload only when the weight
+    needs a gradient; the backward is one fused entry point.  While a graph of the backward is being recorded
+    (create_graph=True) it is composed of two differentiable primitives that close over each other: the convolution
+    itself (linear in each argument) and _ConvWeightGrad."""
+
+    @staticmethod
+    def forward(ctx, data: Tensor, weight: Tensor, bias: Optional[Tensor], lay: M.Lay, reverse: bool, hidden):
+        ctx.lay, ctx.reverse, ctx.hidden, ctx.taps = lay, reverse, tuple(hidden), int(weight.shape[0])
+        ctx.saved_data = ctx.needs_input_grad[1]
+        if ctx.saved_data:
+            ctx.save_for_backward(weight, data)
+        else:
+            ctx.save_for_backward(weight)
+        return launch_causal_conv(lay, data, weight, bias, reverse, hidden)
+
+    @staticmethod
+    def backward(ctx, grad: Tensor):
+        weight = ctx.saved_tensors[0]
+        data = ctx.saved_tensors[1] if ctx.saved_data else None
+        want_x, want_w, want_b = ctx.needs_input_grad[:3]
+        if torch.is_grad_enabled():
+            grad = grad.contiguous()
+            gx = causal_conv(grad, weight, None, ctx.lay, not ctx.reverse, ctx.hidden) if want_x else None
+            gw = gb = None
+            if want_w or want_b:
+                gw, gb = _ConvWeightGrad.apply(grad, data, ctx.lay, ctx.reverse, ctx.hidden, ctx.taps, want_w, want_b)
+        else:
+            gx, gw, gb = launch_causal_conv_backward(ctx.lay, grad, data, weight, ctx.reverse, ctx.hidden, ctx.taps,
+                                                     want_x, want_w, want_b)
+        return gx, gw, gb, None, None, None
+
+
+class _ConvWeightGrad(torch.autograd.Function):
+    """(g, x) -> (grad_weight [K, *hidden], grad_bias [*hidden]) of the convolution whose direction was `reverse`:
+    gw[k] = sum_t g[t] * x[the token tap k read], gb = sum_t g[t].  Bilinear, so with cotangents (cw, cb) its adjoints
+    are convolutions again:  d / dg = causal_conv(x, cw, bias=cb)  in the same direction,
+    d / dx = causal_conv(g, cw, reverse = the other direction) — derivatives of any order from the library's kernels."""
+
+    @staticmethod
+    def forward(ctx, g: Tensor, x: Optional[Tensor], lay: M.Lay, reverse: bool, hidden, taps: int, want_w: bool,
+                want_b: bool):
+        ctx.lay, ctx.reverse, ctx.hidden, ctx.taps, ctx.has_x = lay, reverse, tuple(hidden), taps, x is not None
+        ctx.save_for_backward(*((g, x) if x is not None else (g,)))
+        _, gw, gb = launch_causal_conv_backward(lay, g, x, None, reverse, hidden, taps, False, want_w and x is not None,
+                                                want_b)
+        return gw, gb
+
+    @staticmethod
+    def backward(ctx, cw: Optional[Tensor], cb: Optional[Tensor]):
+        g = ctx.saved_tensors[0]
+        x = ctx.saved_tensors[1] if ctx.has_x else None
+        dg = dx = None
+        if ctx.needs_input_grad[0] and (cw is not None or cb is not None):
+            if cw is not None and x is not None:
+                dg = causal_conv(x, cw.contiguous(), cb, ctx.lay, ctx.reverse, ctx.hidden)
+            else:
+                # only the bias' cotangent: every live token receives cb (a one-tap filter of zeros, plus the bias)
+                zero = torch.zeros((1,) + ctx.hidden, dtype=g.dtype, device=g.device)
+                dg = causal_conv(torch.zeros_like(g), zero, cb, ctx.lay, ctx.reverse, ctx.hidden)
+        if x is not None and ctx.needs_input_grad[1] and cw is not None:
+            dx = causal_conv(g, cw.contiguous(), None, ctx.lay, not ctx.reverse, ctx.hidden)
+        return dg, dx, None, None, None, None, None, None
+
+
+def causal_conv(data: Tensor, weight: Tensor, bias: Optional[Tensor], lay: M.Lay, reverse: bool, hidden) -> Tensor:
+    _conv_args(data, weight, bias, tuple(hidden))
+    _require_dtype(data, L.DTYPES, _CONV_SUPPORT)
+    if torch.is_grad_enabled() and (data.requires_grad or weight.requires_grad or
+                                    (bias is not None and bias.requires_grad)):
+        # contiguous HERE, before the Function (as in reduce()): a copy made inside forward() would carry no history
+        return _CausalConv.apply(data.contiguous(), weight.contiguous(), None if bias is None else bias.contiguous(), lay,
+                                 bool(reverse), tuple(hidden))
+    return launch_causal_conv(lay, _plain(data), _plain(weight), None if bias is None else _plain(bias), bool(reverse),
+                              tuple(hidden))
 
 
 # ------------------------------------------------------------------ per-sequence argmax / argmin (an extension)
