@@ -615,6 +615,56 @@ int rua_segment_causal_conv_backward(const rua_layout* lay, const void* grad_out
                                      void* grad_weight /* NULL */, void* grad_bias /* NULL */, int64_t H, int32_t K,
                                      int32_t dtype, int32_t reverse, void* ws, void* stream);
 
+/* Per-sequence compress — keep the tokens where a mask is set (an EXTENSION, added to ABI 6 — the version number did
+ * not move: the reference's users spell it as data[mask], a segment_sum of the mask and a new constructor, for a
+ * CattedSequence only).  The first operator whose result has ANOTHER raggedness than its input: sequence b of the result
+ * holds the tokens t of sequence b of the input with mask[row(b,t)] != 0, in their order.  Two entry points, because the
+ * new lengths size the result and the caller reads them back in between (ONE read-back of [B] int64; nothing here
+ * synchronises).
+ * rua_segment_compress_plan: `mask` holds one byte per STORAGE ROW of `lay` (ANY layout; n_rows bytes).  Writes
+ *   rank[j]     (int32, n_rows entries) = #{s < t : mask[row(b,s)] != 0} for the row j of token (b, t) when its own
+ *               byte is set — the position the token takes in its new sequence — and -1 for a dropped token AND for a
+ *               padding row of a LEFT / RIGHT storage (whose mask bytes are never read);
+ *   new_lens[b] (int64) = the number of kept tokens of sequence b.
+ * The mask is read once, four bytes are written per storage row, nothing else per token.  The walk goes sequence by
+ * sequence through the layout's own row formula, the same for the four kinds.  Integer work: every form gives the same
+ * bits.  Four forms by the length bound (CAT: T_log or n_rows, LEFT / RIGHT: T_phys, PACK: T): up to 64, two sequences
+ * per wave, 32 lanes each; below 2 048, a wave per sequence; longer, a workgroup per sequence that walks blocks of
+ * 2 048 tokens with a carried count — in all three the count in front of a lane is a popcount over one 64-bit ballot;
+ * few but long sequences (fewer than 1 024 of them with a bound of at least 8 192) are cut into their blocks across
+ * workgroups when `ws` is given: the first launch leaves every block's count in `ws`, the second adds the counts of
+ * the blocks before a block in block order.  rua_compress_ws_bytes(lay) =
+ *   B * ceil(bound / 2 048) * 4
+ * bytes when the cut form applies, else 0 (0 = never needed; ws == NULL = do not cut).  A CAT layout's T_log, where it
+ * is given (> 0), must be a TRUE upper bound of every length, as for rua_segment_softmax.  Lengths are clamped to the
+ * storage and every row is range-checked.
+ * Checks, before any HIP call: a null or inconsistent layout RUA_EINVAL; a length bound of 2^31 or more RUA_ERANGE (a
+ * rank is an int32; rua_compress_ws_bytes returns 0 for both); B == 0 returns 0 without a launch; then a null mask /
+ * rank (with n_rows > 0) / new_lens, or outputs that alias, RUA_EINVAL.  Trace: `seg_compress_plan_kernel form=lanes|
+ * rows|long|cut G= kind= cut= blocks= phase=whole|count|finish`.
+ * rua_segment_compress_move: `big` is the input's layout, `small` the result's (any two kinds, the same B; small's
+ * lengths are new_lens, its offsets / PackedSequence metadata the caller's, from rua_exclusive_scan_i64 /
+ * rua_pack_prepare as for any container); rows are row_bytes wide on both sides and move as BITS.
+ *   expand == 0: every row of big with rank >= 0 is copied to small's row of token (b, rank); padding rows of a LEFT /
+ *                RIGHT small are written as zeros in the same launch (no pre-zeroing).  For CAT / PACK results the
+ *                payload is read once and written once.
+ *   expand != 0: the adjoint.  Every row of big with rank >= 0 reads that row of small; every other row of big —
+ *                dropped tokens and padding — is written as zeros: big is written completely.
+ * A rank that names no token of its new sequence moves nothing.  Two forms: rows of at most 16 bytes put the tokens of
+ * a sequence on 32 lanes, two sequences per wave; wider rows give a workgroup per (sequence x 128-byte column chunk),
+ * 32 tokens x 8 pieces of 16 bytes, four tokens in flight per thread; few but long sequences (the cut rule over
+ * B * chunks units) spread over workgroups per block of 2 048 tokens — no workspace, no second launch.  Accesses are
+ * the widest power of two, up to 16 bytes, that divides row_bytes and both base addresses: any alignment is accepted.
+ * Checks: the entry checks of the plan for `big`, then for `small`; different B RUA_EINVAL; B == 0, row_bytes == 0 or a
+ * destination without rows return 0; a null rank or payload, or small_data == big_data, RUA_EINVAL.  Trace:
+ * `seg_compress_move_lanes_kernel` / `seg_compress_move_rows_kernel` with W= row_bytes= expand= small= big= cut=.
+ * (A variant with a caller-given capacity that never reads the lengths back is the natural follow-up; it is not built.) */
+int64_t rua_compress_ws_bytes(const rua_layout* lay);
+int rua_segment_compress_plan(const rua_layout* lay, const void* mask, int32_t* rank, int64_t* new_lens, void* ws,
+                              void* stream);
+int rua_segment_compress_move(const rua_layout* small, const rua_layout* big, const int32_t* rank, void* small_data,
+                              void* big_data, int64_t row_bytes, int32_t expand, void* stream);
+
 /* Per-sequence argmax / argmin with the selected values (an EXTENSION, added to ABI 6 — the version number did not
  * move: the reference has no position-returning reduction; its users pad with -inf and call torch.argmax along dim 1).
  * For every sequence b of `lay` (ANY layout) and column h, over t < len[b] (op = RUA_MAX or RUA_MIN, anything else:

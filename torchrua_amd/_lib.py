@@ -116,6 +116,10 @@ SYMBOLS = {
                                         c_int32, c_int32, c_void_p]),
     'rua_segment_causal_conv_backward': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                  c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    'rua_compress_ws_bytes': (c_int64, [POINTER(RuaLayout)]),
+    'rua_segment_compress_plan': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'rua_segment_compress_move': (c_int, [POINTER(RuaLayout), POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_int64,
+                                          c_int32, c_void_p]),
     'rua_argreduce_ws_bytes': (c_int64, [POINTER(RuaLayout), c_int64, c_int32]),
     'rua_segment_argreduce': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p,
                                       c_void_p]),

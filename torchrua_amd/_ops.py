@@ -69,11 +69,14 @@ def _target(out: Optional[Tensor], like_shape, dtype: torch.dtype, dev, what: st
     return out
 
 
-def _workspace(ws_bytes_fn: str, lay: 'M.Lay', H: int, code: int, dev, cut: bool = True,
+def _workspace(ws_bytes_fn: str, lay: 'M.Lay', H: Optional[int], code: Optional[int], dev, cut: bool = True,
                taps: Optional[int] = None) -> Optional[Tensor]:
     """What the cut form of a per-sequence operator needs (> 0 bytes: few but long sequences get cut), or None.
-    `taps`: the size function also takes a filter length (the causal conv's backward sums)."""
+    `taps`: the size function also takes a filter length (the causal conv's backward sums).  H is None: it takes the
+    layout alone (the compress plan counts a mask: no row width, no dtype)."""
     args = (lay.ref(), H, code) if taps is None else (lay.ref(), H, taps, code)
+    if H is None:
+        args = (lay.ref(),)
     nbytes = getattr(L.load(), ws_bytes_fn)(*args) if cut else 0
     return torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
 
@@ -1066,6 +1069,97 @@ def causal_conv(data: Tensor, weight: Tensor, bias: Optional[Tensor], lay: M.Lay
                                  bool(reverse), tuple(hidden))
     return launch_causal_conv(lay, _plain(data), _plain(weight), None if bias is None else _plain(bias), bool(reverse),
                               tuple(hidden))
+
+
+# ------------------------------------------------------------------ per-sequence compress: keep tokens by mask (an extension)
+def launch_compress_plan(lay: M.Lay, mask: Tensor, cut: bool = True) -> Tuple[Tensor, Tensor]:
+    """rua_segment_compress_plan: (rank int32 [storage rows of `lay`], new_lens int64 [B]) from a bool mask with one
+    value per storage row — one launch (two for cut sequences); the mask is read once.  rank is the position a kept
+    token takes in its new sequence, -1 for a dropped token and for a padding row.  cut=False withholds the workspace
+    (the same bits from one workgroup per sequence: a developer A/B)."""
+    dev = L.require_device(mask)
+    if mask.dtype != torch.bool or mask.numel() != lay.n_rows:
+        raise L.RuaError(f'compress plan: the mask is a torch.bool tensor with one value per storage row ({lay.n_rows}); '
+                         f'got {mask.dtype} with {mask.numel()} values')
+    mask = _plain(mask).contiguous()
+    rank = torch.empty(lay.n_rows, dtype=torch.int32, device=dev)
+    new_lens = torch.empty(lay.B, dtype=torch.int64, device=dev)
+    if lay.B == 0:
+        return rank.fill_(-1), new_lens                 # (the entry point returns without a launch)
+    ws = _workspace('rua_compress_ws_bytes', lay, None, None, dev, cut)
+    _call('compress_plan', 'rua_segment_compress_plan', dev, lay.ref(), L.ptr(mask), L.ptr(rank), L.ptr(new_lens),
+          L.ptr(ws))
+    return rank, new_lens
+
+
+def launch_compress_move(small: M.Lay, big: M.Lay, rank: Tensor, src: Tensor, hidden: Tuple[int, ...],
+                         out_shape: Sequence[int], expand: bool, out: Optional[Tensor] = None) -> Tensor:
+    """rua_segment_compress_move: expand=False copies the rows of `src` (storage of `big`) whose rank is >= 0 to their
+    rows of a new payload of `small`; expand=True is the adjoint — `src` has the storage of `small`, the result that of
+    `big`, zeros at dropped tokens.  Rows move as bits; padding rows of a padded result are zeros; one launch."""
+    dev = L.require_device(src, rank)
+    if src.element_size() not in (1, 2, 4, 8):
+        raise L.RuaError(f'compress moves elements of 1, 2, 4 or 8 bytes; got {src.dtype}')
+    if rank.dtype != torch.int32 or rank.numel() != big.n_rows or not rank.is_contiguous():
+        raise L.RuaError('compress move: the rank table is a contiguous int32 tensor with one entry per storage row')
+    src = src.contiguous()
+    out = _target(out, out_shape, src.dtype, dev, 'compress' + _LIKE_PAYLOAD)
+    if out.numel() == 0:
+        return out
+    if src.numel() == 0:
+        return out.zero_()                              # nothing was kept (or nothing came in): padding / zeros only
+    rb = _prod(hidden) * src.element_size()
+    args = (L.ptr(out), L.ptr(src)) if not expand else (L.ptr(src), L.ptr(out))
+    _call('compress_expand' if expand else 'compress_move', 'rua_segment_compress_move', dev, small.ref(), big.ref(),
+          L.ptr(rank), *args, rb, int(bool(expand)))
+    return out
+
+
+class _Compress(torch.autograd.Function):
+    """payload of `big` -> payload of `small`: linear, its adjoint is _Expand with the same rank table.  Saves ONLY
+    the int32 rank table (the mask is folded into it); no payload, no int64 index."""
+
+    @staticmethod
+    def forward(ctx, data: Tensor, rank: Tensor, small: M.Lay, big: M.Lay, hidden, small_shape, big_shape):
+        ctx.args = (small, big, tuple(hidden), tuple(small_shape), tuple(big_shape))
+        ctx.save_for_backward(rank)
+        return launch_compress_move(small, big, rank, data, hidden, small_shape, False)
+
+    @staticmethod
+    def backward(ctx, grad: Tensor):
+        rank, = ctx.saved_tensors
+        return (expand(grad, rank, *ctx.args),) + (None,) * 6
+
+
+class _Expand(torch.autograd.Function):
+    """payload of `small` -> payload of `big` with zeros at dropped tokens and padding: the adjoint of _Compress, and
+    _Compress is its adjoint — derivatives of every order from the one kernel."""
+
+    @staticmethod
+    def forward(ctx, data: Tensor, rank: Tensor, small: M.Lay, big: M.Lay, hidden, small_shape, big_shape):
+        ctx.args = (small, big, tuple(hidden), tuple(small_shape), tuple(big_shape))
+        ctx.save_for_backward(rank)
+        return launch_compress_move(small, big, rank, data, hidden, big_shape, True)
+
+    @staticmethod
+    def backward(ctx, grad: Tensor):
+        rank, = ctx.saved_tensors
+        return (compress(grad, rank, *ctx.args),) + (None,) * 6
+
+
+def compress(data: Tensor, rank: Tensor, small: M.Lay, big: M.Lay, hidden, small_shape, big_shape) -> Tensor:
+    L.require_device(data)
+    if data.is_floating_point() and data.requires_grad and torch.is_grad_enabled():
+        # contiguous HERE, before the Function (as in reduce()): a copy made inside forward() would carry no history
+        return _Compress.apply(data.contiguous(), rank, small, big, tuple(hidden), tuple(small_shape), tuple(big_shape))
+    return launch_compress_move(small, big, rank, _plain(data), tuple(hidden), tuple(small_shape), False)
+
+
+def expand(data: Tensor, rank: Tensor, small: M.Lay, big: M.Lay, hidden, small_shape, big_shape) -> Tensor:
+    L.require_device(data)
+    if data.is_floating_point() and data.requires_grad and torch.is_grad_enabled():
+        return _Expand.apply(data.contiguous(), rank, small, big, tuple(hidden), tuple(small_shape), tuple(big_shape))
+    return launch_compress_move(small, big, rank, _plain(data), tuple(hidden), tuple(big_shape), True)
 
 
 # ------------------------------------------------------------------ per-sequence argmax / argmin (an extension)

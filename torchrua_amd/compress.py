@@ -1,0 +1,136 @@
+"""Per-sequence compress over any container (C / L / P / R) — an extension, and the first operator of the family that
+changes the raggedness FROM THE DATA: keep the tokens where a mask is true and return the ragged batch that remains.
+
+    z.compress(mask)       the same container type, the same number of sequences B; sequence b holds exactly the
+                           tokens t of z with mask[b, t] true, in their order.  A sequence may become empty; all may.
+
+`head` / `last` / `trunc` / `roll` pick tokens by closed-form positions only.  This is the data-dependent selection:
+dropping special or sub-word continuation tokens, CTC blanks and repeats after an `argmax`, pruned tokens, the prompt
+of prompt+response episodes, masked-out frames before pooling.  With the reference the spelling leaves the library —
+`data[mask]` (ATen nonzero + index), a `segment_sum(mask)` for the new lengths and a new constructor — for a
+CattedSequence only; an L / R needs hand-rolled index arithmetic and its padding masked out by hand, a PackedSequence
+gets nothing (the sort order of the result changes), and autograd keeps an int64 index per kept token.
+
+`mask` is a `torch.bool` tensor on the payload's device in the container's STORAGE layout of the token dimensions —
+[N] for C / P, [B, T_phys] for L / R — or a container of the same type whose `.data` is that tensor.  One value per
+token: a mask with hidden dimensions is refused.  Mask values in padding rows of an L / R are ignored, so an all-true
+[B, T] mask is the identity.  The mask is not differentiable.
+
+The payload moves as BITS: every dtype of element size 1 / 2 / 4 / 8 (int64 token ids and bool included), 1-D payloads
+and any hidden shape, any row width and alignment; a NaN keeps its bits.
+
+The result is defined by commutation.  For a C the data is the kept rows in storage order and `token_sizes` the new
+lengths (int64).  For every other layout X, `z.compress(m)` equals `z.cat().compress(m_as_cat).X()` field by field and
+bit for bit, where `m_as_cat` is the mask cast like the data: for a P that covers data, batch_sizes, sorted_indices and
+unsorted_indices (empty sequences included, exactly as `C.pack()` treats them), for an L / R the new T (the longest
+new sequence) and zero padding rows.  `z.compress(m).cat()` equals `z.cat().compress(m_as_cat)` likewise.
+
+Two HIP kernels (csrc/rua_compress.hip), identical for the four layouts.  The plan counts the mask per sequence —
+64-bit ballots and popcounts — into an int32 rank per storage row (the position the token takes in its new sequence;
+-1 for dropped tokens and padding) and the new lengths.  The move copies every kept row to the row of token (b, rank)
+of the result, whatever the result's kind; padding rows of an L / R result are written as zeros by the same launch.
+The result's offsets and PackedSequence metadata come from the library's existing scan / host-sort path over the new
+lengths.
+
+SYNCHRONISATION.  The new lengths decide the allocation (N', T', and for a P the host sort), so every call reads them
+back: ONE blocking copy of [B] int64, as `torch.masked_select` and `data[mask]` synchronise too.  The host copy is
+attached to the result's lengths, so a following `pack()` / `left()` / `size()` reads nothing back again.  (A variant
+with a caller-given capacity that never synchronises is the natural follow-up; it is not built.)
+
+Autograd: `compress` and its adjoint `expand` (kept rows back to their places, true zeros elsewhere) are two Functions
+that are each other's backward, so derivatives of every order exist.  Only the int32 rank table is saved — no payload,
+no int64 index, not the mask.  Gradients of dropped tokens and of padding rows are exact zeros, whatever the payload
+holds there (NaN, inf).  Integer and bool payloads pass through without a graph.
+
+Out of scope: selection by index lists or top-k, per-column masks, a fused `unique_consecutive` / CTC collapse (that is
+a mask built with `roll` and `!=`), returning the dropped tokens as well.
+"""
+from typing import Tuple
+
+import torch
+from torch import Tensor
+
+from torchrua_amd import _lib as K
+from torchrua_amd import _meta as M
+from torchrua_amd import _ops as O
+from torchrua_amd.core import _pack_meta
+from torchrua_amd.layout import C, L, P, R, T, Z, cat_lay, lay_hidden
+
+__all__ = ['segment_compress', 'compress']
+
+
+def _check_mask(mask, lead_shape: Tuple[int, ...], data: Tensor, what: str) -> Tensor:
+    """The mask as a tensor, after the checks that need no device: bool, one value per token in the storage layout of
+    the token dimensions, on the payload's device."""
+    if not isinstance(mask, Tensor):
+        raise K.RuaError(f'{what}: the mask is a torch.bool tensor (or a container of the same type holding one); got '
+                         f'{type(mask).__name__}')
+    if mask.dtype != torch.bool:
+        raise K.RuaError(f'{what}: the mask has dtype {mask.dtype}; it must be torch.bool')
+    lead_shape = tuple(lead_shape)
+    if mask.dim() > len(lead_shape) and tuple(mask.shape[:len(lead_shape)]) == lead_shape:
+        raise K.RuaError(f'{what}: the mask has shape {tuple(mask.shape)}: hidden dimensions — it holds ONE value per '
+                         f'token, shape {lead_shape}')
+    if tuple(mask.shape) != lead_shape:
+        raise K.RuaError(f'{what}: the mask has shape {tuple(mask.shape)}; the token dimensions of the storage are '
+                         f'{lead_shape}')
+    if mask.device != data.device:
+        raise K.RuaError(f'{what}: the mask lives on {mask.device}, the payload on {data.device}')
+    return mask
+
+
+def _new_lengths(big: M.Lay, mask: Tensor) -> Tuple[Tensor, Tensor]:
+    """(rank, new lengths) of the plan, the lengths with their host copy attached: the call's ONE read-back."""
+    rank, new_sizes = O.launch_compress_plan(big, mask)
+    M.attach_host(new_sizes, M._read_back(new_sizes))
+    return rank, new_sizes
+
+
+def segment_compress(tensor: T, mask: T, segment_sizes: T) -> Tuple[T, T]:
+    """The rows of `tensor` [N, *hidden] where `mask` [N] is true, and how many every run of `segment_sizes` rows keeps
+    (the argument order of segment_cumsum, plus the mask): (tensor [N', *hidden], new_sizes [S] int64)."""
+    mask = _check_mask(mask, tuple(tensor.shape[:1]), tensor, 'segment_compress')
+    K.require_device(tensor, mask, segment_sizes)
+    big, hidden = cat_lay(tensor, segment_sizes), tuple(tensor.shape[1:])
+    rank, new_sizes = _new_lengths(big, mask)
+    n = M.total_len(new_sizes)
+    small = M.lay_cat(new_sizes, big.B, n)
+    return O.compress(tensor, rank, small, big, hidden, (n,) + hidden, tuple(tensor.shape)), new_sizes
+
+
+def compress(sequence: Z, mask) -> Z:
+    """Keep the tokens where `mask` is true; the same container type and number of sequences.  See the module
+    docstring."""
+    data = sequence.data
+    if isinstance(mask, (C, L, P, R)):
+        if type(mask) is not type(sequence):
+            raise K.RuaError(f'compress: a mask given as a container must be a {type(sequence).__name__}; got '
+                             f'{type(mask).__name__}')
+        mask = mask.data
+    lead = 1 if isinstance(sequence, (C, P)) else 2
+    mask = _check_mask(mask, tuple(data.shape[:lead]), data, 'compress')
+    big, hidden = lay_hidden(sequence)
+    dev = data.device
+    rank, new_sizes = _new_lengths(big, mask)
+    B = big.B
+    if isinstance(sequence, C):
+        n = M.total_len(new_sizes)
+        small, shape = M.lay_cat(new_sizes, B, n), (n,) + hidden
+        return C(data=O.compress(data, rank, small, big, hidden, shape, tuple(data.shape)), token_sizes=new_sizes)
+    if isinstance(sequence, P):
+        # the metadata C.pack() derives from these lengths: the reference's host sort, batch_sizes, the device scans
+        lens, sorted_indices, unsorted, batch_sizes, bsz_dev, boff = _pack_meta(new_sizes, dev)
+        n = M.total_len(new_sizes)
+        shell = P(data=data, batch_sizes=batch_sizes, sorted_indices=sorted_indices, unsorted_indices=unsorted)
+        M.adopt_pack(shell, lens, boff, bsz_dev)
+        small = M.lay_pack(shell, lens=lens, boff=boff, T=batch_sizes.numel(), n_rows=n)
+        return shell._replace(data=O.compress(data, rank, small, big, hidden, (n,) + hidden, tuple(data.shape)))
+    kind = K.LEFT if isinstance(sequence, L) else K.RIGHT
+    t = M.max_len(new_sizes)
+    small, shape = M.lay_padded(kind, new_sizes, B, t, t), (B, t) + hidden
+    return type(sequence)(data=O.compress(data, rank, small, big, hidden, shape, tuple(data.shape)),
+                          token_sizes=new_sizes)
+
+
+for _cls in (C, L, P, R):
+    _cls.compress = compress
