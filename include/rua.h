@@ -665,6 +665,63 @@ int rua_segment_compress_plan(const rua_layout* lay, const void* mask, int32_t* 
 int rua_segment_compress_move(const rua_layout* small, const rua_layout* big, const int32_t* rank, void* small_data,
                               void* big_data, int64_t row_bytes, int32_t expand, void* stream);
 
+/* Per-sequence join and unjoin — concatenate ragged batches along time, and cut one at per-sequence boundaries (an
+ * EXTENSION, added to ABI 6 — the version number did not move: the reference's users loop over B pairs with torch.cat,
+ * or gather through an index built with repeat_interleave, and call a constructor again; for a CattedSequence only).
+ * n_parts (1 .. RUA_JOIN_MAX_PARTS) parts with the same B: sequence b of the JOINED side is sequence b of part 0, then
+ * of part 1, ... in order.  With len_k[b] the length of part k clamped to its storage and pre_k[b] = sum_{i<k} len_i[b]:
+ *   token (b, u) of the joined side  <->  token (b, u - pre_k[b]) of part k,   pre_k[b] <= u < pre_(k+1)[b]
+ * — a closed form per token: there is no per-token table of any kind (no rank, no index, no workspace).  `part_lays` is
+ * an ARRAY of n_parts layouts of ANY kinds.  One token per sequence (a [B, *hidden] tensor: a BOS embedding, a
+ * conditioning vector) is the LEFT layout with T_phys = 1, lens = NULL, len_add = 1.  Nothing here synchronises.
+ * rua_segment_join_lens: out_lens[b] = sum_k len_k[b] ([B] int64, one thread per sequence, one launch); part_lens, if
+ *   given ([n_parts, B]), receives the length of every part as its layout GIVES it (lens[b] + len_add, unclamped) —
+ *   what a caller that has to read the sums back reads back with them.  A RIGHT part whose T_log the caller does not
+ *   know yet may be described with T_log = T_phys here: only the clamp reads it.
+ * rua_segment_unjoin_lens: the lengths of the parts an unjoin of `joined` cuts.  wanted_k[b] = (sizes[k] ? sizes[k][b] :
+ *   0) + size_add[k] (`sizes` and `size_add` are HOST arrays of n_parts entries; sizes[k] a device [B] int64 or NULL),
+ *   out_lens[k * B + b] = min(max(wanted_k[b], 0), len[b] - pre_k[b]): a part that would run past the end of its
+ *   sequence is clamped to it, tokens beyond the last part are dropped.  own_lens, if given ([B]), receives the length
+ *   of every sequence as `joined` GIVES it (unclamped): what a caller that has to read the parts' lengths back reads
+ *   back with them; a RIGHT `joined` whose T_log the caller does not know yet may be described with T_log = T_phys here.
+ * rua_segment_join: rows are row_bytes wide on every side and move as BITS.
+ *   unjoin == 0: every storage row of `joined` is written exactly once — its tokens from their parts (a token no part
+ *                holds: zeros), the padding rows of a LEFT / RIGHT `joined` as zeros in the same launch (no pre-zeroing).
+ *                A CAT `joined` whose storage holds more rows than its lengths add up to (a caller that sizes it by
+ *                the parts' storages without reading the lengths back) gets the spare rows behind its last sequence
+ *                as zeros too.  Padding rows of the parts are never read.  Every payload byte is read once and
+ *                written once.
+ *   unjoin != 0: the adjoint, and the inverse.  Token (b, t) of part k reads token (b, pre_k[b] + t) of `joined` (zeros
+ *                if `joined` does not hold it); every part's LEFT / RIGHT padding rows are written as zeros: every
+ *                part is written completely, in ONE launch for all parts.  Tokens of `joined` beyond the parts are not
+ *                read.  The parts' lengths are those of their layouts (rua_segment_unjoin_lens's, or any others).
+ * ONE kernel, walked by the sequences of `joined`; a thread group owns WHOLE rows, 16 bytes per thread and step, four
+ * rows in flight, so the lengths, the (at most 8) prefixes and both row formulas are paid once per row.  Three forms:
+ * rows of at most 16 bytes put the tokens of a sequence on 32 lanes, two sequences per wave (`lanes`); wider rows whose
+ * longest joined sequence (the bound: CAT T_log or n_rows, LEFT / RIGHT T_phys, PACK T) times row_bytes is at most
+ * 16 KiB give a wave per sequence (`wave`); anything longer a workgroup per sequence (`rows`).  Few but long sequences
+ * (fewer than 1 024 with a bound of at least 8 192; narrow rows too) are cut into blocks of 2 048 tokens across
+ * workgroups: blocks need nothing of each other, so no workspace and no second launch.  A CAT `joined` layout's T_log,
+ * where given (> 0), must be a TRUE bound, as for rua_segment_softmax.  Accesses are the widest power of two, up to 16
+ * bytes, that divides row_bytes and every base address: any alignment is accepted.  Lengths are clamped to the storage
+ * and every row is range-checked.
+ * Checks, before any HIP call: a null or inconsistent layout, n_parts outside 1 .. 8, a null `part_lays` (`sizes`,
+ * `size_add`), a part of another B: RUA_EINVAL; B == 0 (and, for the move, row_bytes == 0 or a destination without
+ * rows) returns 0 without a launch; then a null output or a null payload where its layout has rows, the joined payload
+ * equal to a part's, two parts of an unjoin in one place, out_lens equal to part_lens / own_lens or either equal to a
+ * sizes[k]: RUA_EINVAL; a length vector that is not 8-byte aligned RUA_EALIGN.  The alias checks compare BASE POINTERS
+ * only, like the family's: buffers that overlap at another offset are the caller's to avoid (torchrua_amd always
+ * allocates its outputs afresh).  Sums and parts agree where the layouts are well formed — lengths within their
+ * storages; out_lens sums the CLAMPED lengths, part_lens / own_lens hold the lengths as given.  Trace: `seg_join_lens_kernel` / `seg_unjoin_lens_kernel` with
+ * parts= B=, and `seg_join_kernel form=lanes|wave|rows W= row_bytes= parts= unjoin= joined=<kind> G= cut= blocks=`. */
+#define RUA_JOIN_MAX_PARTS 8
+int rua_segment_join_lens(const rua_layout* part_lays, int32_t n_parts, int64_t* out_lens, int64_t* part_lens,
+                          void* stream);
+int rua_segment_unjoin_lens(const rua_layout* joined, const int64_t* const* sizes, const int64_t* size_add,
+                            int32_t n_parts, int64_t* out_lens, int64_t* own_lens, void* stream);
+int rua_segment_join(const rua_layout* joined, const rua_layout* part_lays, int32_t n_parts, void* joined_data,
+                     void* const* part_data, int64_t row_bytes, int32_t unjoin, void* stream);
+
 /* Per-sequence argmax / argmin with the selected values (an EXTENSION, added to ABI 6 — the version number did not
  * move: the reference has no position-returning reduction; its users pad with -inf and call torch.argmax along dim 1).
  * For every sequence b of `lay` (ANY layout) and column h, over t < len[b] (op = RUA_MAX or RUA_MIN, anything else:

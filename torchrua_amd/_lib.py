@@ -31,6 +31,7 @@ POOL_OUT_ACC = 0x100       # rua.h: RUA_POOL_OUT_ACC, OR-ed into the dtype of ru
 NORM_MEAN_ACC = 0x100      # rua.h: RUA_NORM_MEAN_ACC, OR-ed into the dtype of rua_segment_var_mean[_backward]
 OP_SHORT_SEQS = 0x400      # rua.h: a CattedSequence of short sequences, none far above the average (a hint)
 CONV_MAX_TAPS = 8          # rua.h: RUA_CONV_MAX_TAPS, the longest filter of rua_segment_causal_conv
+JOIN_MAX_PARTS = 8         # rua.h: RUA_JOIN_MAX_PARTS, the most parts of one rua_segment_join
 # enum rua_dtype / rua_op
 F32, BF16, F16, F64 = 0, 1, 2, 3
 SUM, MEAN, MAX, MIN, PROD, LOGSUMEXP = 0, 1, 2, 3, 4, 5
@@ -120,6 +121,11 @@ SYMBOLS = {
     'rua_segment_compress_plan': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'rua_segment_compress_move': (c_int, [POINTER(RuaLayout), POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_int64,
                                           c_int32, c_void_p]),
+    'rua_segment_join_lens': (c_int, [POINTER(RuaLayout), c_int32, c_void_p, c_void_p, c_void_p]),
+    'rua_segment_unjoin_lens': (c_int, [POINTER(RuaLayout), POINTER(c_void_p), POINTER(c_int64), c_int32, c_void_p,
+                                        c_void_p, c_void_p]),
+    'rua_segment_join': (c_int, [POINTER(RuaLayout), POINTER(RuaLayout), c_int32, c_void_p, POINTER(c_void_p), c_int64,
+                                 c_int32, c_void_p]),
     'rua_argreduce_ws_bytes': (c_int64, [POINTER(RuaLayout), c_int64, c_int32]),
     'rua_segment_argreduce': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p,
                                       c_void_p]),

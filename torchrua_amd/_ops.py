@@ -4,6 +4,7 @@ Backward of a move is the adjoint move (layouts swapped, token map inverted, zer
 nothing maps to) — the same kernel.  Backward of a segmented reduce is one fused kernel
 (rua_segment_reduce_backward), which also serves scatter_* through the bucket indirection.
 """
+import ctypes
 import threading
 from typing import Callable, Optional, Sequence, Tuple
 
@@ -1160,6 +1161,114 @@ def expand(data: Tensor, rank: Tensor, small: M.Lay, big: M.Lay, hidden, small_s
     if data.is_floating_point() and data.requires_grad and torch.is_grad_enabled():
         return _Expand.apply(data.contiguous(), rank, small, big, tuple(hidden), tuple(small_shape), tuple(big_shape))
     return launch_compress_move(small, big, rank, _plain(data), tuple(hidden), tuple(big_shape), True)
+
+
+# ------------------------------------------------------------------ per-sequence join / unjoin along time (an extension)
+class JoinPlan:
+    """Everything one rua_segment_join launch needs except the payloads: the layout and storage shape of the JOINED side
+    and of every part (the layouts keep their length vectors alive).  This is all the autograd Functions hold."""
+    __slots__ = ('joined', 'parts', 'hidden', 'joined_shape', 'part_shapes')
+
+    def __init__(self, joined: M.Lay, parts: Sequence[M.Lay], hidden, joined_shape, part_shapes):
+        self.joined, self.parts, self.hidden = joined, tuple(parts), tuple(hidden)
+        self.joined_shape, self.part_shapes = tuple(joined_shape), tuple(tuple(s) for s in part_shapes)
+
+
+def _lay_array(lays: Sequence[M.Lay]):
+    """`lays` as the contiguous array of rua_layout the join entry points take (copies of the structs)."""
+    return (L.RuaLayout * len(lays))(*[lay.c for lay in lays])
+
+
+def launch_join_lens(lays: Sequence[M.Lay], dev, want_parts: bool = False) -> Tensor:
+    """rua_segment_join_lens: row 0 of the result is the summed (clamped) length of every sequence over the parts; with
+    want_parts the rows 1 .. n are the parts' own lengths — one buffer, so that a caller who has to read the sums back
+    reads everything in one copy.  One small launch, no ATen kernel."""
+    n, B = len(lays), lays[0].B
+    out = torch.empty((n + 1 if want_parts else 1, B), dtype=torch.long, device=dev)
+    if B:
+        _call('join_lens', 'rua_segment_join_lens', dev, _lay_array(lays), n, L.ptr(out),
+              out.data_ptr() + 8 * B if want_parts else None)
+    return out
+
+
+def launch_unjoin_lens(joined: M.Lay, sizes: Sequence, dev, want_own: bool = False) -> Tensor:
+    """rua_segment_unjoin_lens: [n, B] — row k holds the length of part k of every sequence: what `sizes[k]` (a device
+    [B] int64 tensor, or an int for every sequence) asks for, clamped to what the parts before left of the sequence.
+    With want_own a row n follows: the container's own lengths — one buffer, one copy for a caller who reads back."""
+    n, B = len(sizes), joined.B
+    out = torch.empty((n + 1 if want_own else n, B), dtype=torch.long, device=dev)
+    ptrs = (ctypes.c_void_p * n)(*[L.ptr(s) if isinstance(s, Tensor) else None for s in sizes])
+    adds = (ctypes.c_int64 * n)(*[0 if isinstance(s, Tensor) else int(s) for s in sizes])
+    if B:
+        _call('unjoin_lens', 'rua_segment_unjoin_lens', dev, joined.ref(), ptrs, adds, n, L.ptr(out),
+              out.data_ptr() + 8 * n * B if want_own else None)
+    return out
+
+
+def launch_join(plan: JoinPlan, src, unjoin: bool):
+    """rua_segment_join.  unjoin=False: `src` is the parts' payloads, the result the joined payload; unjoin=True: `src`
+    is the joined payload, the result a tuple with every part's.  Rows move as bits; padding rows of every result are
+    zeros; ONE launch either way."""
+    srcs = [src] if unjoin else list(src)
+    dev = L.require_device(*srcs)
+    dtype = srcs[0].dtype
+    if srcs[0].element_size() not in (1, 2, 4, 8):
+        raise L.RuaError(f'join moves elements of 1, 2, 4 or 8 bytes; got {dtype}')
+    want = [plan.joined_shape] if unjoin else list(plan.part_shapes)
+    if len(srcs) != len(want) or any(s.dtype != dtype or s.numel() != _prod(w) for s, w in zip(srcs, want)):
+        raise L.RuaError('join: the payloads do not fit the plan (one per part, of one dtype, of the planned storage shapes)')
+    srcs = [s.contiguous() for s in srcs]
+    outs = [torch.empty(s, dtype=dtype, device=dev) for s in (plan.part_shapes if unjoin else [plan.joined_shape])]
+    joined_data, part_data = (srcs[0], outs) if unjoin else (outs[0], srcs)
+    n = len(plan.parts)
+    ptrs = (ctypes.c_void_p * n)(*[L.ptr(t) if t.numel() else None for t in part_data])
+    rb = _prod(plan.hidden) * srcs[0].element_size()
+    _call('unjoin' if unjoin else 'join', 'rua_segment_join', dev, plan.joined.ref(), _lay_array(plan.parts), n,
+          L.ptr(joined_data) if joined_data.numel() else None, ptrs, rb, int(bool(unjoin)))
+    return tuple(outs) if unjoin else outs[0]
+
+
+class _Join(torch.autograd.Function):
+    """payloads of the parts -> payload of the joined side: a permutation of rows plus zeros, linear; its adjoint is
+    _Unjoin with the same plan.  Holds ONLY the plan (length vectors and layout metadata): no payload, no index."""
+
+    @staticmethod
+    def forward(ctx, plan: JoinPlan, *datas: Tensor):
+        ctx.plan = plan
+        return launch_join(plan, datas, False)
+
+    @staticmethod
+    def backward(ctx, grad: Tensor):
+        return (None,) + tuple(unjoin(grad, ctx.plan))
+
+
+class _Unjoin(torch.autograd.Function):
+    """payload of the joined side -> payloads of the parts: the adjoint of _Join, and _Join is its adjoint (dropped
+    tokens and padding rows get exact zeros) — derivatives of every order from the one kernel."""
+
+    @staticmethod
+    def forward(ctx, plan: JoinPlan, data: Tensor):
+        ctx.plan = plan
+        return launch_join(plan, data, True)
+
+    @staticmethod
+    def backward(ctx, *grads: Tensor):
+        return None, join(grads, ctx.plan)
+
+
+def join(datas: Sequence[Tensor], plan: JoinPlan) -> Tensor:
+    L.require_device(*datas)
+    if torch.is_grad_enabled() and any(d.is_floating_point() and d.requires_grad for d in datas):
+        # contiguous HERE, before the Function (as in reduce()): a copy made inside forward() would carry no history
+        return _Join.apply(plan, *[d.contiguous() for d in datas])
+    return launch_join(plan, [_plain(d) for d in datas], False)
+
+
+def unjoin(data: Tensor, plan: JoinPlan) -> Tuple[Tensor, ...]:
+    L.require_device(data)
+    if data.is_floating_point() and data.requires_grad and torch.is_grad_enabled():
+        return _Unjoin.apply(plan, data.contiguous())
+    return launch_join(plan, _plain(data), True)
 
 
 # ------------------------------------------------------------------ per-sequence argmax / argmin (an extension)
