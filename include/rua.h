@@ -722,6 +722,83 @@ int rua_segment_unjoin_lens(const rua_layout* joined, const int64_t* const* size
 int rua_segment_join(const rua_layout* joined, const rua_layout* part_lays, int32_t n_parts, void* joined_data,
                      void* const* part_data, int64_t row_bytes, int32_t unjoin, void* stream);
 
+/* Per-sequence repeat_interleave — every token counts[b, t] times inside its own sequence (an EXTENSION, added to ABI 6
+ * — the version number did not move: the reference's users spell it as torch.repeat_interleave(data, counts, dim=0), a
+ * segment_sum of the counts and a new constructor, for a CattedSequence only, or as a gather through an int64 index).
+ * The inverse direction of compress: the result's raggedness GROWS from the data.  Sequence b of the result is
+ * repeat_interleave(sequence b of the input, its counts); a count may be 0.  Three entry points; the caller reads the
+ * new lengths back between the first two (ONE read-back of [B + 1] int64; nothing here synchronises).
+ * rua_segment_repeat_plan (replaces segment_sum(counts) and the cumsum of torch.repeat_interleave): `counts` and `first`
+ * hold one int64 per STORAGE ROW of `lay` (ANY layout; n_rows entries).  A count below 0 or above 2^31 - 1 is INVALID: it
+ * is counted and taken as 0.  Writes
+ *   first[j]        = the sum of the valid counts of the tokens s < t of sequence b, for the row j of token (b, t): the
+ *                     position of the token's first copy in its new sequence; -1 for a padding row of a LEFT / RIGHT
+ *                     storage (whose counts are never read);
+ *   new_lens[b]     = the sum of the valid counts of sequence b (b < B);
+ *   new_lens[B]     = the number of invalid counts (the entry point zeroes the word on the stream, lanes that met one
+ *                     add to it with a vector atomic): new_lens has B + 1 entries, so the one read-back carries it.
+ * Integer work: every form gives the same bits.  Four forms by the length bound (CAT: T_log or n_rows, LEFT / RIGHT:
+ * T_phys, PACK: T), as for rua_segment_compress_plan: up to 64, two sequences per wave, 32 lanes each; below 2 048, a
+ * wave per sequence; longer, a workgroup per sequence with the sum carried from step to step — in all three the sum in
+ * front of a lane is a shuffle scan; few but long sequences (fewer than 1 024 of them with a bound of at least 8 192)
+ * are cut into blocks of 2 048 tokens across workgroups when `ws` is given: the first launch leaves every block's sum
+ * in `ws`, the second adds the sums of the blocks before a block in block order.  rua_repeat_ws_bytes(lay) =
+ *   B * ceil(bound / 2 048) * 8
+ * bytes when the cut form applies, else 0 (0 = never needed; ws == NULL = do not cut).  Lengths are clamped to the
+ * storage and every row is range-checked.
+ * Checks, before any HIP call: a null or inconsistent layout RUA_EINVAL (rua_repeat_ws_bytes: 0); B == 0 returns 0
+ * without a launch; then a null counts / first (with n_rows > 0) / new_lens, or outputs that alias each other or the
+ * counts, RUA_EINVAL; a pointer that is not 8-byte aligned RUA_EALIGN.  Trace: `seg_repeat_plan_kernel form=lanes|rows|
+ * long|cut G= kind= cut= blocks= phase=whole|sum|finish`.
+ * rua_segment_repeat_move (replaces torch.repeat_interleave(data, counts, dim=0) / the gather): DESTINATION-driven.
+ * `src` is the input's layout, `dst` the result's (any two kinds, the same B; dst's lengths are new_lens, its offsets /
+ * PackedSequence metadata the caller's); rows are row_bytes wide on both sides and move as BITS.  The row of every token
+ * (b, u) of dst receives the row of source token t:
+ *   first != NULL: the largest t < len_src[b] with first[row_src(b, t)] <= u.  `first` is non-decreasing over t and tokens
+ *                  that share a value all have count 0 except the last of them, so that t is the token whose run
+ *                  [first, first + count) holds u — with zero counts anywhere, leading and trailing included;
+ *   first == NULL: t = u / uniform (every token `uniform` times; uniform == 0: dst holds no token).
+ * A token of dst that no source token answers for (layouts that do not belong together) is written as zeros; padding
+ * rows of a LEFT / RIGHT dst are written as zeros in the same launch (no pre-zeroing).  One kernel: a workgroup per
+ * (sequence of dst, 128-byte column chunk) walks the sequence in blocks of 2 048 destination tokens; few but long
+ * destination sequences (the cut rule over B * chunks units of dst) spread their blocks over workgroups — no workspace,
+ * no second launch.  Per block the source tokens it covers are found ONCE (two searches of the sequence's `first`
+ * entries — strided rows for a PACK src), their entries are staged in LDS as offsets from the block's start (up to
+ * 2 048 of them; a block that covers more — long stretches of zero counts — searches the table itself) and every
+ * destination token searches there.  32 tokens x 8 pieces of 16 bytes per step for rows wider than 16 bytes (`form=
+ * rows`), a token per thread for rows of one vector (`form=lanes`); four tokens in flight per thread.  The copies of
+ * a long run are different destination tokens, so they spread over the threads of the workgroup that owns their block
+ * (256 at most) and, when the destination is cut, over the workgroups of its blocks; WITHOUT the cut — the ordinary batch
+ * of 1 024 or more (sequence x chunk) units — one workgroup per chunk walks a whole destination sequence block after
+ * block, a count of 100 000 among short sequences included: correct, and slow (the skew limit of DESIGN 3.2j).
+ * Accesses are the widest power of two, up to 16 bytes, that divides row_bytes and both base addresses: any alignment is
+ * accepted.  Every row index is range-checked on both sides.
+ * Checks: the layout checks for `src`, then for `dst`; different B, or first == NULL with uniform < 0, RUA_EINVAL; B == 0,
+ * row_bytes == 0 or a destination without rows return 0; a null payload, or dst_data == src_data, RUA_EINVAL.  Trace:
+ * `seg_repeat_move_kernel form=rows|lanes W= row_bytes= table= dst= src= cut= blocks= chunks=`.
+ * rua_segment_repeat_sum (replaces the index_add / segment_sum of the stock backward): the adjoint, SOURCE-driven.
+ *   grad_src[row_src(b, t)] = sum over u in [first, first + count) of grad_dst[row_dst(b, u)]
+ * (first == NULL: first = t * uniform, count = uniform; an invalid count is 0, a run is clamped to dst's length).  The
+ * sum runs in ascending u in fp32 (fp64 for RUA_F64) and is rounded once: ONE fold order per (token, column) whatever
+ * the two layouts are, so it commutes with the casts bit for bit and is the same from run to run.  dtype is RUA_F32 /
+ * RUA_F64 / RUA_BF16 / RUA_F16 (anything else: RUA_EINVAL).  A token with count 0 and every padding row of a LEFT / RIGHT
+ * src receive exact zeros whatever grad_dst holds around them.  No float atomics, no workspace.  A workgroup per
+ * (sequence of src, 128-byte column chunk[, block of 2 048 source tokens: the cut rule over src]); a run is walked by
+ * ONE thread group (the eight threads of its row chunk): correct for any count, SLOW for a very long one — a count of
+ * 100 000 is 100 000 dependent steps of one group.  Splitting runs is not built.  16-byte accesses where H * esize and
+ * both bases allow (`vec=1`), else element by element.  Checks as for the move, plus: a table without counts, or
+ * grad_src equal to grad_dst / first / counts, RUA_EINVAL.  Trace: `seg_repeat_sum_kernel form= dtype= H= vec= table=
+ * src= dst= cut= blocks= chunks=`.
+ * (A variant with a caller-given capacity that never reads the lengths back is the follow-up compress names too.) */
+int64_t rua_repeat_ws_bytes(const rua_layout* lay);
+int rua_segment_repeat_plan(const rua_layout* lay, const int64_t* counts, int64_t* first, int64_t* new_lens /* B + 1 */,
+                            void* ws, void* stream);
+int rua_segment_repeat_move(const rua_layout* dst, const rua_layout* src, const int64_t* first /* NULL: uniform */,
+                            int64_t uniform, void* dst_data, const void* src_data, int64_t row_bytes, void* stream);
+int rua_segment_repeat_sum(const rua_layout* src, const rua_layout* dst, const int64_t* first /* NULL: uniform */,
+                           const int64_t* counts, int64_t uniform, void* grad_src, const void* grad_dst, int64_t H,
+                           int32_t dtype, void* stream);
+
 /* Per-sequence argmax / argmin with the selected values (an EXTENSION, added to ABI 6 — the version number did not
  * move: the reference has no position-returning reduction; its users pad with -inf and call torch.argmax along dim 1).
  * For every sequence b of `lay` (ANY layout) and column h, over t < len[b] (op = RUA_MAX or RUA_MIN, anything else:

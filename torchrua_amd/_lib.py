@@ -126,6 +126,12 @@ SYMBOLS = {
                                         c_void_p, c_void_p]),
     'rua_segment_join': (c_int, [POINTER(RuaLayout), POINTER(RuaLayout), c_int32, c_void_p, POINTER(c_void_p), c_int64,
                                  c_int32, c_void_p]),
+    'rua_repeat_ws_bytes': (c_int64, [POINTER(RuaLayout)]),
+    'rua_segment_repeat_plan': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'rua_segment_repeat_move': (c_int, [POINTER(RuaLayout), POINTER(RuaLayout), c_void_p, c_int64, c_void_p, c_void_p,
+                                        c_int64, c_void_p]),
+    'rua_segment_repeat_sum': (c_int, [POINTER(RuaLayout), POINTER(RuaLayout), c_void_p, c_void_p, c_int64, c_void_p,
+                                       c_void_p, c_int64, c_int32, c_void_p]),
     'rua_argreduce_ws_bytes': (c_int64, [POINTER(RuaLayout), c_int64, c_int32]),
     'rua_segment_argreduce': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p,
                                       c_void_p]),

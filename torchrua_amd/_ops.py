@@ -1163,6 +1163,143 @@ def expand(data: Tensor, rank: Tensor, small: M.Lay, big: M.Lay, hidden, small_s
     return launch_compress_move(small, big, rank, _plain(data), tuple(hidden), tuple(big_shape), True)
 
 
+# ------------------------------------------------------------------ per-sequence repeat_interleave (an extension)
+def launch_repeat_plan(lay: M.Lay, counts: Tensor, cut: bool = True) -> Tuple[Tensor, Tensor]:
+    """rua_segment_repeat_plan: (first int64 [storage rows of `lay`], new_lens int64 [B + 1]) from int64 counts with one
+    value per storage row — one launch (two for cut sequences); the counts are read once.  first is the position of a
+    token's first copy in its new sequence, -1 for a padding row; new_lens[B] is the number of invalid counts (negative or
+    above 2^31 - 1; taken as 0).  cut=False withholds the workspace (the same bits from one workgroup per sequence)."""
+    dev = L.require_device(counts)
+    if counts.dtype != torch.int64 or counts.numel() != lay.n_rows:
+        raise L.RuaError(f'repeat plan: the counts are a torch.int64 tensor with one value per storage row ({lay.n_rows}); '
+                         f'got {counts.dtype} with {counts.numel()} values')
+    counts = _plain(counts).contiguous()
+    first = torch.empty(lay.n_rows, dtype=torch.int64, device=dev)
+    if lay.B == 0:
+        return first.fill_(-1), torch.zeros(1, dtype=torch.int64, device=dev)     # (the entry point returns without a launch)
+    new_lens = torch.empty(lay.B + 1, dtype=torch.int64, device=dev)
+    ws = _workspace('rua_repeat_ws_bytes', lay, None, None, dev, cut)
+    _call('repeat_plan', 'rua_segment_repeat_plan', dev, lay.ref(), L.ptr(counts), L.ptr(first), L.ptr(new_lens),
+          L.ptr(ws))
+    return first, new_lens
+
+
+def _repeat_table(first: Optional[Tensor], counts: Optional[Tensor], src: M.Lay, what: str) -> None:
+    for t, name in ((first, 'first'), (counts, 'counts')):
+        if t is not None and (t.dtype != torch.int64 or t.numel() != src.n_rows or not t.is_contiguous()):
+            raise L.RuaError(f'{what}: `{name}` is a contiguous int64 tensor with one entry per storage row of the source')
+
+
+def launch_repeat_move(dst: M.Lay, src: M.Lay, first: Optional[Tensor], uniform: int, data: Tensor,
+                       hidden: Tuple[int, ...], out_shape: Sequence[int], out: Optional[Tensor] = None) -> Tensor:
+    """rua_segment_repeat_move: the row of every token (b, u) of a new payload of `dst` receives the bits of the source
+    token whose run holds u — found in `first`, or u // uniform when first is None.  Padding rows of a padded result are
+    zeros; one launch."""
+    dev = L.require_device(data, first)
+    if data.element_size() not in (1, 2, 4, 8):
+        raise L.RuaError(f'repeat_interleave moves elements of 1, 2, 4 or 8 bytes; got {data.dtype}')
+    _repeat_table(first, None, src, 'repeat move')
+    if data.numel() != src.n_rows * _prod(hidden):
+        raise L.RuaError(f'repeat move: the payload has {data.numel()} elements, the source layout {src.n_rows} rows of '
+                         f'{_prod(hidden)}')
+    data = data.contiguous()
+    out = _target(out, out_shape, data.dtype, dev, 'repeat_interleave' + _LIKE_PAYLOAD)
+    if out.numel() != dst.n_rows * _prod(hidden):
+        raise L.RuaError(f'repeat move: the result has {out.numel()} elements, its layout {dst.n_rows} rows of '
+                         f'{_prod(hidden)}')
+    if out.numel() == 0:
+        return out
+    if data.numel() == 0:
+        return out.zero_()
+    rb = _prod(hidden) * data.element_size()
+    _call('repeat_move', 'rua_segment_repeat_move', dev, dst.ref(), src.ref(), L.ptr(first), int(uniform), L.ptr(out),
+          L.ptr(data), rb)
+    return out
+
+
+def launch_repeat_sum(src: M.Lay, dst: M.Lay, first: Optional[Tensor], counts: Optional[Tensor], uniform: int,
+                      grad: Tensor, hidden: Tuple[int, ...], src_shape: Sequence[int],
+                      out: Optional[Tensor] = None) -> Tensor:
+    """rua_segment_repeat_sum, the adjoint of the move: every token of a new payload of `src` receives the sum of the
+    rows of its run in `grad` (storage of `dst`), in ascending order, accumulated in fp32 (fp64) and rounded once; tokens
+    with count 0 and padding rows are zeros.  One launch, no atomics."""
+    dev = L.require_device(grad, first, counts)
+    code = _require_dtype(grad, L.DTYPES, 'repeat_interleave sums')
+    _repeat_table(first, counts, src, 'repeat sum')
+    if (first is None) != (counts is None):
+        raise L.RuaError('repeat sum: `first` and `counts` come together')
+    if grad.numel() != dst.n_rows * _prod(hidden) or _prod(src_shape) != src.n_rows * _prod(hidden):
+        raise L.RuaError(f'repeat sum: the gradient has {grad.numel()} elements, the layout it belongs to {dst.n_rows} '
+                         f'rows of {_prod(hidden)}')
+    grad = grad.contiguous()
+    out = _target(out, src_shape, grad.dtype, dev, 'repeat_interleave' + _LIKE_PAYLOAD)
+    if out.numel() == 0:
+        return out
+    if grad.numel() == 0:
+        return out.zero_()                              # every count was 0
+    _call('repeat_sum', 'rua_segment_repeat_sum', dev, src.ref(), dst.ref(), L.ptr(first), L.ptr(counts), int(uniform),
+          L.ptr(out), L.ptr(grad), _prod(hidden), code)
+    return out
+
+
+class _Repeat(torch.autograd.Function):
+    """payload of `src` -> payload of `dst`, every token `count` times: linear, its adjoint is _RunSum with the same
+    table.  Saves ONLY `first` and the caller's counts (nothing at all for an int count): no payload, no index per
+    output token."""
+
+    @staticmethod
+    def forward(ctx, data: Tensor, first: Optional[Tensor], counts: Optional[Tensor], uniform: int, dst: M.Lay,
+                src: M.Lay, hidden, dst_shape, src_shape):
+        ctx.args = (int(uniform), dst, src, tuple(hidden), tuple(dst_shape), tuple(src_shape))
+        ctx.table = first is not None
+        if ctx.table:
+            ctx.save_for_backward(first, counts)
+        return launch_repeat_move(dst, src, first, uniform, data, hidden, dst_shape)
+
+    @staticmethod
+    def backward(ctx, grad: Tensor):
+        first, counts = ctx.saved_tensors if ctx.table else (None, None)
+        return (run_sum(grad, first, counts, *ctx.args),) + (None,) * 8
+
+
+class _RunSum(torch.autograd.Function):
+    """payload of `dst` -> payload of `src`, every token the sum of its run: the adjoint of _Repeat, and _Repeat is its
+    adjoint — derivatives of every order from the two kernels."""
+
+    @staticmethod
+    def forward(ctx, grad: Tensor, first: Optional[Tensor], counts: Optional[Tensor], uniform: int, dst: M.Lay,
+                src: M.Lay, hidden, dst_shape, src_shape):
+        ctx.args = (int(uniform), dst, src, tuple(hidden), tuple(dst_shape), tuple(src_shape))
+        ctx.table = first is not None
+        if ctx.table:
+            ctx.save_for_backward(first, counts)
+        return launch_repeat_sum(src, dst, first, counts, uniform, grad, hidden, src_shape)
+
+    @staticmethod
+    def backward(ctx, grad: Tensor):
+        first, counts = ctx.saved_tensors if ctx.table else (None, None)
+        return (repeat(grad, first, counts, *ctx.args),) + (None,) * 8
+
+
+def repeat(data: Tensor, first: Optional[Tensor], counts: Optional[Tensor], uniform: int, dst: M.Lay, src: M.Lay, hidden,
+           dst_shape, src_shape) -> Tensor:
+    L.require_device(data)
+    if data.is_floating_point() and data.requires_grad and torch.is_grad_enabled():
+        # contiguous HERE, before the Function (as in compress()): a copy made inside forward() would carry no history
+        return _Repeat.apply(data.contiguous(), first, counts, int(uniform), dst, src, tuple(hidden), tuple(dst_shape),
+                             tuple(src_shape))
+    return launch_repeat_move(dst, src, first, int(uniform), _plain(data), tuple(hidden), tuple(dst_shape))
+
+
+def run_sum(grad: Tensor, first: Optional[Tensor], counts: Optional[Tensor], uniform: int, dst: M.Lay, src: M.Lay, hidden,
+            dst_shape, src_shape) -> Tensor:
+    L.require_device(grad)
+    if grad.is_floating_point() and grad.requires_grad and torch.is_grad_enabled():
+        return _RunSum.apply(grad.contiguous(), first, counts, int(uniform), dst, src, tuple(hidden), tuple(dst_shape),
+                             tuple(src_shape))
+    return launch_repeat_sum(src, dst, first, counts, int(uniform), _plain(grad), tuple(hidden), tuple(src_shape))
+
+
 # ------------------------------------------------------------------ per-sequence join / unjoin along time (an extension)
 class JoinPlan:
     """Everything one rua_segment_join launch needs except the payloads: the layout and storage shape of the JOINED side

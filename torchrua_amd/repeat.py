@@ -1,0 +1,192 @@
+"""Per-sequence repeat_interleave over any container (C / L / P / R) — an extension, and the inverse direction of
+`compress`: the ragged batch GROWS from the data.
+
+    z.repeat_interleave(repeats)    the same container type, the same number of sequences B; sequence b is
+                                    torch.repeat_interleave(seq_b, repeats_b, dim=0).  A count may be 0, so a sequence
+                                    may become empty; all may.
+
+This is the length regulator of duration-based TTS (FastSpeech), the upsampling of frame-level features to sample level,
+a token -> sub-word alignment turned back into sub-word positions, the un-pooling after `seg`; it is the adjoint of
+`seg(duration, segment_sum)`.  With the reference the spelling is `torch.repeat_interleave(c.data, counts, dim=0)` plus
+a `segment_sum` of the counts and a new constructor — for a CattedSequence only — or a gather through an index built
+with repeat_interleave / arange, with hand-rolled arithmetic for an L / R; a PackedSequence gets nothing (the sort order
+of the result changes), and autograd keeps an int64 index per output token.
+
+`repeats` is one of
+  * a `torch.int64` tensor on the payload's device in the container's STORAGE layout of the token dimensions — [N] for
+    C / P, [B, T_phys] for L / R; counts in padding rows of an L / R are never read;
+  * a container of the same type whose `.data` is that tensor;
+  * a Python int r >= 0: every token r times.
+One value per token: counts with hidden dimensions are refused.  The counts are not differentiable.
+
+The payload moves as BITS: every dtype of element size 1 / 2 / 4 / 8 (int64 token ids and bool included), 1-D payloads
+and any hidden shape, any row width and alignment; a NaN keeps its bits.
+
+The result is defined by commutation, as for `compress`.  For a C the data is the repeated rows in storage order and
+`token_sizes` the new lengths (int64).  For every other layout X, `z.repeat_interleave(r)` equals
+`z.cat().repeat_interleave(r_as_cat).X()` field by field and bit for bit, where `r_as_cat` is the counts cast like the
+data: for a P that covers data, batch_sizes, sorted_indices and unsorted_indices, for an L / R the new T and zero padding
+rows.  `z.repeat_interleave(r).cat()` equals `z.cat().repeat_interleave(r_as_cat)` likewise.  With a bool mask m,
+`z.repeat_interleave(m.long()) == z.compress(m)`; `z.repeat_interleave(1) == z`; `z.repeat_interleave(0)` is empty.
+
+INVALID COUNTS.  A negative count, or one above 2^31 - 1, raises RuaError (torch raises too).  The plan counts such
+entries, takes them as 0 and leaves their number behind the new lengths, so the one read-back carries it.  A new
+sequence longer than 2^31 - 1 tokens is refused after the read-back, before anything is allocated.  The one exception:
+an int count on a C whose lengths the host never saw — that call never synchronises, so it cannot tell; its result is
+sized N * r and the first cast that reads the lengths back sees them.
+
+Three HIP kernels (csrc/rua_repeat.hip), identical for the four layouts.  The plan is a per-sequence exclusive scan of
+the counts: `first`, the position of every token's first copy in its new sequence (int64 per storage row), and the new
+lengths.  The move is DESTINATION-driven: the row of token (b, u) of the result reads the source token t, the largest t
+with first[b, t] <= u — right with zero counts anywhere; a workgroup finds the source tokens of its block of consecutive
+destination tokens once, stages their entries in LDS and searches there.  Padding rows of an L / R result are written as
+zeros by the same launch.  The result's offsets and PackedSequence metadata come from the library's existing scan /
+host-sort path over the new lengths.
+
+SYNCHRONISATION.  With tensor counts the new lengths decide the allocation, so every call reads them back: ONE blocking
+copy of [B + 1] int64 (torch.repeat_interleave synchronises too).  The host copy is attached to the result's lengths, so
+a following `pack()` / `left()` / `size()` reads nothing back again.  With an int r the new lengths are r * len and the
+source of output token u is u // r: no plan launch, no table; a C result never synchronises, an L / R / P result reads
+the lengths back exactly when the corresponding cast would (not at all when they carry a host copy).
+
+Autograd: `repeat` and its adjoint, the run sum (every token receives the sum of its copies' gradients, in ascending
+order, accumulated in fp32 — fp64 for float64 — and rounded once; no atomics: the same bits from run to run and in every
+layout), are two Functions that are each other's backward, so derivatives of every order exist.  Only `first` and the
+caller's counts are saved (nothing for an int r) — no payload, no index per output token.  Gradients of tokens with
+count 0 and of padding rows are exact zeros.  Integer and bool payloads pass through without a graph.  A very long run
+(one count of 100 000) is summed by ONE thread group in the backward: correct, and slow.
+
+Out of scope: per-column counts, fractional / interpolating upsampling, a caller-given capacity that never synchronises
+(the follow-up `compress` names too), splitting long runs in the backward, differentiable durations, int32 counts.
+"""
+from typing import Tuple, Union
+
+import torch
+from torch import Tensor
+
+from torchrua_amd import _lib as K
+from torchrua_amd import _meta as M
+from torchrua_amd import _ops as O
+from torchrua_amd.core import _pack_meta
+from torchrua_amd.layout import C, L, P, R, T, Z, cat_lay, lay_hidden, lens_of
+
+__all__ = ['segment_repeat_interleave', 'repeat_interleave']
+
+MAX_COUNT = 2 ** 31 - 1
+
+
+def _check_repeats(repeats, lead_shape: Tuple[int, ...], data: Tensor, what: str) -> Union[int, Tensor]:
+    """The counts as an int or a tensor, after the checks that need no device: int64, one value per token in the
+    storage layout of the token dimensions, on the payload's device; an int is not negative."""
+    if isinstance(repeats, int) and not isinstance(repeats, bool):
+        if repeats < 0:
+            raise K.RuaError(f'{what}: repeats is a negative int ({repeats}); it must be >= 0')
+        if repeats > MAX_COUNT:
+            raise K.RuaError(f'{what}: repeats is {repeats}; a count above 2^31 - 1 is invalid')
+        return repeats
+    if not isinstance(repeats, Tensor):
+        raise K.RuaError(f'{what}: repeats is a torch.int64 tensor (or a container of the same type holding one) or an '
+                         f'int; got {type(repeats).__name__}')
+    if repeats.dtype == torch.bool:
+        raise K.RuaError(f'{what}: repeats has dtype torch.bool; keeping tokens by a mask is compress(mask)')
+    if repeats.dtype != torch.int64:
+        raise K.RuaError(f'{what}: repeats has dtype {repeats.dtype}; it must be torch.int64')
+    lead_shape = tuple(lead_shape)
+    if repeats.dim() > len(lead_shape) and tuple(repeats.shape[:len(lead_shape)]) == lead_shape:
+        raise K.RuaError(f'{what}: repeats has shape {tuple(repeats.shape)}: hidden dimensions — it holds ONE count per '
+                         f'token, shape {lead_shape}')
+    if tuple(repeats.shape) != lead_shape:
+        raise K.RuaError(f'{what}: repeats has shape {tuple(repeats.shape)}; the token dimensions of the storage are '
+                         f'{lead_shape}')
+    if repeats.device != data.device:
+        raise K.RuaError(f'{what}: repeats lives on {repeats.device}, the payload on {data.device}')
+    return repeats
+
+
+def _too_long(new_sizes: Tensor, what: str) -> None:
+    longest = M.known_max_len(new_sizes)
+    if longest is not None and longest > MAX_COUNT:
+        raise K.RuaError(f'{what}: a new sequence would hold {longest} tokens; the most is 2^31 - 1')
+
+
+def _new_lengths(src: M.Lay, lens: Tensor, repeats: Union[int, Tensor], what: str):
+    """(first, counts, uniform, new lengths).  Tensor counts: the plan and the call's ONE read-back — the new lengths
+    and the number of invalid counts — with the host copy attached to the lengths.  An int: r * len, with the host copy
+    when `lens` carries one; nothing is launched for the table and nothing is read back."""
+    if isinstance(repeats, int):
+        new_sizes = M._as_lens(lens) * repeats
+        host = lens if not lens.is_cuda else M._memo_get(lens, 'host')
+        if host is not None:
+            M.attach_host(new_sizes, M.private_host_copy(host * repeats))
+        _too_long(new_sizes, what)
+        return None, None, repeats, new_sizes
+    counts = O._plain(repeats).contiguous()
+    first, buf = O.launch_repeat_plan(src, counts)
+    host = M._read_back(buf)
+    invalid = int(host[-1])
+    if invalid:
+        raise K.RuaError(f'{what}: {invalid} invalid count{"s" if invalid != 1 else ""} in repeats (negative, or above '
+                         f'2^31 - 1)')
+    # (the lengths are the first B words of the plan's [B + 1] buffer — a contiguous view at offset 0, not a tensor that
+    # owns its storage as every other constructor's lengths do: the invalid-count word stays alive behind them.  A clone
+    # would be one more launch per call for nothing a reader of `token_sizes` can see short of `untyped_storage()`)
+    new_sizes = buf[:src.B]
+    M.attach_host(new_sizes, host[:src.B])
+    _too_long(new_sizes, what)
+    return first, counts, 0, new_sizes
+
+
+def segment_repeat_interleave(tensor: T, repeats, segment_sizes: T) -> Tuple[T, T]:
+    """Row i of `tensor` [N, *hidden] `repeats[i]` times, and how many rows every run of `segment_sizes` rows becomes
+    (the argument order of segment_compress): (tensor [N', *hidden], new_sizes [S] int64)."""
+    repeats = _check_repeats(repeats, tuple(tensor.shape[:1]), tensor, 'segment_repeat_interleave')
+    K.require_device(tensor, segment_sizes, repeats if isinstance(repeats, Tensor) else None)
+    src, hidden = cat_lay(tensor, segment_sizes), tuple(tensor.shape[1:])
+    first, counts, uniform, new_sizes = _new_lengths(src, segment_sizes, repeats, 'segment_repeat_interleave')
+    n = int(tensor.size(0)) * uniform if first is None else M.total_len(new_sizes)
+    dst = M.lay_cat(new_sizes, src.B, n)
+    return O.repeat(tensor, first, counts, uniform, dst, src, hidden, (n,) + hidden, tuple(tensor.shape)), new_sizes
+
+
+def repeat_interleave(sequence: Z, repeats) -> Z:
+    """Every token `repeats[b, t]` (or `repeats`, an int) times in its own sequence; the same container type and number
+    of sequences.  See the module docstring."""
+    data = sequence.data
+    if isinstance(repeats, (C, L, P, R)):
+        if type(repeats) is not type(sequence):
+            raise K.RuaError(f'repeat_interleave: repeats given as a container must be a {type(sequence).__name__}; got '
+                             f'{type(repeats).__name__}')
+        repeats = repeats.data
+    lead = 1 if isinstance(sequence, (C, P)) else 2
+    repeats = _check_repeats(repeats, tuple(data.shape[:lead]), data, 'repeat_interleave')
+    src, hidden = lay_hidden(sequence)
+    dev = data.device
+    first, counts, uniform, new_sizes = _new_lengths(src, lens_of(sequence), repeats, 'repeat_interleave')
+    B = src.B
+    args = (first, counts, uniform)
+    if isinstance(sequence, C):
+        # (an int count: N * r rows, known without a look at the lengths — a C result never synchronises)
+        n = int(data.size(0)) * uniform if first is None else M.total_len(new_sizes)
+        dst, shape = M.lay_cat(new_sizes, B, n), (n,) + hidden
+        return C(data=O.repeat(data, *args, dst, src, hidden, shape, tuple(data.shape)), token_sizes=new_sizes)
+    if isinstance(sequence, P):
+        # (an int count and lengths the host never saw: the read-back pack() would do, BEFORE batch_sizes is sized by it)
+        M.max_len(new_sizes)
+        _too_long(new_sizes, 'repeat_interleave')
+        # the metadata C.pack() derives from these lengths: the reference's host sort, batch_sizes, the device scans
+        lens, sorted_indices, unsorted, batch_sizes, bsz_dev, boff = _pack_meta(new_sizes, dev)
+        n = M.total_len(new_sizes)
+        shell = P(data=data, batch_sizes=batch_sizes, sorted_indices=sorted_indices, unsorted_indices=unsorted)
+        M.adopt_pack(shell, lens, boff, bsz_dev)
+        dst = M.lay_pack(shell, lens=lens, boff=boff, T=batch_sizes.numel(), n_rows=n)
+        return shell._replace(data=O.repeat(data, *args, dst, src, hidden, (n,) + hidden, tuple(data.shape)))
+    kind = K.LEFT if isinstance(sequence, L) else K.RIGHT
+    t = M.max_len(new_sizes)
+    _too_long(new_sizes, 'repeat_interleave')           # (an int count and lengths the host never saw: known only now)
+    dst, shape = M.lay_padded(kind, new_sizes, B, t, t), (B, t) + hidden
+    return type(sequence)(data=O.repeat(data, *args, dst, src, hidden, shape, tuple(data.shape)),
+                          token_sizes=new_sizes)
+
+
+for _cls in (C, L, P, R):
+    _cls.repeat_interleave = repeat_interleave
