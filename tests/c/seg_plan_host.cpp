@@ -4,14 +4,18 @@
 // A violation is a plan the launchers could not launch as they compute it: a grid beyond 2^31 - 1 workgroups that
 // seg_rows_grid / seg_lanes_geometry did not refuse, a block or chunk count that does not cover the bound or the row,
 // a workspace that is not exactly one slot per (sequence, block, chunk, padded column), or a cut outside the rule.
+// The plan of the offsets scan (seg_make_scan_plan: compress, repeat_interleave) is walked here too, for both workspace
+// elements, over B up to 2^40 and bounds up to 2^36: a form outside its rule, a grid that does not cover every sequence
+// (or, cut, every block) or exceeds what a launch takes, a workspace that is not one element per (sequence, block).
 #include <stdint.h>
 #include <stdio.h>
 #include <initializer_list>
 #include "rua_seg_plan.h"
+#include "plan_walk.h"
 
 using namespace rua;
 
-static long long violations = 0, plans = 0, cuts = 0;
+static long long plans = 0, cuts = 0, scan_plans = 0, scan_cuts = 0, scan_forms[4] = {0, 0, 0, 0};
 
 static void fail(const char* what, const rua_layout& L, int64_t H, int es) {
   if (++violations <= 20)
@@ -82,6 +86,39 @@ static void walk_plan(const rua_layout& L, int64_t H, int es, int per_col) {
   }
 }
 
+static void walk_scan_plan(const rua_layout& L, int ws_elem_bytes) {
+  if (seg_check_entry(&L, 1, 1) != 0) { fail("entry checks refuse a sound call", L); return; }
+  const int64_t bound = sm_len_bound(L);
+  const seg_scan_plan p = seg_make_scan_plan(L, ws_elem_bytes);
+  ++scan_plans;
+  if (L.B == 0) {
+    if (p.grid || p.ws_bytes || p.maxblk) fail("a plan for an empty batch", L);
+    return;
+  }
+  if (p.form < 0 || p.form > 3) { fail("no such form", L); return; }
+  ++scan_forms[p.form];
+  if ((p.form == SEG_SCAN_CUT) != cut_rule(L, L.B)) fail("a cut outside the rule (or a rule without its cut)", L);
+  if (p.form == SEG_SCAN_CUT) {
+    ++scan_cuts;
+    if ((int64_t)p.maxblk * SEG_BLOCK_TOK < bound || ((int64_t)p.maxblk - 1) * SEG_BLOCK_TOK >= bound)
+      fail("the blocks do not cover the bound exactly", L);
+    if (p.ws_bytes != L.B * p.maxblk * ws_elem_bytes) fail("ws_bytes is not one element per (sequence, block)", L);
+    if ((__int128)p.grid != (__int128)L.B * p.maxblk || p.grid > 0x7fffffffLL) fail("the cut grid is not B * maxblk", L);
+    if (p.per_wg != 1) fail("a cut unit is a workgroup's", L);
+    return;
+  }
+  if (p.maxblk || p.ws_bytes) fail("maxblk or ws_bytes without a cut", L);
+  if (p.form == SEG_SCAN_LANES && (bound > SEG_SCAN_LANES_MAX_LEN || p.per_wg != 2 * SEG_WAVES_PER_BLOCK))
+    fail("lanes form outside its rule", L);
+  if (p.form == SEG_SCAN_ROWS && (bound <= SEG_SCAN_LANES_MAX_LEN || bound >= SEG_BLOCK_TOK || p.per_wg != SEG_WAVES_PER_BLOCK))
+    fail("rows form outside its rule", L);
+  if (p.form == SEG_SCAN_LONG && (bound < SEG_BLOCK_TOK || p.per_wg != 1)) fail("long form outside its rule", L);
+  const __int128 want = ((__int128)L.B + p.per_wg - 1) / p.per_wg;
+  if (p.grid < 0 || p.grid > 0x7fffffffLL) fail("a grid beyond what a launch takes", L);
+  if (p.grid != 0 && (__int128)p.grid != want) fail("the grid does not cover B exactly", L);
+  if (p.grid == 0 && want <= 0x7fffffffLL) fail("a grid refused that fits", L);
+}
+
 int main() {
   const int kinds[4] = {RUA_CAT, RUA_LEFT, RUA_PACK, RUA_RIGHT};
   // (dtype, whether the operator lets int64 in, the bytes it keeps per block and padded column)
@@ -115,6 +152,10 @@ int main() {
               walk_plan(L, H, es, op.accs * (es == 8 ? 8 : 4) + op.extra);
               if (seg_too_large(&L, H, es) != ((double)L.n_rows * (double)H * es >= 9.0e18)) fail("seg_too_large", L, H, es);
             }
-  printf("plans %lld cuts %lld violations %lld\n", plans, cuts, violations);
-  return violations ? 1 : (cuts > 0 ? 0 : 2);
+  for (int ws_elem_bytes : {4, 8})
+    for_each_bound_layout([&](const rua_layout& L) { walk_scan_plan(L, ws_elem_bytes); });
+  printf("plans %lld cuts %lld scan plans %lld cuts %lld lanes %lld rows %lld long %lld violations %lld\n", plans, cuts,
+         scan_plans, scan_cuts, scan_forms[0], scan_forms[1], scan_forms[2], violations);
+  const bool seen = cuts > 0 && scan_cuts > 0 && scan_forms[0] > 0 && scan_forms[1] > 0 && scan_forms[2] > 0;
+  return violations ? 1 : (seen ? 0 : 2);
 }

@@ -53,7 +53,7 @@ from torch import Tensor
 from torchrua_amd import _lib as K
 from torchrua_amd import _meta as M
 from torchrua_amd import _ops as O
-from torchrua_amd.core import _pack_meta
+from torchrua_amd.core import result_like
 from torchrua_amd.layout import C, L, P, R, T, Z, cat_lay, lay_hidden
 
 __all__ = ['segment_compress', 'compress']
@@ -110,26 +110,9 @@ def compress(sequence: Z, mask) -> Z:
     lead = 1 if isinstance(sequence, (C, P)) else 2
     mask = _check_mask(mask, tuple(data.shape[:lead]), data, 'compress')
     big, hidden = lay_hidden(sequence)
-    dev = data.device
     rank, new_sizes = _new_lengths(big, mask)
-    B = big.B
-    if isinstance(sequence, C):
-        n = M.total_len(new_sizes)
-        small, shape = M.lay_cat(new_sizes, B, n), (n,) + hidden
-        return C(data=O.compress(data, rank, small, big, hidden, shape, tuple(data.shape)), token_sizes=new_sizes)
-    if isinstance(sequence, P):
-        # the metadata C.pack() derives from these lengths: the reference's host sort, batch_sizes, the device scans
-        lens, sorted_indices, unsorted, batch_sizes, bsz_dev, boff = _pack_meta(new_sizes, dev)
-        n = M.total_len(new_sizes)
-        shell = P(data=data, batch_sizes=batch_sizes, sorted_indices=sorted_indices, unsorted_indices=unsorted)
-        M.adopt_pack(shell, lens, boff, bsz_dev)
-        small = M.lay_pack(shell, lens=lens, boff=boff, T=batch_sizes.numel(), n_rows=n)
-        return shell._replace(data=O.compress(data, rank, small, big, hidden, (n,) + hidden, tuple(data.shape)))
-    kind = K.LEFT if isinstance(sequence, L) else K.RIGHT
-    t = M.max_len(new_sizes)
-    small, shape = M.lay_padded(kind, new_sizes, B, t, t), (B, t) + hidden
-    return type(sequence)(data=O.compress(data, rank, small, big, hidden, shape, tuple(data.shape)),
-                          token_sizes=new_sizes)
+    small, shape, wrap = result_like(type(sequence), new_sizes, big.B, hidden, data)
+    return wrap(O.compress(data, rank, small, big, hidden, shape, tuple(data.shape)))
 
 
 for _cls in (C, L, P, R):

@@ -8,7 +8,7 @@ core/view.py:34-38 + core/cast.py:19-23).
 """
 import threading
 from numbers import Number
-from typing import Any, List, Tuple, Union
+from typing import Any, List, Optional, Tuple, Union
 
 import torch
 from torch import Tensor
@@ -107,6 +107,27 @@ def _pack_meta(token_sizes: Tensor, dev: torch.device):
     M._memo_put(token_sizes, key, (meta, tuple(M._version(t) for t in meta)))
     M._memo_put(sorted_indices, 'reference_order', True)        # (pack_reference_order below)
     return (lens,) + meta
+
+
+def result_like(cls, sizes: Tensor, B: int, hidden: Tuple[int, ...], like: Tensor, n: Optional[int] = None):
+    """(layout, storage shape, payload -> container) of a `cls` result with the lengths `sizes` — what the operators
+    that change a batch's raggedness (compress, join / unjoin, repeat_interleave) build before they move the rows —
+    through the paths the casts use: the device scan (C), the host sort + rua_pack_prepare (P: _pack_meta), the longest
+    sequence (L / R).  `like`: a payload on the result's device.  `n`: the storage rows of a C whose lengths the host
+    does not know."""
+    if issubclass(cls, C):
+        n = M.total_len(sizes) if n is None else n
+        return M.lay_cat(sizes, B, n), (n,) + hidden, lambda data: C(data=data, token_sizes=sizes)
+    if issubclass(cls, P):
+        lens, sorted_indices, unsorted, batch_sizes, bsz_dev, boff = _pack_meta(sizes, like.device)
+        n = M.total_len(sizes)
+        shell = P(data=like, batch_sizes=batch_sizes, sorted_indices=sorted_indices, unsorted_indices=unsorted)
+        M.adopt_pack(shell, lens, boff, bsz_dev)
+        lay = M.lay_pack(shell, lens=lens, boff=boff, T=batch_sizes.numel(), n_rows=n)
+        return lay, (n,) + hidden, lambda data: shell._replace(data=data)
+    t = M.max_len(sizes)
+    lay = M.lay_padded(K.LEFT if issubclass(cls, L) else K.RIGHT, sizes, B, t, t)
+    return lay, (B, t) + hidden, lambda data: cls(data=data, token_sizes=sizes)
 
 
 _sort_job = threading.Lock()

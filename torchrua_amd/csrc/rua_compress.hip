@@ -17,13 +17,10 @@
 #include <stdint.h>
 #include <string.h>
 #include <atomic>
-#include "rua_seg.h"
+#include "rua_seg_scan.h"
 #include "rua_compress_plan.h"
 
 namespace rua {
-
-extern std::atomic<int> g_trace_on;        // the dispatch trace (rua_reduce.hip)
-void trace_add(const char* rec);
 
 constexpr int CM_SLOTS = 32;               // move: tokens a step of a workgroup (rows form) or half wave (lanes form) takes
 constexpr int CM_LPR = 8;                  // rows form: 16-byte pieces per row chunk (128 bytes)
@@ -31,66 +28,21 @@ constexpr int CM_UNR = 4;                  // tokens in flight per thread
 static_assert(CM_SLOTS * CM_LPR == RUA_BLOCK, "a thread per (token slot, 16-byte piece of the chunk)");
 static_assert(RUA_WAVE == 64, "the counts below are 64-bit ballots");
 
-// the tokens [tb, te) of sequence b that block `blk` of `maxblk` takes (maxblk == 0: all of them).  The last block takes
-// what a length bound that understates left over: every token is ranked
-__device__ __forceinline__ void cp_block_range(int maxblk, int blk, int64_t len, int64_t& tb, int64_t& te) {
-  tb = 0;
-  te = len;
-  if (maxblk > 0) {
-    tb = (int64_t)blk * SEG_BLOCK_TOK;
-    if (blk < maxblk - 1 && te > tb + SEG_BLOCK_TOK) te = tb + SEG_BLOCK_TOK;
-    if (tb > te) tb = te;
-  }
-}
-
 // ---------------------------------------------------------------- the plan
-// G lanes walk one sequence, G tokens per step: 32 (two sequences per wave), 64 (a wave per sequence) or 256 (a
-// workgroup per sequence, or — maxblk > 0, the cut form — per block of SEG_BLOCK_TOK tokens of one).  Inside a wave the
-// count in front of a lane is a popcount of the lower lanes' bits of one 64-bit ballot; a workgroup adds the counts of
-// the waves below through LDS; the count of the steps before is carried in a register.
-// phase 0: ranks and new_lens in one launch.  The cut form takes two: phase 1 leaves every block's count in
-// ws[b * maxblk + blk]; phase 2 adds the counts of the blocks before its own in block order and writes the ranks, the
-// last block also new_lens.  Padding rows of a LEFT / RIGHT storage get -1 (block 0 writes them).
-template <int G>
-__global__ __launch_bounds__(RUA_BLOCK) void seg_compress_plan_kernel(rua_layout L, const uint8_t* __restrict__ mask,
-                                                                      int32_t* __restrict__ rank,
-                                                                      int64_t* __restrict__ new_lens, int maxblk,
-                                                                      int32_t* ws, int phase) {
-  constexpr int PER_WG = RUA_BLOCK / G;
-  __shared__ int wsum[RUA_WAVES_PER_BLOCK];
-  const int tid = threadIdx.x;
-  const int lane = tid & (RUA_WAVE - 1), w = tid >> 6;
-  const int q = tid % G;
-  int64_t b = (int64_t)blockIdx.x * PER_WG + tid / G;
-  int blk = 0;
-  if (G == RUA_BLOCK && maxblk > 0) {
-    blk = (int)(blockIdx.x % (unsigned)maxblk);
-    b = blockIdx.x / (unsigned)maxblk;
-  }
-  const bool have = b < L.B;
-  const int64_t len = have ? safe_len(L, b) : 0;
-  int64_t tb, te;
-  cp_block_range(G == RUA_BLOCK ? maxblk : 0, blk, len, tb, te);
-  int64_t span = te - tb;                                      // uniform over the lanes that vote together
-  if (G == 32) {
-    const int64_t other = __shfl_xor(span, 32, RUA_WAVE);
-    span = span > other ? span : other;
-  }
-
-  int32_t carried = 0;
-  if (phase == 2 && have) {
-    for (int i = 0; i < blk; ++i) carried += ws[b * maxblk + i];
-  }
-  for (int64_t u0 = 0; u0 < span; u0 += G) {
-    const int64_t t = tb + u0 + q;
-    int64_t row = -1;
-    bool keep = false;
-    if (t < te) {
-      row = token_to_row(L, b, t, len);
-      if (row >= 0 && row < L.n_rows) keep = mask[row] != 0; else row = -1;
-    }
+// the family's offsets scan (rua_seg_scan.h) over the mask: a token's value is whether it is kept, the sum in front of a
+// lane a popcount of the lower lanes' bits of one 64-bit ballot, and a kept token stores its position, a dropped one -1
+struct cp_scan {
+  using in_t = uint8_t;
+  using out_t = int32_t;
+  using sum_t = int32_t;
+  using val_t = bool;
+  static constexpr bool COUNTS_INVALID = false;
+  static const char* kernel() { return "seg_compress_plan_kernel"; }
+  static const char* phase1() { return "count"; }
+  static __device__ __forceinline__ bool load(const uint8_t* mask, int64_t row, int&) { return mask[row] != 0; }
+  template <int G>
+  static __device__ __forceinline__ void wave_prefix(bool keep, int lane, int q, int32_t& before, int32_t& total) {
     const unsigned long long bal = __ballot(keep);
-    int before, total;
     if (G == 32) {
       const uint32_t m = (uint32_t)(bal >> (lane & 32));
       before = __popc(m & ((1u << q) - 1u));
@@ -99,58 +51,12 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_compress_plan_kernel(rua_layout
       before = __popcll(bal & ((1ull << lane) - 1ull));
       total = __popcll(bal);
     }
-    if (G == RUA_BLOCK) {
-      if (lane == 0) wsum[w] = total;
-      __syncthreads();                                         // (workgroup-uniform trip count: b and blk are)
-      total = 0;
-#pragma unroll
-      for (int i = 0; i < RUA_WAVES_PER_BLOCK; ++i) {
-        const int s = wsum[i];
-        if (i < w) before += s;
-        total += s;
-      }
-      __syncthreads();
-    }
-    if (phase != 1 && row >= 0) rank[row] = keep ? carried + before : -1;
-    carried += total;
   }
-
-  if (!have) return;
-  if (q == 0) {
-    if (phase == 1) ws[b * maxblk + blk] = carried;
-    else if (phase == 0 || blk == maxblk - 1) new_lens[b] = carried;
-  }
-  if (phase != 1 && blk == 0 && (L.kind == RUA_LEFT || L.kind == RUA_RIGHT)) {
-    for (int64_t j = q; j < L.T_phys; j += G) {
-      if (!is_pad(L, j, len)) continue;
-      const int64_t row = b * L.T_phys + j;
-      if (row < L.n_rows) rank[row] = -1;
-    }
-  }
-}
+  static __device__ __forceinline__ int32_t store(bool keep, int32_t pos) { return keep ? pos : -1; }
+};
+static_assert(sizeof(cp_scan::sum_t) == CP_WS_ELEM_BYTES, "the workspace the host plan sizes holds the kernel's counts");
 
 // ---------------------------------------------------------------- the move
-// 16 bytes of a row (fewer at its end: `nb`) in accesses of W bytes, W a power of two that divides the row and the bases
-template <int W> struct cm_word;
-template <> struct cm_word<16> { using t = uint4; };
-template <> struct cm_word<8> { using t = uint2; };
-template <> struct cm_word<4> { using t = uint32_t; };
-template <> struct cm_word<2> { using t = uint16_t; };
-template <> struct cm_word<1> { using t = uint8_t; };
-struct alignas(16) cm_vec { uint32_t d[4]; };
-
-template <int W> __device__ __forceinline__ void cm_ld(const char* p, int nb, cm_vec& v) {
-  using T = typename cm_word<W>::t;
-#pragma unroll
-  for (int i = 0; i < 16 / W; ++i) if (i * W < nb) ((T*)&v)[i] = ((const T*)p)[i];
-}
-template <int W> __device__ __forceinline__ void cm_st(char* p, int nb, const cm_vec& v) {
-  using T = typename cm_word<W>::t;
-#pragma unroll
-  for (int i = 0; i < 16 / W; ++i) if (i * W < nb) ((T*)p)[i] = ((const T*)&v)[i];
-}
-__device__ __forceinline__ void cm_zero(cm_vec& v) { v.d[0] = v.d[1] = v.d[2] = v.d[3] = 0u; }
-
 // the row of `small` that the token of big's row `row` (sequence b) goes to, or -1: dropped, or a rank that names no
 // token of the new sequence (a rank table that does not belong to these layouts must not index out of range)
 __device__ __forceinline__ int64_t cm_small_row(const rua_layout& S, const int32_t* rank, int64_t b, int64_t row,
@@ -159,17 +65,6 @@ __device__ __forceinline__ int64_t cm_small_row(const rua_layout& S, const int32
   if (r < 0 || r >= slen) return -1;
   const int64_t sr = token_to_row(S, b, r, slen);
   return sr >= 0 && sr < S.n_rows ? sr : -1;
-}
-
-// padding rows of sequence b of a LEFT / RIGHT destination, as zeros: position j0, j0 + step, ... of [0, T_phys)
-template <typename St>
-__device__ __forceinline__ void cm_zero_padding(const rua_layout& D, int64_t b, int64_t dlen, int j0, int step, St st) {
-  if (D.kind != RUA_LEFT && D.kind != RUA_RIGHT) return;
-  for (int64_t j = j0; j < D.T_phys; j += step) {
-    if (!is_pad(D, j, dlen)) continue;
-    const int64_t row = b * D.T_phys + j;
-    if (row < D.n_rows) st(row);
-  }
 }
 
 // Rows wider than one vector: a workgroup per unit of `big` and 128-byte column chunk; a unit is a sequence, or
@@ -193,16 +88,16 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_compress_move_rows_kernel(rua_l
   if (nb <= 0) return;
   const int64_t len = safe_len(Bg, b), slen = safe_len(S, b);
   int64_t tb, te;
-  cp_block_range(maxblk, blk, len, tb, te);
+  seg_block_range(maxblk, blk, len, tb, te);
 
   for (int64_t t0 = tb + q; t0 < te; t0 += CM_SLOTS * CM_UNR) {
     int64_t rows[CM_UNR], srows[CM_UNR];
-    cm_vec v[CM_UNR];
+    row_vec v[CM_UNR];
 #pragma unroll
     for (int i = 0; i < CM_UNR; ++i) {
       const int64_t t = t0 + (int64_t)i * CM_SLOTS;
       rows[i] = srows[i] = -1;
-      cm_zero(v[i]);
+      row_zero(v[i]);
       if (t < te) {
         const int64_t row = token_to_row(Bg, b, t, len);
         if (row >= 0 && row < Bg.n_rows) {
@@ -214,25 +109,25 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_compress_move_rows_kernel(rua_l
 #pragma unroll
     for (int i = 0; i < CM_UNR; ++i) {
       if (srows[i] < 0) continue;
-      if (expand) cm_ld<W>(small + srows[i] * rb + col0, nb, v[i]);
-      else cm_ld<W>(big + rows[i] * rb + col0, nb, v[i]);
+      if (expand) row_ld<W>(small + srows[i] * rb + col0, nb, v[i]);
+      else row_ld<W>(big + rows[i] * rb + col0, nb, v[i]);
     }
 #pragma unroll
     for (int i = 0; i < CM_UNR; ++i) {
       if (expand) {
-        if (rows[i] >= 0) cm_st<W>(big + rows[i] * rb + col0, nb, v[i]);
+        if (rows[i] >= 0) row_st<W>(big + rows[i] * rb + col0, nb, v[i]);
       } else if (srows[i] >= 0) {
-        cm_st<W>(small + srows[i] * rb + col0, nb, v[i]);
+        row_st<W>(small + srows[i] * rb + col0, nb, v[i]);
       }
     }
   }
 
   if (blk == 0) {
-    cm_vec z;
-    cm_zero(z);
+    row_vec z;
+    row_zero(z);
     char* out = expand ? big : small;
-    cm_zero_padding(expand ? Bg : S, b, expand ? len : slen, q, CM_SLOTS,
-                    [&](int64_t row) { cm_st<W>(out + row * rb + col0, nb, z); });
+    seg_fill_padding(expand ? Bg : S, b, expand ? len : slen, q, CM_SLOTS,
+                     [&](int64_t row) { row_st<W>(out + row * rb + col0, nb, z); });
   }
 }
 
@@ -251,12 +146,12 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_compress_move_lanes_kernel(rua_
 
   for (int64_t t0 = q; t0 < len; t0 += CM_SLOTS * CM_UNR) {
     int64_t rows[CM_UNR], srows[CM_UNR];
-    cm_vec v[CM_UNR];
+    row_vec v[CM_UNR];
 #pragma unroll
     for (int i = 0; i < CM_UNR; ++i) {
       const int64_t t = t0 + (int64_t)i * CM_SLOTS;
       rows[i] = srows[i] = -1;
-      cm_zero(v[i]);
+      row_zero(v[i]);
       if (t < len) {
         const int64_t row = token_to_row(Bg, b, t, len);
         if (row >= 0 && row < Bg.n_rows) {
@@ -268,98 +163,33 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_compress_move_lanes_kernel(rua_
 #pragma unroll
     for (int i = 0; i < CM_UNR; ++i) {
       if (srows[i] < 0) continue;
-      if (expand) cm_ld<W>(small + srows[i] * nb, nb, v[i]);
-      else cm_ld<W>(big + rows[i] * nb, nb, v[i]);
+      if (expand) row_ld<W>(small + srows[i] * nb, nb, v[i]);
+      else row_ld<W>(big + rows[i] * nb, nb, v[i]);
     }
 #pragma unroll
     for (int i = 0; i < CM_UNR; ++i) {
       if (expand) {
-        if (rows[i] >= 0) cm_st<W>(big + rows[i] * nb, nb, v[i]);
+        if (rows[i] >= 0) row_st<W>(big + rows[i] * nb, nb, v[i]);
       } else if (srows[i] >= 0) {
-        cm_st<W>(small + srows[i] * nb, nb, v[i]);
+        row_st<W>(small + srows[i] * nb, nb, v[i]);
       }
     }
   }
 
-  cm_vec z;
-  cm_zero(z);
+  row_vec z;
+  row_zero(z);
   char* out = expand ? big : small;
-  cm_zero_padding(expand ? Bg : S, b, expand ? len : slen, q, CM_SLOTS,
-                  [&](int64_t row) { cm_st<W>(out + row * nb, nb, z); });
+  seg_fill_padding(expand ? Bg : S, b, expand ? len : slen, q, CM_SLOTS,
+                   [&](int64_t row) { row_st<W>(out + row * nb, nb, z); });
 }
 
 // ---------------------------------------------------------------- host side
-static const char* cp_form_name(int form) {
-  switch (form) {
-    case CP_LANES: return "lanes";
-    case CP_ROWS:  return "rows";
-    case CP_LONG:  return "long";
-    case CP_CUT:   return "cut";
-  }
-  return "?";
-}
-
-static int cp_launch_plan(const rua_layout& L, const uint8_t* mask, int32_t* rank, int64_t* new_lens, void* ws,
-                          hipStream_t s) {
-  cp_plan p = cp_make_plan(L);
-  if (p.form == CP_CUT && !ws) {                               // ws == NULL: do not cut
-    p.form = CP_LONG;
-    p.maxblk = 0;
-    p.grid = L.B;
-  }
-  if (p.grid <= 0 || p.grid > 0x7fffffffLL) return RUA_ERANGE;
-  const bool tr = g_trace_on.load(std::memory_order_relaxed) != 0;
-  char rec[200];
-  const dim3 grid((unsigned)p.grid), block(RUA_BLOCK);
-  auto note = [&](const char* phase) {
-    if (!tr) return;
-    snprintf(rec, sizeof rec, "seg_compress_plan_kernel form=%s G=%d kind=%d cut=%d blocks=%d phase=%s",
-             cp_form_name(p.form), RUA_BLOCK / p.per_wg, L.kind, (int)(p.form == CP_CUT), p.maxblk, phase);
-    trace_add(rec);
-  };
-  switch (p.form) {
-    case CP_LANES:
-      note("whole");
-      hipLaunchKernelGGL((seg_compress_plan_kernel<32>), grid, block, 0, s, L, mask, rank, new_lens, 0, nullptr, 0);
-      break;
-    case CP_ROWS:
-      note("whole");
-      hipLaunchKernelGGL((seg_compress_plan_kernel<64>), grid, block, 0, s, L, mask, rank, new_lens, 0, nullptr, 0);
-      break;
-    case CP_LONG:
-      note("whole");
-      hipLaunchKernelGGL((seg_compress_plan_kernel<RUA_BLOCK>), grid, block, 0, s, L, mask, rank, new_lens, 0, nullptr, 0);
-      break;
-    case CP_CUT: {
-      note("count");
-      hipLaunchKernelGGL((seg_compress_plan_kernel<RUA_BLOCK>), grid, block, 0, s, L, mask, rank, new_lens, p.maxblk,
-                         (int32_t*)ws, 1);
-      const int e = (int)hipGetLastError();
-      if (e) return e;
-      note("finish");
-      hipLaunchKernelGGL((seg_compress_plan_kernel<RUA_BLOCK>), grid, block, 0, s, L, mask, rank, new_lens, p.maxblk,
-                         (int32_t*)ws, 2);
-      break;
-    }
-  }
-  return (int)hipGetLastError();
-}
-
 static int cm_launch_move(const rua_layout& S, const rua_layout& Bg, const int32_t* rank, char* small, char* big,
                           int64_t rb, int expand, hipStream_t s) {
   const uint64_t bases = (uint64_t)(uintptr_t)small | (uint64_t)(uintptr_t)big;
-  const uint64_t mix = (uint64_t)rb | bases | 16u;
-  const int W = (int)(mix & (~mix + 1));                      // the widest access that divides the row and the bases
+  const int W = seg_access_width(rb, bases);
   const bool tr = g_trace_on.load(std::memory_order_relaxed) != 0;
   char rec[200];
-#define RUA_CM_W(LAUNCH)                                                                                               \
-  switch (W) {                                                                                                         \
-    case 16: LAUNCH(16); break;                                                                                        \
-    case 8:  LAUNCH(8); break;                                                                                         \
-    case 4:  LAUNCH(4); break;                                                                                         \
-    case 2:  LAUNCH(2); break;                                                                                         \
-    default: LAUNCH(1); break;                                                                                         \
-  }
   if (rb <= 16) {
     const seg_lanes ln = seg_lanes_geometry(rb, bases, Bg.B);
     if (!ln.grid) return RUA_ERANGE;
@@ -371,7 +201,7 @@ static int cm_launch_move(const rua_layout& S, const rua_layout& Bg, const int32
 #define RUA_CM_LANES(WV)                                                                                               \
   hipLaunchKernelGGL((seg_compress_move_lanes_kernel<WV>), dim3((unsigned)ln.grid), dim3(RUA_BLOCK), 0, s, S, Bg, rank, \
                      small, big, (int)rb, expand)
-    RUA_CM_W(RUA_CM_LANES)
+    RUA_DISPATCH_W(W, RUA_CM_LANES)
 #undef RUA_CM_LANES
   } else {
     const seg_plan p = seg_make_plan(Bg, rb, 1, 0);
@@ -386,10 +216,9 @@ static int cm_launch_move(const rua_layout& S, const rua_layout& Bg, const int32
 #define RUA_CM_ROWS(WV)                                                                                                \
   hipLaunchKernelGGL((seg_compress_move_rows_kernel<WV>), dim3((unsigned)grid), dim3(RUA_BLOCK), 0, s, S, Bg, rank,     \
                      small, big, rb, p.n_chunks, p.maxblk, expand)
-    RUA_CM_W(RUA_CM_ROWS)
+    RUA_DISPATCH_W(W, RUA_CM_ROWS)
 #undef RUA_CM_ROWS
   }
-#undef RUA_CM_W
   return (int)hipGetLastError();
 }
 
@@ -405,7 +234,7 @@ static int cp_check_entry(const rua_layout* lay, int64_t row_bytes) {
 extern "C" int64_t rua_compress_ws_bytes(const rua_layout* lay) {
   using namespace rua;
   if (cp_check_entry(lay, 1) != 0) return 0;
-  return cp_make_plan(*lay).ws_bytes;
+  return seg_make_scan_plan(*lay, CP_WS_ELEM_BYTES).ws_bytes;
 }
 
 extern "C" int rua_segment_compress_plan(const rua_layout* lay, const void* mask, int32_t* rank, int64_t* new_lens,
@@ -418,7 +247,14 @@ extern "C" int rua_segment_compress_plan(const rua_layout* lay, const void* mask
   if ((const void*)rank == mask || (const void*)new_lens == mask || (const void*)new_lens == (const void*)rank)
     return RUA_EINVAL;
   if ((uint64_t)(uintptr_t)rank % 4 || (uint64_t)(uintptr_t)new_lens % 8 || (uint64_t)(uintptr_t)ws % 4) return RUA_EALIGN;
-  return cp_launch_plan(*lay, (const uint8_t*)mask, rank, new_lens, ws, (hipStream_t)stream);
+  seg_scan_plan p = seg_make_scan_plan(*lay, CP_WS_ELEM_BYTES);
+  if (p.form == SEG_SCAN_CUT && !ws) {                         // ws == NULL: do not cut
+    p.form = SEG_SCAN_LONG;
+    p.maxblk = 0;
+    p.grid = lay->B;
+  }
+  if (p.grid <= 0 || p.grid > 0x7fffffffLL) return RUA_ERANGE;
+  return seg_launch_offsets<cp_scan>(p, *lay, (const uint8_t*)mask, rank, new_lens, ws, (hipStream_t)stream);
 }
 
 extern "C" int rua_segment_compress_move(const rua_layout* small, const rua_layout* big, const int32_t* rank,

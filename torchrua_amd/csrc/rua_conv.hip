@@ -138,13 +138,8 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_conv_rows_kernel(rua_layout L, 
     int blk = 0;
     if (maxblk > 0) { blk = (int)(unit % maxblk); b = unit / maxblk; }
     const int64_t len = safe_len(L, b);
-    int64_t tb = 0, te = len;
-    if (maxblk > 0) {
-      // the last block takes what a length bound that understates left over: every token is written
-      tb = (int64_t)blk * SEG_BLOCK_TOK;
-      if (blk < maxblk - 1 && te > tb + SEG_BLOCK_TOK) te = tb + SEG_BLOCK_TOK;
-      if (tb > te) tb = te;
-    }
+    int64_t tb, te;
+    seg_block_range(maxblk, blk, len, tb, te);
     const int64_t run = (te - tb + CV_SLOTS - 1) / CV_SLOTS;
     const int64_t s = tb + (int64_t)q * run < te ? tb + (int64_t)q * run : te;
     const int64_t se = s + run < te ? s + run : te;

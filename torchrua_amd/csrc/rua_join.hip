@@ -73,41 +73,20 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_unjoin_lens_kernel(rua_layout J
 }
 
 // ---------------------------------------------------------------- the move
-// 16 bytes of a row (fewer at its end: `nb`) in accesses of W bytes
-template <int W> struct jn_word;
-template <> struct jn_word<16> { using t = uint4; };
-template <> struct jn_word<8> { using t = uint2; };
-template <> struct jn_word<4> { using t = uint32_t; };
-template <> struct jn_word<2> { using t = uint16_t; };
-template <> struct jn_word<1> { using t = uint8_t; };
-struct alignas(16) jn_vec { uint32_t d[4]; };
-
-template <int W> __device__ __forceinline__ void jn_ld(const char* p, int nb, jn_vec& v) {
-  using T = typename jn_word<W>::t;
-#pragma unroll
-  for (int i = 0; i < 16 / W; ++i) if (i * W < nb) ((T*)&v)[i] = ((const T*)p)[i];
-}
-template <int W> __device__ __forceinline__ void jn_st(char* p, int nb, const jn_vec& v) {
-  using T = typename jn_word<W>::t;
-#pragma unroll
-  for (int i = 0; i < 16 / W; ++i) if (i * W < nb) ((T*)p)[i] = ((const T*)&v)[i];
-}
-__device__ __forceinline__ void jn_zero(jn_vec& v) { v.d[0] = v.d[1] = v.d[2] = v.d[3] = 0u; }
-
 // padding rows of sequence b of a LEFT / RIGHT side, as zeros: the positions q, q + rs, ... of [0, T_phys), every thread
 // its pieces of the row.  A CAT storage that holds more rows than its lengths add up to (a join of device-only lengths
 // sizes it by the parts' storages) has spare rows behind its last sequence: the group of that sequence zeroes them.
 template <int W>
 __device__ __forceinline__ void jn_zero_padding(const rua_layout& D, char* data, int64_t b, int64_t dlen, int64_t rb,
                                                 int q, int rs, int64_t col0, int64_t colstep) {
-  jn_vec z;
-  jn_zero(z);
+  row_vec z;
+  row_zero(z);
   if (D.kind == RUA_CAT && b == D.B - 1) {
     int64_t row = cat_off(D, b);
     if (row < 0) return;                         // (offsets that are no offsets: safe_len gave the sequence no token)
     for (row += dlen + q; row < D.n_rows; row += rs)
       for (int64_t col = col0; col < rb; col += colstep)
-        jn_st<W>(data + row * rb + col, rb - col >= 16 ? 16 : (int)(rb - col), z);
+        row_st<W>(data + row * rb + col, rb - col >= 16 ? 16 : (int)(rb - col), z);
     return;
   }
   if (D.kind != RUA_LEFT && D.kind != RUA_RIGHT) return;
@@ -116,7 +95,7 @@ __device__ __forceinline__ void jn_zero_padding(const rua_layout& D, char* data,
     const int64_t row = b * D.T_phys + j;
     if (row >= D.n_rows) continue;
     for (int64_t col = col0; col < rb; col += colstep)
-      jn_st<W>(data + row * rb + col, rb - col >= 16 ? 16 : (int)(rb - col), z);
+      row_st<W>(data + row * rb + col, rb - col >= 16 ? 16 : (int)(rb - col), z);
   }
 }
 
@@ -157,6 +136,7 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_join_kernel(rua_layout J, jn_pa
   const int64_t total = pre[JN_MAX_PARTS];
 
   // the tokens [tb, te) of the side that is written; the last block takes what a bound that understates left over
+  // (seg_block_range, spelled out: through the helper this kernel compiles to another instruction stream)
   int64_t tb = 0, te = unjoin ? total : jlen;
   if (maxblk > 0) {
     tb = (int64_t)blk * SEG_BLOCK_TOK;
@@ -200,15 +180,15 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_join_kernel(rua_layout J, jn_pa
     }
     for (int64_t col = col0; col < rb; col += colstep) {
       const int nb = rb - col >= 16 ? 16 : (int)(rb - col);
-      jn_vec v[JN_UNR];
+      row_vec v[JN_UNR];
 #pragma unroll
       for (int i = 0; i < JN_UNR; ++i) {
-        jn_zero(v[i]);
-        if (dst[i] && src[i]) jn_ld<W>(src[i] + col, nb, v[i]);
+        row_zero(v[i]);
+        if (dst[i] && src[i]) row_ld<W>(src[i] + col, nb, v[i]);
       }
 #pragma unroll
       for (int i = 0; i < JN_UNR; ++i)
-        if (dst[i]) jn_st<W>(dst[i] + col, nb, v[i]);
+        if (dst[i]) row_st<W>(dst[i] + col, nb, v[i]);
     }
   }
 
@@ -338,13 +318,7 @@ extern "C" int rua_segment_join(const rua_layout* joined, const rua_layout* part
 #define RUA_JN_LAUNCH(WV)                                                                                              \
   hipLaunchKernelGGL((seg_join_kernel<WV>), dim3((unsigned)p.grid), dim3(RUA_BLOCK), 0, (hipStream_t)stream, *joined,  \
                      P, (char*)joined_data, row_bytes, (int)n_parts, p.tg_log2, p.g_log2, p.maxblk, unjoin ? 1 : 0)
-  switch (p.W) {
-    case 16: RUA_JN_LAUNCH(16); break;
-    case 8:  RUA_JN_LAUNCH(8); break;
-    case 4:  RUA_JN_LAUNCH(4); break;
-    case 2:  RUA_JN_LAUNCH(2); break;
-    default: RUA_JN_LAUNCH(1); break;
-  }
+  RUA_DISPATCH_W(p.W, RUA_JN_LAUNCH)
 #undef RUA_JN_LAUNCH
   return (int)hipGetLastError();
 }

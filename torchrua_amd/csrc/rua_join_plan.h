@@ -23,7 +23,7 @@ enum jn_form { JN_LANES = 0, JN_WAVE = 1, JN_ROWS = 2 };
 
 struct jn_plan {
   int form;          // enum jn_form
-  int W;             // bytes per access: the widest power of two <= 16 that divides the row and every base address
+  int W;             // bytes per access: seg_access_width of the row and every base address
   int tg_log2;       // log2 of the threads that walk one unit: 5, 6 or 8
   int g_log2;        // log2 of the threads that own one row: 0 .. 6 (16 bytes each per step; rows beyond 1 KiB loop)
   int maxblk;        // > 0: cut, with this many blocks per sequence
@@ -33,8 +33,7 @@ struct jn_plan {
 // `J` is the JOINED side's layout (the destination of a join, the source of an unjoin): its sequences are the units
 static jn_plan jn_make_plan(const rua_layout& J, int64_t row_bytes, uint64_t bases) {
   jn_plan p = {JN_LANES, 1, 5, 0, 0, 0};
-  const uint64_t mix = (uint64_t)row_bytes | bases | 16u;
-  p.W = (int)(mix & (~mix + 1));
+  p.W = seg_access_width(row_bytes, bases);
   if (J.B <= 0 || row_bytes <= 0) return p;
   const int64_t pieces = (row_bytes - 1) / 16 + 1;
   while (p.g_log2 < 6 && ((int64_t)1 << p.g_log2) < pieces) ++p.g_log2;

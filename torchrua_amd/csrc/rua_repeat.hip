@@ -19,13 +19,10 @@
 #include <stdint.h>
 #include <string.h>
 #include <atomic>
-#include "rua_seg.h"
+#include "rua_seg_scan.h"
 #include "rua_repeat_plan.h"
 
 namespace rua {
-
-extern std::atomic<int> g_trace_on;        // the dispatch trace (rua_reduce.hip)
-void trace_add(const char* rec);
 
 constexpr int RM_UNR = 4;                  // tokens in flight per thread
 constexpr int RM_STAGE = SEG_BLOCK_TOK;    // `first` entries a workgroup stages per block of destination tokens
@@ -33,123 +30,36 @@ static_assert(RUA_WAVE == 64, "the scans below shuffle inside 64 lanes");
 static_assert(RUA_BLOCK == 256, "a row chunk of eight 16-byte pieces on 32 token slots, or a token per thread");
 
 // ---------------------------------------------------------------- the plan
-// G lanes walk one sequence, G tokens per step: 32 (two sequences per wave), 64 (a wave per sequence) or 256 (a
-// workgroup per sequence, or — maxblk > 0, the cut form — per block of SEG_BLOCK_TOK tokens of one).  Inside a wave the
-// sum in front of a lane is a shuffle scan; a workgroup adds the sums of the waves below through LDS; the sum of the
-// steps before is carried in a register.
-// phase 0: `first` and new_lens in one launch.  The cut form takes two: phase 1 leaves every block's sum in
-// ws[b * maxblk + blk] and counts the invalid entries; phase 2 adds the sums of the blocks before its own in block order
-// and writes `first`, the last block also new_lens.  Padding rows of a LEFT / RIGHT storage get -1 (block 0 writes them).
-template <int G>
-__global__ __launch_bounds__(RUA_BLOCK) void seg_repeat_plan_kernel(rua_layout L, const int64_t* __restrict__ counts,
-                                                                    int64_t* __restrict__ first,
-                                                                    int64_t* __restrict__ new_lens, int maxblk,
-                                                                    int64_t* ws, int phase) {
-  constexpr int PER_WG = RUA_BLOCK / G;
-  constexpr int GW = G < RUA_WAVE ? G : RUA_WAVE;              // the lanes that scan together by shuffles
-  __shared__ int64_t wsum[RUA_WAVES_PER_BLOCK];
-  const int tid = threadIdx.x;
-  const int lane = tid & (RUA_WAVE - 1), w = tid >> 6;
-  const int q = tid % G;
-  int64_t b = (int64_t)blockIdx.x * PER_WG + tid / G;
-  int blk = 0;
-  if (G == RUA_BLOCK && maxblk > 0) {
-    blk = (int)(blockIdx.x % (unsigned)maxblk);
-    b = blockIdx.x / (unsigned)maxblk;
+// the family's offsets scan (rua_seg_scan.h) over the counts: a token's value is its count (an invalid one: counted,
+// taken as 0), the sum in front of a lane a shuffle scan, and every token stores the position of its first copy
+struct rp_scan {
+  using in_t = int64_t;
+  using out_t = int64_t;
+  using sum_t = int64_t;
+  using val_t = int64_t;
+  static constexpr bool COUNTS_INVALID = true;
+  static const char* kernel() { return "seg_repeat_plan_kernel"; }
+  static const char* phase1() { return "sum"; }
+  static __device__ __forceinline__ int64_t load(const int64_t* counts, int64_t row, int& bad) {
+    int64_t c = counts[row];
+    if (c < 0 || c > RP_MAX_COUNT) { c = 0; ++bad; }
+    return c;
   }
-  const bool have = b < L.B;
-  const int64_t len = have ? safe_len(L, b) : 0;
-  int64_t tb = 0, te = len;                                    // the tokens this unit takes; the last block takes
-  if (G == RUA_BLOCK && maxblk > 0) {                          // what a bound that understates left over
-    tb = (int64_t)blk * SEG_BLOCK_TOK;
-    if (blk < maxblk - 1 && te > tb + SEG_BLOCK_TOK) te = tb + SEG_BLOCK_TOK;
-    if (tb > te) tb = te;
-  }
-  int64_t span = te - tb;                                      // uniform over the lanes that shuffle together
-  if (G == 32) {
-    const int64_t other = __shfl_xor(span, 32, RUA_WAVE);
-    span = span > other ? span : other;
-  }
-
-  int64_t carried = 0;
-  int bad = 0;
-  if (phase == 2 && have) {
-    for (int i = 0; i < blk; ++i) carried += ws[b * maxblk + i];
-  }
-  for (int64_t u0 = 0; u0 < span; u0 += G) {
-    const int64_t t = tb + u0 + q;
-    int64_t row = -1, c = 0;
-    if (t < te) {
-      row = token_to_row(L, b, t, len);
-      if (row >= 0 && row < L.n_rows) {
-        c = counts[row];
-        if (c < 0 || c > RP_MAX_COUNT) { c = 0; ++bad; }
-      } else {
-        row = -1;
-      }
-    }
+  template <int G>
+  static __device__ __forceinline__ void wave_prefix(int64_t c, int lane, int q, int64_t& before, int64_t& total) {
+    constexpr int GW = G < RUA_WAVE ? G : RUA_WAVE;            // the lanes that scan together by shuffles
     int64_t inc = c;                                           // inclusive scan over the GW lanes
 #pragma unroll
     for (int d = 1; d < GW; d <<= 1) {
       const int64_t o = __shfl_up(inc, d, GW);
       if ((lane & (GW - 1)) >= d) inc += o;
     }
-    int64_t total = __shfl(inc, GW - 1, GW);
-    int64_t before = inc - c;
-    if (G == RUA_BLOCK) {
-      if (lane == 0) wsum[w] = total;
-      __syncthreads();                                         // (workgroup-uniform trip count: b and blk are)
-      total = 0;
-#pragma unroll
-      for (int i = 0; i < RUA_WAVES_PER_BLOCK; ++i) {
-        const int64_t s = wsum[i];
-        if (i < w) before += s;
-        total += s;
-      }
-      __syncthreads();
-    }
-    if (phase != 1 && row >= 0) first[row] = carried + before;
-    carried += total;
+    total = __shfl(inc, GW - 1, GW);
+    before = inc - c;
   }
-
-  if (!have) return;
-  // invalid counts are rare (the caller raises on any): a vector atomic per lane that met one, into the word the
-  // entry point zeroed
-  if (phase != 2 && bad > 0) atomicAdd((unsigned long long*)(new_lens + L.B), (unsigned long long)bad);
-  if (q == 0) {
-    if (phase == 1) ws[b * maxblk + blk] = carried;
-    else if (phase == 0 || blk == maxblk - 1) new_lens[b] = carried;
-  }
-  if (phase != 1 && blk == 0 && (L.kind == RUA_LEFT || L.kind == RUA_RIGHT)) {
-    for (int64_t j = q; j < L.T_phys; j += G) {
-      if (!is_pad(L, j, len)) continue;
-      const int64_t row = b * L.T_phys + j;
-      if (row < L.n_rows) first[row] = -1;
-    }
-  }
-}
-
-// ---------------------------------------------------------------- rows as bits
-// 16 bytes of a row (fewer at its end: `nb`) in accesses of W bytes, W a power of two that divides the row and the bases
-template <int W> struct rm_word;
-template <> struct rm_word<16> { using t = uint4; };
-template <> struct rm_word<8> { using t = uint2; };
-template <> struct rm_word<4> { using t = uint32_t; };
-template <> struct rm_word<2> { using t = uint16_t; };
-template <> struct rm_word<1> { using t = uint8_t; };
-struct alignas(16) rm_vec { uint32_t d[4]; };
-
-template <int W> __device__ __forceinline__ void rm_ld(const char* p, int nb, rm_vec& v) {
-  using T = typename rm_word<W>::t;
-#pragma unroll
-  for (int i = 0; i < 16 / W; ++i) if (i * W < nb) ((T*)&v)[i] = ((const T*)p)[i];
-}
-template <int W> __device__ __forceinline__ void rm_st(char* p, int nb, const rm_vec& v) {
-  using T = typename rm_word<W>::t;
-#pragma unroll
-  for (int i = 0; i < 16 / W; ++i) if (i * W < nb) ((T*)p)[i] = ((const T*)&v)[i];
-}
-__device__ __forceinline__ void rm_zero(rm_vec& v) { v.d[0] = v.d[1] = v.d[2] = v.d[3] = 0u; }
+  static __device__ __forceinline__ int64_t store(int64_t, int64_t pos) { return pos; }
+};
+static_assert(sizeof(rp_scan::sum_t) == RP_WS_ELEM_BYTES, "the workspace the host plan sizes holds the kernel's sums");
 
 // first[] of source token (b, t); a token whose row is not in the storage never matches
 __device__ __forceinline__ int64_t rm_first(const rua_layout& S, const int64_t* __restrict__ first, int64_t b, int64_t t,
@@ -229,12 +139,12 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_repeat_move_kernel(rua_layout D
     if (nb > 0) {
       for (int64_t u0 = ub + q; u0 < ue; u0 += (int64_t)slots * RM_UNR) {
         int64_t drows[RM_UNR], srows[RM_UNR];
-        rm_vec v[RM_UNR];
+        row_vec v[RM_UNR];
 #pragma unroll
         for (int i = 0; i < RM_UNR; ++i) {
           const int64_t u = u0 + (int64_t)i * slots;
           drows[i] = srows[i] = -1;
-          rm_zero(v[i]);
+          row_zero(v[i]);
           if (u >= ue) continue;
           const int64_t drow = token_to_row(D, b, u, dlen);
           if (drow < 0 || drow >= D.n_rows) continue;
@@ -259,10 +169,10 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_repeat_move_kernel(rua_layout D
         }
 #pragma unroll
         for (int i = 0; i < RM_UNR; ++i)
-          if (srows[i] >= 0) rm_ld<W>(src + srows[i] * rb + col0, nb, v[i]);
+          if (srows[i] >= 0) row_ld<W>(src + srows[i] * rb + col0, nb, v[i]);
 #pragma unroll
         for (int i = 0; i < RM_UNR; ++i)
-          if (drows[i] >= 0) rm_st<W>(dst + drows[i] * rb + col0, nb, v[i]);
+          if (drows[i] >= 0) row_st<W>(dst + drows[i] * rb + col0, nb, v[i]);
       }
     }
     if (one_block) break;
@@ -270,12 +180,12 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_repeat_move_kernel(rua_layout D
 
   // padding rows of a LEFT / RIGHT destination as zeros: position q, q + slots, ... of [0, T_phys)
   if (k0 == 0 && nb > 0 && (D.kind == RUA_LEFT || D.kind == RUA_RIGHT)) {
-    rm_vec z;
-    rm_zero(z);
+    row_vec z;
+    row_zero(z);
     for (int64_t j = q; j < D.T_phys; j += slots) {
       if (!is_pad(D, j, dlen)) continue;
       const int64_t row = b * D.T_phys + j;
-      if (row < D.n_rows) rm_st<W>(dst + row * rb + col0, nb, z);
+      if (row < D.n_rows) row_st<W>(dst + row * rb + col0, nb, z);
     }
   }
 }
@@ -368,68 +278,9 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_repeat_sum_kernel(rua_layout S,
 }
 
 // ---------------------------------------------------------------- host side
-static const char* rp_form_name(int form) {
-  switch (form) {
-    case RP_LANES: return "lanes";
-    case RP_ROWS:  return "rows";
-    case RP_LONG:  return "long";
-    case RP_CUT:   return "cut";
-  }
-  return "?";
-}
-
-static int rp_launch_plan(const rua_layout& L, const int64_t* counts, int64_t* first, int64_t* new_lens, void* ws,
-                          hipStream_t s) {
-  rp_plan p = rp_make_plan(L);
-  if (p.form == RP_CUT && !ws) {                               // ws == NULL: do not cut
-    p.form = RP_LONG;
-    p.maxblk = 0;
-    p.grid = L.B;
-  }
-  if (p.grid <= 0 || p.grid > 0x7fffffffLL) return RUA_ERANGE;
-  int e = (int)hipMemsetAsync(new_lens + L.B, 0, sizeof(int64_t), s);      // the invalid-count word
-  if (e) return e;
-  const bool tr = g_trace_on.load(std::memory_order_relaxed) != 0;
-  char rec[200];
-  const dim3 grid((unsigned)p.grid), block(RUA_BLOCK);
-  auto note = [&](const char* phase) {
-    if (!tr) return;
-    snprintf(rec, sizeof rec, "seg_repeat_plan_kernel form=%s G=%d kind=%d cut=%d blocks=%d phase=%s",
-             rp_form_name(p.form), RUA_BLOCK / p.per_wg, L.kind, (int)(p.form == RP_CUT), p.maxblk, phase);
-    trace_add(rec);
-  };
-  switch (p.form) {
-    case RP_LANES:
-      note("whole");
-      hipLaunchKernelGGL((seg_repeat_plan_kernel<32>), grid, block, 0, s, L, counts, first, new_lens, 0, nullptr, 0);
-      break;
-    case RP_ROWS:
-      note("whole");
-      hipLaunchKernelGGL((seg_repeat_plan_kernel<64>), grid, block, 0, s, L, counts, first, new_lens, 0, nullptr, 0);
-      break;
-    case RP_LONG:
-      note("whole");
-      hipLaunchKernelGGL((seg_repeat_plan_kernel<RUA_BLOCK>), grid, block, 0, s, L, counts, first, new_lens, 0, nullptr, 0);
-      break;
-    case RP_CUT: {
-      note("sum");
-      hipLaunchKernelGGL((seg_repeat_plan_kernel<RUA_BLOCK>), grid, block, 0, s, L, counts, first, new_lens, p.maxblk,
-                         (int64_t*)ws, 1);
-      e = (int)hipGetLastError();
-      if (e) return e;
-      note("finish");
-      hipLaunchKernelGGL((seg_repeat_plan_kernel<RUA_BLOCK>), grid, block, 0, s, L, counts, first, new_lens, p.maxblk,
-                         (int64_t*)ws, 2);
-      break;
-    }
-  }
-  return (int)hipGetLastError();
-}
-
 static int rm_launch_move(const rua_layout& D, const rua_layout& S, const int64_t* first, int64_t uniform, char* dst,
                           const char* src, int64_t rb, hipStream_t s) {
-  const uint64_t mix = (uint64_t)rb | (uint64_t)(uintptr_t)dst | (uint64_t)(uintptr_t)src | 16u;
-  const int W = (int)(mix & (~mix + 1));                      // the widest access that divides the row and the bases
+  const int W = seg_access_width(rb, (uint64_t)(uintptr_t)dst | (uint64_t)(uintptr_t)src);
   const rp_walk w = rp_make_walk(D, rb);
   if (!w.grid) return RUA_ERANGE;
   if (g_trace_on.load(std::memory_order_relaxed) != 0) {
@@ -442,13 +293,7 @@ static int rm_launch_move(const rua_layout& D, const rua_layout& S, const int64_
 #define RUA_RM_MOVE(WV)                                                                                                \
   hipLaunchKernelGGL((seg_repeat_move_kernel<WV>), dim3((unsigned)w.grid), dim3(RUA_BLOCK), 0, s, D, S, first, uniform,  \
                      dst, src, rb, w.n_chunks, w.lpr_log2, w.maxblk)
-  switch (W) {
-    case 16: RUA_RM_MOVE(16); break;
-    case 8:  RUA_RM_MOVE(8); break;
-    case 4:  RUA_RM_MOVE(4); break;
-    case 2:  RUA_RM_MOVE(2); break;
-    default: RUA_RM_MOVE(1); break;
-  }
+  RUA_DISPATCH_W(W, RUA_RM_MOVE)
 #undef RUA_RM_MOVE
   return (int)hipGetLastError();
 }
@@ -478,7 +323,7 @@ static int rs_launch_sum(const rua_layout& S, const rua_layout& D, const int64_t
 extern "C" int64_t rua_repeat_ws_bytes(const rua_layout* lay) {
   using namespace rua;
   if (seg_check_entry(lay, 1, 1) != 0) return 0;
-  return rp_make_plan(*lay).ws_bytes;
+  return seg_make_scan_plan(*lay, RP_WS_ELEM_BYTES).ws_bytes;
 }
 
 extern "C" int rua_segment_repeat_plan(const rua_layout* lay, const int64_t* counts, int64_t* first, int64_t* new_lens,
@@ -494,7 +339,16 @@ extern "C" int rua_segment_repeat_plan(const rua_layout* lay, const int64_t* cou
   if ((uint64_t)(uintptr_t)counts % 8 || (uint64_t)(uintptr_t)first % 8 || (uint64_t)(uintptr_t)new_lens % 8 ||
       (uint64_t)(uintptr_t)ws % 8)
     return RUA_EALIGN;
-  return rp_launch_plan(*lay, counts, first, new_lens, ws, (hipStream_t)stream);
+  seg_scan_plan p = seg_make_scan_plan(*lay, RP_WS_ELEM_BYTES);
+  if (p.form == SEG_SCAN_CUT && !ws) {                         // ws == NULL: do not cut
+    p.form = SEG_SCAN_LONG;
+    p.maxblk = 0;
+    p.grid = lay->B;
+  }
+  if (p.grid <= 0 || p.grid > 0x7fffffffLL) return RUA_ERANGE;
+  hipStream_t s = (hipStream_t)stream;
+  if ((e = (int)hipMemsetAsync(new_lens + lay->B, 0, sizeof(int64_t), s)) != 0) return e;    // the invalid-count word
+  return seg_launch_offsets<rp_scan>(p, *lay, counts, first, new_lens, ws, s);
 }
 
 extern "C" int rua_segment_repeat_move(const rua_layout* dst, const rua_layout* src, const int64_t* first,

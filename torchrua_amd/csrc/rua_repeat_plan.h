@@ -1,52 +1,15 @@
-// rua_repeat_plan.h — what the per-sequence repeat_interleave (rua_repeat.hip) decides BEFORE its first HIP call, as
-// plain host C++ (no HIP header): which of its four forms scans the counts, the launch geometry of that form and the
-// workspace of the cut form; and the grid of the move and of the run sum.  Layout and entry checks, the length bound
-// and the cut rule are rua_seg_plan.h.  tests/c/repeat_plan_host.cpp walks this header alone.
+// rua_repeat_plan.h — what the per-sequence repeat_interleave (rua_repeat.hip) decides BEFORE its first HIP call beyond
+// rua_seg_plan.h, as plain host C++ (no HIP header): the counts it takes, the element of its workspace and the grid of
+// the move and of the run sum.  The forms of the plan, its grid and its workspace are the family's offsets scan
+// (seg_make_scan_plan); layout and entry checks, the length bound and the cut rule are rua_seg_plan.h too.
+// tests/c/repeat_plan_host.cpp walks this header.
 #pragma once
 #include "rua_seg_plan.h"
 
 namespace rua {
 
-// the plan scans one int64 count per token, so its forms go by the length bound, as the compress plan's do:
-//   RP_LANES  bound <= 64: two sequences per wave, 32 lanes each (8 per workgroup)
-//   RP_ROWS   bound < SEG_BLOCK_TOK: a wave per sequence, 64 tokens per step (4 per workgroup)
-//   RP_LONG   longer (or unknown: CAT lengths the host never saw): a workgroup per sequence, 256 tokens per step, the
-//             sum carried from step to step
-//   RP_CUT    the family's cut rule over B units (seg_cut_blocks): a workgroup per (sequence, block), two launches, the
-//             blocks' sums in the workspace
-enum rp_form { RP_LANES = 0, RP_ROWS = 1, RP_LONG = 2, RP_CUT = 3 };
-
-constexpr int64_t RP_LANES_MAX_LEN = 64;
 constexpr int64_t RP_MAX_COUNT = 0x7fffffffLL;   // a count above this (or below 0) is invalid: counted, taken as 0
-
-struct rp_plan {
-  int form;           // enum rp_form
-  int per_wg;         // sequences a workgroup takes (CUT: 1 unit)
-  int maxblk;         // CUT: blocks per sequence, else 0
-  int64_t grid;       // workgroups; 0 = nothing to launch or it does not fit (RUA_ERANGE when B > 0)
-  int64_t ws_bytes;   // CUT: one int64 per (sequence, block), else 0
-};
-
-static rp_plan rp_make_plan(const rua_layout& L) {
-  rp_plan p = {RP_LANES, 2 * SEG_WAVES_PER_BLOCK, 0, 0, 0};
-  if (L.B <= 0) return p;
-  const int64_t bound = sm_len_bound(L);
-  const int64_t mb = seg_cut_blocks(L, L.B);
-  if (mb > 0 && mb <= SEG_CUT_MAX_BLOCKS) {
-    p.form = RP_CUT;
-    p.per_wg = 1;
-    p.maxblk = (int)mb;
-    p.grid = L.B * mb;                            // < SEG_CUT_MAX_UNITS * SEG_CUT_MAX_BLOCKS <= 2^31 - 1
-    p.ws_bytes = L.B * mb * 8;
-    return p;
-  }
-  if (bound <= RP_LANES_MAX_LEN) { p.form = RP_LANES; p.per_wg = 2 * SEG_WAVES_PER_BLOCK; }
-  else if (bound < SEG_BLOCK_TOK) { p.form = RP_ROWS; p.per_wg = SEG_WAVES_PER_BLOCK; }
-  else { p.form = RP_LONG; p.per_wg = 1; }
-  const int64_t grid = (L.B - 1) / p.per_wg + 1;  // (B itself may be 2^63 - 1)
-  p.grid = grid > 0x7fffffffLL ? 0 : grid;
-  return p;
-}
+constexpr int RP_WS_ELEM_BYTES = 8;              // the cut form keeps one int64 sum per (sequence, block)
 
 // the move (walked by the DESTINATION's sequences) and the run sum (walked by the SOURCE's): a workgroup per (sequence,
 // 128-byte column chunk) that walks the sequence block by block, or — the cut rule over B * chunks units of the layout

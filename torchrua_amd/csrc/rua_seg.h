@@ -1,7 +1,8 @@
 // rua_seg.h — what the kernels of the per-sequence operators (rua_softmax.hip, rua_scan.hip, rua_argreduce.hip,
-// rua_linear_scan.hip, rua_pool.hip, rua_norm.hip) share: the element types, the clamped sequence length, the padding
-// test, narrow-row accesses and the exp / log / inf / nan / shuffle one-liners.  Their host side — checks, cut plan,
-// lanes geometry — is rua_seg_plan.h.
+// rua_linear_scan.hip, rua_pool.hip, rua_norm.hip, rua_conv.hip, rua_compress.hip, rua_join.hip, rua_repeat.hip) share:
+// the element types, the clamped sequence length, the padding test and fill, the block range of the cut form, rows
+// moved as bits, narrow-row accesses and the exp / log / inf / nan / shuffle one-liners.  Their host side — checks, cut
+// plan, lanes geometry, access width — is rua_seg_plan.h; the offsets scan of compress and repeat is rua_seg_scan.h.
 #pragma once
 #include "rua_dev.h"
 #include "rua_seg_plan.h"
@@ -66,7 +67,66 @@ __device__ __forceinline__ bool is_pad(const rua_layout& L, int64_t j, int64_t l
   return j < lo || j >= L.T_log;
 }
 
-// `nb` bytes (a row) in pieces of W bytes, W a power of two that divides nb and every base address
+// the tokens [tb, te) of a sequence of `len` that block `blk` of `maxblk` takes (maxblk == 0: all of them).  The last
+// block takes what a length bound that understates left over: every token is walked
+__device__ __forceinline__ void seg_block_range(int maxblk, int blk, int64_t len, int64_t& tb, int64_t& te) {
+  tb = 0;
+  te = len;
+  if (maxblk > 0) {
+    tb = (int64_t)blk * SEG_BLOCK_TOK;
+    if (blk < maxblk - 1 && te > tb + SEG_BLOCK_TOK) te = tb + SEG_BLOCK_TOK;
+    if (tb > te) tb = te;
+  }
+}
+
+// the padding rows of sequence b of a LEFT / RIGHT storage: st(row) for the positions j0, j0 + step, ... of [0, T_phys)
+// that hold no token (zeros in the compress moves, -1 in the tables of rua_seg_scan.h; rua_join.hip and rua_repeat.hip
+// keep this loop spelled out in their kernels, which compile to another instruction schedule through it)
+template <typename St>
+__device__ __forceinline__ void seg_fill_padding(const rua_layout& D, int64_t b, int64_t dlen, int j0, int step, St st) {
+  if (D.kind != RUA_LEFT && D.kind != RUA_RIGHT) return;
+  for (int64_t j = j0; j < D.T_phys; j += step) {
+    if (!is_pad(D, j, dlen)) continue;
+    const int64_t row = b * D.T_phys + j;
+    if (row < D.n_rows) st(row);
+  }
+}
+
+// ---------------------------------------------------------------- rows as bits (compress, join, repeat_interleave)
+// 16 bytes of a row (fewer at its end: `nb`) in accesses of W bytes, W = seg_access_width: a power of two that divides
+// the row and every base address.  W is a template argument: the launchers pick the kernel with RUA_DISPATCH_W
+template <int W> struct row_word;
+template <> struct row_word<16> { using t = uint4; };
+template <> struct row_word<8> { using t = uint2; };
+template <> struct row_word<4> { using t = uint32_t; };
+template <> struct row_word<2> { using t = uint16_t; };
+template <> struct row_word<1> { using t = uint8_t; };
+struct alignas(16) row_vec { uint32_t d[4]; };
+
+template <int W> __device__ __forceinline__ void row_ld(const char* p, int nb, row_vec& v) {
+  using T = typename row_word<W>::t;
+#pragma unroll
+  for (int i = 0; i < 16 / W; ++i) if (i * W < nb) ((T*)&v)[i] = ((const T*)p)[i];
+}
+template <int W> __device__ __forceinline__ void row_st(char* p, int nb, const row_vec& v) {
+  using T = typename row_word<W>::t;
+#pragma unroll
+  for (int i = 0; i < 16 / W; ++i) if (i * W < nb) ((T*)p)[i] = ((const T*)&v)[i];
+}
+__device__ __forceinline__ void row_zero(row_vec& v) { v.d[0] = v.d[1] = v.d[2] = v.d[3] = 0u; }
+
+// LAUNCH(16 | 8 | 4 | 2 | 1) for the access width W of a launch
+#define RUA_DISPATCH_W(W, LAUNCH)                                                                                      \
+  switch (W) {                                                                                                         \
+    case 16: LAUNCH(16); break;                                                                                        \
+    case 8:  LAUNCH(8); break;                                                                                         \
+    case 4:  LAUNCH(4); break;                                                                                         \
+    case 2:  LAUNCH(2); break;                                                                                         \
+    default: LAUNCH(1); break;                                                                                         \
+  }
+
+// `nb` bytes (a row) in pieces of W bytes, W a power of two that divides nb and every base address.  (W at run time,
+// for the fold operators, whose kernels are instantiated by element type; the movers above take row_ld<W> / row_st<W>)
 __device__ __forceinline__ void ld_row_w(const char* p, int nb, int W, void* dst) {
   if (W == 16) { *(uint4*)dst = *(const uint4*)p; return; }
   if (W == 8) {

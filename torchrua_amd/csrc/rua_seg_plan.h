@@ -1,7 +1,8 @@
-// rua_seg_plan.h — what the per-sequence operators (softmax, cumsum, argreduce, linear_scan, softmax_pool, norm)
-// decide BEFORE their first HIP call, as plain host C++ (no HIP header): the element size, the layout and entry checks,
-// the cut plan and the launch geometry of the lanes form.  One place for all of them: a new operator of the family
-// takes these and adds only its kernels, its pointer checks and the bytes it keeps per (block, padded column).
+// rua_seg_plan.h — what the per-sequence operators (softmax, cumsum, argreduce, linear_scan, softmax_pool, norm, conv,
+// compress, join, repeat_interleave) decide BEFORE their first HIP call, as plain host C++ (no HIP header): the element
+// size, the layout and entry checks, the cut plan, the launch geometry of the lanes form, the access width of the
+// operators that move rows as bits and the plan of the offsets scan.  One place for all of them: a new operator of the
+// family takes these and adds only its kernels, its pointer checks and the bytes it keeps per (block, padded column).
 #pragma once
 #include <stdint.h>
 #include "rua.h"
@@ -93,14 +94,62 @@ static int64_t seg_rows_grid(const rua_layout& L, const seg_plan& p, bool cut) {
   return p.n_chunks <= 0 || grid > 0x7fffffffLL ? 0 : grid;
 }
 
-// the lanes form (rows of one vector): two sequences per wave; W = the widest power of two, up to 16 bytes, that
-// divides the row and every base address.  grid == 0: B does not fit (RUA_ERANGE)
+// bytes per access of the operators that move rows as bits: the widest power of two, up to 16, that divides the row and
+// every base address (`bases`: the addresses ORed together)
+static int seg_access_width(int64_t row_bytes, uint64_t bases) {
+  const uint64_t mix = (uint64_t)row_bytes | bases | 16u;
+  return (int)(mix & (~mix + 1));
+}
+
+// the lanes form (rows of one vector): two sequences per wave; W = seg_access_width.  grid == 0: B does not fit
+// (RUA_ERANGE)
 struct seg_lanes { int W; int64_t grid; };
 static seg_lanes seg_lanes_geometry(int64_t row_bytes, uint64_t bases, int64_t B) {
-  const uint64_t mix = (uint64_t)row_bytes | bases | 16u;
   const int64_t waves = (B + 1) / 2;
   const int64_t grid = (waves + SEG_WAVES_PER_BLOCK - 1) / SEG_WAVES_PER_BLOCK;
-  return {(int)(mix & (~mix + 1)), grid > 0x7fffffffLL ? 0 : grid};
+  return {seg_access_width(row_bytes, bases), grid > 0x7fffffffLL ? 0 : grid};
+}
+
+// ---------------------------------------------------------------- the offsets scan (compress, repeat_interleave)
+// The operators whose result has another raggedness than their input scan ONE value per token (a 1-byte mask, an int64
+// count) per sequence, so the forms of that scan go by the length bound, not by the row width:
+//   SEG_SCAN_LANES  bound <= 64: two sequences per wave, 32 lanes each (8 per workgroup)
+//   SEG_SCAN_ROWS   bound < SEG_BLOCK_TOK: a wave per sequence, 64 tokens per step (4 per workgroup)
+//   SEG_SCAN_LONG   longer (or unknown: CAT lengths the host never saw): a workgroup per sequence, 256 tokens per step,
+//                   the sum carried from step to step
+//   SEG_SCAN_CUT    the family's cut rule over B units (seg_cut_blocks): a workgroup per (sequence, block), two launches,
+//                   the blocks' sums in the workspace
+enum seg_scan_form { SEG_SCAN_LANES = 0, SEG_SCAN_ROWS = 1, SEG_SCAN_LONG = 2, SEG_SCAN_CUT = 3 };
+
+constexpr int64_t SEG_SCAN_LANES_MAX_LEN = 64;
+
+struct seg_scan_plan {
+  int form;           // enum seg_scan_form
+  int per_wg;         // sequences a workgroup takes (CUT: 1 unit)
+  int maxblk;         // CUT: blocks per sequence, else 0
+  int64_t grid;       // workgroups; 0 = nothing to launch or it does not fit (RUA_ERANGE when B > 0)
+  int64_t ws_bytes;   // CUT: one sum of `ws_elem_bytes` per (sequence, block), else 0
+};
+
+static seg_scan_plan seg_make_scan_plan(const rua_layout& L, int ws_elem_bytes) {
+  seg_scan_plan p = {SEG_SCAN_LANES, 2 * SEG_WAVES_PER_BLOCK, 0, 0, 0};
+  if (L.B <= 0) return p;
+  const int64_t bound = sm_len_bound(L);
+  const int64_t mb = seg_cut_blocks(L, L.B);
+  if (mb > 0 && mb <= SEG_CUT_MAX_BLOCKS) {
+    p.form = SEG_SCAN_CUT;
+    p.per_wg = 1;
+    p.maxblk = (int)mb;
+    p.grid = L.B * mb;                            // < SEG_CUT_MAX_UNITS * SEG_CUT_MAX_BLOCKS <= 2^31 - 1
+    p.ws_bytes = L.B * mb * ws_elem_bytes;
+    return p;
+  }
+  if (bound <= SEG_SCAN_LANES_MAX_LEN) { p.form = SEG_SCAN_LANES; p.per_wg = 2 * SEG_WAVES_PER_BLOCK; }
+  else if (bound < SEG_BLOCK_TOK) { p.form = SEG_SCAN_ROWS; p.per_wg = SEG_WAVES_PER_BLOCK; }
+  else { p.form = SEG_SCAN_LONG; p.per_wg = 1; }
+  const int64_t grid = (L.B - 1) / p.per_wg + 1;  // (B - 1) / per_wg + 1: B itself may be 2^63 - 1
+  p.grid = grid > 0x7fffffffLL ? 0 : grid;
+  return p;
 }
 
 }  // namespace rua

@@ -64,7 +64,7 @@ from torch import Tensor
 from torchrua_amd import _lib as K
 from torchrua_amd import _meta as M
 from torchrua_amd import _ops as O
-from torchrua_amd.core import _pack_meta
+from torchrua_amd.core import result_like
 from torchrua_amd.layout import C, L, P, R, T, Z, lay_hidden, lens_of
 
 __all__ = ['join', 'unjoin', 'segment_join', 'segment_unjoin']
@@ -195,25 +195,6 @@ def _lens_lay(x, B: int) -> M.Lay:
     return _part_lay(x, B)
 
 
-def _result(cls, sizes: Tensor, B: int, hidden: Tuple[int, ...], like: Tensor, n: Optional[int] = None):
-    """(layout, storage shape, payload -> container) of a `cls` result with the lengths `sizes`, through the paths the
-    casts use: the device scan (C), the host sort + rua_pack_prepare (P: core._pack_meta), the longest sequence (L / R).
-    `n`: the storage rows of a C whose lengths the host does not know."""
-    if cls is C:
-        n = M.total_len(sizes) if n is None else n
-        return M.lay_cat(sizes, B, n), (n,) + hidden, lambda data: C(data=data, token_sizes=sizes)
-    if cls is P:
-        lens, sorted_indices, unsorted, batch_sizes, bsz_dev, boff = _pack_meta(sizes, like.device)
-        n = M.total_len(sizes)
-        shell = P(data=like, batch_sizes=batch_sizes, sorted_indices=sorted_indices, unsorted_indices=unsorted)
-        M.adopt_pack(shell, lens, boff, bsz_dev)
-        lay = M.lay_pack(shell, lens=lens, boff=boff, T=batch_sizes.numel(), n_rows=n)
-        return lay, (n,) + hidden, lambda data: shell._replace(data=data)
-    t = M.max_len(sizes)
-    lay = M.lay_padded(K.LEFT if cls is L else K.RIGHT, sizes, B, t, t)
-    return lay, (B, t) + hidden, lambda data: cls(data=data, token_sizes=sizes)
-
-
 def join(sequences: Sequence[Union[Z, T]]) -> Z:
     """The parts glued together along time, sequence by sequence; a container of the parts' type.  See the module
     docstring."""
@@ -245,7 +226,7 @@ def join(sequences: Sequence[Union[Z, T]]) -> Z:
             if not _host_known(v):
                 M.attach_host(v, host[k + 1].to(v.dtype))
         lays = [_part_lay(x, B) for x in parts]
-    joined, shape, wrap = _result(cls, sizes, B, hidden, datas[0], n)
+    joined, shape, wrap = result_like(cls, sizes, B, hidden, datas[0], n)
     plan = O.JoinPlan(joined, lays, hidden, shape, [tuple(d.shape) for d in datas])
     return wrap(O.join(datas, plan))
 
@@ -283,7 +264,7 @@ def unjoin(sequence: Z, sizes: Sequence[Union[T, int]]) -> List[Z]:
     for k in range(len(sizes)):
         part_sizes = buf[k]                       # (ONE tensor object per part: the memo lives on the object)
         M.attach_host(part_sizes, host[k])
-        plans.append(_result(cls, part_sizes, B, hidden, sequence.data))
+        plans.append(result_like(cls, part_sizes, B, hidden, sequence.data))
     plan = O.JoinPlan(joined, [p[0] for p in plans], hidden, tuple(sequence.data.shape), [p[1] for p in plans])
     outs = O.unjoin(sequence.data, plan)
     return [p[2](out) for p, out in zip(plans, outs)]

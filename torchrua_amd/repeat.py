@@ -67,7 +67,7 @@ from torch import Tensor
 from torchrua_amd import _lib as K
 from torchrua_amd import _meta as M
 from torchrua_amd import _ops as O
-from torchrua_amd.core import _pack_meta
+from torchrua_amd.core import result_like
 from torchrua_amd.layout import C, L, P, R, T, Z, cat_lay, lay_hidden, lens_of
 
 __all__ = ['segment_repeat_interleave', 'repeat_interleave']
@@ -160,32 +160,16 @@ def repeat_interleave(sequence: Z, repeats) -> Z:
     lead = 1 if isinstance(sequence, (C, P)) else 2
     repeats = _check_repeats(repeats, tuple(data.shape[:lead]), data, 'repeat_interleave')
     src, hidden = lay_hidden(sequence)
-    dev = data.device
     first, counts, uniform, new_sizes = _new_lengths(src, lens_of(sequence), repeats, 'repeat_interleave')
-    B = src.B
-    args = (first, counts, uniform)
-    if isinstance(sequence, C):
-        # (an int count: N * r rows, known without a look at the lengths — a C result never synchronises)
-        n = int(data.size(0)) * uniform if first is None else M.total_len(new_sizes)
-        dst, shape = M.lay_cat(new_sizes, B, n), (n,) + hidden
-        return C(data=O.repeat(data, *args, dst, src, hidden, shape, tuple(data.shape)), token_sizes=new_sizes)
-    if isinstance(sequence, P):
-        # (an int count and lengths the host never saw: the read-back pack() would do, BEFORE batch_sizes is sized by it)
+    # (a C and an int count: N * r rows, known without a look at the lengths — a C result never synchronises)
+    n = int(data.size(0)) * uniform if isinstance(sequence, C) and first is None else None
+    if not isinstance(sequence, C):
+        # (an int count and lengths the host never saw: the read-back the cast would do, BEFORE anything — batch_sizes
+        # of a P, the storage of an L / R — is sized by it; the new lengths are known only now)
         M.max_len(new_sizes)
         _too_long(new_sizes, 'repeat_interleave')
-        # the metadata C.pack() derives from these lengths: the reference's host sort, batch_sizes, the device scans
-        lens, sorted_indices, unsorted, batch_sizes, bsz_dev, boff = _pack_meta(new_sizes, dev)
-        n = M.total_len(new_sizes)
-        shell = P(data=data, batch_sizes=batch_sizes, sorted_indices=sorted_indices, unsorted_indices=unsorted)
-        M.adopt_pack(shell, lens, boff, bsz_dev)
-        dst = M.lay_pack(shell, lens=lens, boff=boff, T=batch_sizes.numel(), n_rows=n)
-        return shell._replace(data=O.repeat(data, *args, dst, src, hidden, (n,) + hidden, tuple(data.shape)))
-    kind = K.LEFT if isinstance(sequence, L) else K.RIGHT
-    t = M.max_len(new_sizes)
-    _too_long(new_sizes, 'repeat_interleave')           # (an int count and lengths the host never saw: known only now)
-    dst, shape = M.lay_padded(kind, new_sizes, B, t, t), (B, t) + hidden
-    return type(sequence)(data=O.repeat(data, *args, dst, src, hidden, shape, tuple(data.shape)),
-                          token_sizes=new_sizes)
+    dst, shape, wrap = result_like(type(sequence), new_sizes, src.B, hidden, data, n)
+    return wrap(O.repeat(data, first, counts, uniform, dst, src, hidden, shape, tuple(data.shape)))
 
 
 for _cls in (C, L, P, R):
