@@ -4,6 +4,8 @@
 // A violation is a plan the launchers could not launch as they compute it: a grid beyond 2^31 - 1 workgroups that
 // seg_rows_grid / seg_lanes_geometry did not refuse, a block or chunk count that does not cover the bound or the row,
 // a workspace that is not exactly one slot per (sequence, block, chunk, padded column), or a cut outside the rule.
+// seg_rows_form (al, cut and the grid of a rows launch) and seg_slab_cap (the resident slab of softmax and norm) are
+// walked over the same plans: a cut without its workspace, a slab for a cut or a long sequence, a slab beyond its cap.
 // The plan of the offsets scan (seg_make_scan_plan: compress, repeat_interleave) is walked here too, for both workspace
 // elements, over B up to 2^40 and bounds up to 2^36: a form outside its rule, a grid that does not cover every sequence
 // (or, cut, every block) or exceeds what a launch takes, a workspace that is not one element per (sequence, block).
@@ -15,7 +17,7 @@
 
 using namespace rua;
 
-static long long plans = 0, cuts = 0, scan_plans = 0, scan_cuts = 0, scan_forms[4] = {0, 0, 0, 0};
+static long long plans = 0, cuts = 0, forms = 0, slabs = 0, scan_plans = 0, scan_cuts = 0, scan_forms[4] = {0, 0, 0, 0};
 
 static void fail(const char* what, const rua_layout& L, int64_t H, int es) {
   if (++violations <= 20)
@@ -69,6 +71,29 @@ static void walk_plan(const rua_layout& L, int64_t H, int es, int per_col) {
     if (grid < 0 || grid > 0x7fffffffLL) fail("a rows grid beyond what a launch takes", L, H, es);
     if (grid != 0 && (__int128)grid != want) fail("the rows grid is not maxblk * n_chunks * B", L, H, es);
     if (grid == 0 && want > 0 && want <= 0x7fffffffLL) fail("a rows grid refused that fits", L, H, es);
+  }
+  // the form of a rows launch: al from the row and the bases, cut only with the workspace, the grid seg_rows_grid's
+  for (uint64_t bases : {(uint64_t)0x1000, (uint64_t)0x1008}) {
+    for (int ws = 0; ws < 2; ++ws) {
+      const seg_rows r = seg_rows_form(p, L, row_bytes, bases, ws != 0);
+      ++forms;
+      if (r.al != (row_bytes % 16 == 0 && bases % 16 == 0)) fail("al is not 'whole aligned vectors'", L, H, es);
+      if (r.cut != (ws && p.maxblk > 0)) fail("cut without the workspace or the plan", L, H, es);
+      if (r.grid != seg_rows_grid(L, p, r.cut)) fail("the form's grid is not seg_rows_grid", L, H, es);
+      if (r.cut && !r.grid) fail("a cut grid that does not fit", L, H, es);
+      // the resident slab: never when cut, never beyond `most`, whole rounds of slots, and it holds the bound it can
+      for (int slots : {32, 64}) {
+        for (int64_t most : {(int64_t)224, (int64_t)480, (int64_t)1024}) {
+          const int cap = seg_slab_cap(L, r.cut, slots, most);
+          const int64_t expect = L.kind == RUA_CAT && !(L.T_log > 0) ? 2 * (L.n_rows / L.B) : bound;
+          ++slabs;
+          if (cap < 0 || cap > most || (cap % slots && cap != most)) fail("a slab beyond its cap or of broken rounds", L, H, es);
+          if ((r.cut || expect > 1024) && cap) fail("a slab for sequences that stream", L, H, es);
+          if (!r.cut && expect <= 1024 && cap < most && cap < bound) fail("a slab below both the bound and its cap", L, H, es);
+          if (cap >= slots + bound) fail("a slab a round larger than the bound", L, H, es);
+        }
+      }
+    }
   }
   if (row_bytes <= 16) {
     for (uint64_t bases : {(uint64_t)0, (uint64_t)0x1000, (uint64_t)0x1008, (uint64_t)0x1004, (uint64_t)0x1002}) {
@@ -154,8 +179,8 @@ int main() {
             }
   for (int ws_elem_bytes : {4, 8})
     for_each_bound_layout([&](const rua_layout& L) { walk_scan_plan(L, ws_elem_bytes); });
-  printf("plans %lld cuts %lld scan plans %lld cuts %lld lanes %lld rows %lld long %lld violations %lld\n", plans, cuts,
-         scan_plans, scan_cuts, scan_forms[0], scan_forms[1], scan_forms[2], violations);
+  printf("plans %lld cuts %lld forms %lld slabs %lld scan plans %lld cuts %lld lanes %lld rows %lld long %lld violations %lld\n",
+         plans, cuts, forms, slabs, scan_plans, scan_cuts, scan_forms[0], scan_forms[1], scan_forms[2], violations);
   const bool seen = cuts > 0 && scan_cuts > 0 && scan_forms[0] > 0 && scan_forms[1] > 0 && scan_forms[2] > 0;
   return violations ? 1 : (seen ? 0 : 2);
 }

@@ -23,19 +23,15 @@
 #include <stdint.h>
 #include <string.h>
 #include <atomic>
-#include "rua_seg.h"
+#include "rua_seg_launch.h"
 
 namespace rua {
-
-extern std::atomic<int> g_trace_on;        // the dispatch trace (rua_reduce.hip)
-void trace_add(const char* rec);
 
 constexpr int AR_SLOTS = 32;               // tokens a step of a sequence puts side by side
 constexpr int AR_BLOCK_TOK = SEG_BLOCK_TOK; // tokens per block: 32-bit offsets inside, a 64-bit base outside
 constexpr int AR_LPR = 8;                  // rows form: 16-byte lanes per row chunk (128 bytes)
 constexpr int AR_ROWS_UNR = 4;             // rows form: rows in flight per thread
 constexpr int AR_LANES_UNR = 8;            // lanes form: tokens in flight per lane
-enum { AR_FULL = 0, AR_PARTIAL = 1, AR_FINISH = 2 };
 static_assert(AR_SLOTS * AR_LPR == RUA_BLOCK, "a step of the rows form is a workgroup");
 
 // ---------------------------------------------------------------- element types
@@ -161,8 +157,8 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_argreduce_lanes_kernel(rua_layo
 // A workgroup takes (sequence x 128-byte column chunk): thread (q, l) = (tid / 8, tid % 8) takes the tokens t = q
 // (mod 32), four of them in flight, and owns the l-th 16-byte vector of the chunk.  The 32 threads of a vector are
 // combined by shuffles inside a wave (lanes 8, 16, 32 apart) and through LDS across the four waves.
-// mode AR_PARTIAL: the CUT form — a workgroup per (sequence, block of 2 048 tokens, chunk) leaves its block's (value,
-// position) in `ws`; AR_FINISH: a workgroup per (sequence, chunk) combines the pairs of the sequence's blocks.
+// mode SEG_PARTIAL: the CUT form — a workgroup per (sequence, block of 2 048 tokens, chunk) leaves its block's (value,
+// position) in `ws`; SEG_FINISH: a workgroup per (sequence, chunk) combines the pairs of the sequence's blocks.
 // AL = false: rows or bases off 16 bytes — the same geometry with elementwise accesses.
 template <typename E, int OP, bool AL>
 __global__ __launch_bounds__(RUA_BLOCK) void seg_argreduce_rows_kernel(rua_layout L, const typename E::raw* xin,
@@ -182,19 +178,19 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_argreduce_rows_kernel(rua_layou
   const int c = (int)(blockIdx.x % (unsigned)n_chunks);
   int64_t b = blockIdx.x / (unsigned)n_chunks;
   int blk = 0;
-  if (mode == AR_PARTIAL) { blk = (int)(b % maxblk); b /= maxblk; }
+  if (mode == SEG_PARTIAL) { blk = (int)(b % maxblk); b /= maxblk; }
   if (b >= L.B) return;
   const int64_t len = safe_len(L, b);
   // the cut form sized `ws` and the grid from the host's length bound: a CAT layout whose T_log understates a length
   // must not walk past the maxblk blocks that exist (rua.h: T_log has to be a true bound)
   const int64_t have_blk = (len + AR_BLOCK_TOK - 1) / AR_BLOCK_TOK;
-  const int64_t nblk = mode != AR_FULL && have_blk > maxblk ? maxblk : have_blk;
-  if (mode == AR_PARTIAL && blk > 0 && blk >= nblk) return;    // workgroup-uniform
+  const int64_t nblk = mode != SEG_FULL && have_blk > maxblk ? maxblk : have_blk;
+  if (mode == SEG_PARTIAL && blk > 0 && blk >= nblk) return;    // workgroup-uniform
   const int64_t col0 = (int64_t)c * CW + (int64_t)l * VE;
   const int nval = H - col0 >= VE ? VE : (H - col0 > 0 ? (int)(H - col0) : 0);
   const bool active = nval > 0;
   int64_t tb = 0, te = len;
-  if (mode == AR_PARTIAL) {
+  if (mode == SEG_PARTIAL) {
     tb = (int64_t)blk * AR_BLOCK_TOK;
     te = len < tb + AR_BLOCK_TOK ? len : tb + AR_BLOCK_TOK;
     if (tb > te) tb = te;
@@ -209,7 +205,7 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_argreduce_rows_kernel(rua_layou
 #pragma unroll
   for (int e = 0; e < VE; ++e) { V[e] = ar_ident<A, OP>(); I[e] = -1; }
 
-  if (mode == AR_FINISH) {
+  if (mode == SEG_FINISH) {
     if (active) {
       for (int64_t k = q; k < nblk; k += AR_SLOTS) {
         const int64_t at = (((b * maxblk + k) * n_chunks + c) * AR_LPR + l) * VE;
@@ -282,7 +278,7 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_argreduce_rows_kernel(rua_layou
 #pragma unroll
     for (int e = 0; e < VE; ++e) ar_merge<OP>(V[e], I[e], xv[k][l][e], xi[k][l][e]);
   }
-  if (mode == AR_PARTIAL) {
+  if (mode == SEG_PARTIAL) {
     const int64_t at = (((b * maxblk + blk) * n_chunks + c) * AR_LPR + l) * VE;
 #pragma unroll
     for (int e = 0; e < VE; ++e) { wsv[at + e] = V[e]; wsi[at + e] = I[e]; }
@@ -389,68 +385,42 @@ static int ar_launch(const rua_layout& L, const void* x, void* values, int64_t* 
   const int64_t row_bytes = H * (int64_t)sizeof(raw);
   const uint64_t base = (uint64_t)(uintptr_t)x;
   const char* opn = OP == RUA_MAX ? "max" : "min";
-  char rec[200];
   if (base % sizeof(raw) || (uint64_t)(uintptr_t)values % sizeof(raw) || (uint64_t)(uintptr_t)index % 8)
     return RUA_EALIGN;                                         // (elements themselves are always aligned)
 
   if (row_bytes <= 16) {
     const seg_lanes ln = seg_lanes_geometry(row_bytes, base, L.B);
-    const int W = ln.W;
-    const int64_t grid = ln.grid;
-    if (!grid) return RUA_ERANGE;
-    if (g_trace_on.load(std::memory_order_relaxed)) {
-      snprintf(rec, sizeof rec, "seg_argreduce_lanes_kernel T=%s op=%s W=%d H=%d values=%d kind=%d", E::name(), opn, W,
-               (int)H, (int)(values != nullptr), L.kind);
-      trace_add(rec);
-    }
-    hipLaunchKernelGGL((seg_argreduce_lanes_kernel<E, OP>), dim3((unsigned)grid), dim3(RUA_BLOCK), 0, s, L,
-                       (const char*)x, (raw*)values, index, (int)H, W);
+    if (!ln.grid) return RUA_ERANGE;
+    seg_trace("seg_argreduce_lanes_kernel T=%s op=%s W=%d H=%d values=%d kind=%d", E::name(), opn, ln.W, (int)H,
+              (int)(values != nullptr), L.kind);
+    hipLaunchKernelGGL((seg_argreduce_lanes_kernel<E, OP>), dim3((unsigned)ln.grid), dim3(RUA_BLOCK), 0, s, L,
+                       (const char*)x, (raw*)values, index, (int)H, ln.W);
     return (int)hipGetLastError();
   }
 
-  const seg_plan p = ar_make_plan(L, H, dtype);
+  const seg_rows r = seg_rows_form(ar_make_plan(L, H, dtype), L, row_bytes, base, ws != nullptr);
+  const seg_plan& p = r.p;
   if (p.n_chunks <= 0) return RUA_ERANGE;
-  const bool al = row_bytes % 16 == 0 && base % 16 == 0;
-  const bool cut = ws != nullptr && p.maxblk > 0;
-  if (cut && (uint64_t)(uintptr_t)ws % 8) return RUA_EALIGN;
-  const int64_t units = L.B * (int64_t)p.n_chunks;
-  const int64_t grid = seg_rows_grid(L, p, cut);
-  if (!grid) return RUA_ERANGE;
-
-#define RUA_AR_ROWS(ALV, MODE, GRID)                                                                                   \
-  hipLaunchKernelGGL((seg_argreduce_rows_kernel<E, OP, ALV>), dim3((unsigned)(GRID)), dim3(RUA_BLOCK), 0, s, L,        \
-                     (const raw*)x, (raw*)values, index, H, p.n_chunks, MODE, cut ? p.maxblk : 1, (char*)ws)
-  const bool tr = g_trace_on.load(std::memory_order_relaxed) != 0;
-  if (cut) {
-    if (tr) {
-      snprintf(rec, sizeof rec, "seg_argreduce_rows_kernel T=%s op=%s AL=%d values=%d kind=%d cut=1 phase=partial blocks=%d chunks=%d",
-               E::name(), opn, (int)al, (int)(values != nullptr), L.kind, p.maxblk, p.n_chunks);
-      trace_add(rec);
-      snprintf(rec, sizeof rec, "seg_argreduce_rows_kernel T=%s op=%s AL=%d values=%d kind=%d cut=1 phase=finish blocks=%d chunks=%d",
-               E::name(), opn, (int)al, (int)(values != nullptr), L.kind, p.maxblk, p.n_chunks);
-      trace_add(rec);
-    }
-    if (al) RUA_AR_ROWS(true, AR_PARTIAL, grid); else RUA_AR_ROWS(false, AR_PARTIAL, grid);
-    int e = (int)hipGetLastError();
-    if (e) return e;
-    if (al) RUA_AR_ROWS(true, AR_FINISH, units); else RUA_AR_ROWS(false, AR_FINISH, units);
-    return (int)hipGetLastError();
-  }
-  if (tr) {
-    snprintf(rec, sizeof rec, "seg_argreduce_rows_kernel T=%s op=%s AL=%d values=%d kind=%d cut=0 chunks=%d", E::name(), opn,
-             (int)al, (int)(values != nullptr), L.kind, p.n_chunks);
-    trace_add(rec);
-  }
-  if (al) RUA_AR_ROWS(true, AR_FULL, grid); else RUA_AR_ROWS(false, AR_FULL, grid);
-#undef RUA_AR_ROWS
-  return (int)hipGetLastError();
-}
-
-template <typename E>
-static int ar_launch_op(const rua_layout& L, const void* x, void* values, int64_t* index, int64_t H, int32_t dtype,
-                        int32_t op, void* ws, hipStream_t s) {
-  return op == RUA_MAX ? ar_launch<E, RUA_MAX>(L, x, values, index, H, dtype, ws, s)
-                       : ar_launch<E, RUA_MIN>(L, x, values, index, H, dtype, ws, s);
+  if (r.cut && (uint64_t)(uintptr_t)ws % 8) return RUA_EALIGN;
+  if (!r.grid) return RUA_ERANGE;
+  return seg_launch_rows(
+      r,
+      [&](int mode) {                                          // the finish: a workgroup per (sequence, chunk)
+        const int64_t grid = mode == SEG_FINISH ? L.B * (int64_t)p.n_chunks : r.grid;
+        seg_with_al(r.al, [&](auto AL) {
+          hipLaunchKernelGGL((seg_argreduce_rows_kernel<E, OP, decltype(AL)::value>), dim3((unsigned)grid), dim3(RUA_BLOCK),
+                             0, s, L, (const raw*)x, (raw*)values, index, H, p.n_chunks, mode, r.cut ? p.maxblk : 1,
+                             (char*)ws);
+        });
+      },
+      [&](const char* phase) {
+        if (phase)
+          seg_trace("seg_argreduce_rows_kernel T=%s op=%s AL=%d values=%d kind=%d cut=1 phase=%s blocks=%d chunks=%d",
+                    E::name(), opn, (int)r.al, (int)(values != nullptr), L.kind, phase, p.maxblk, p.n_chunks);
+        else
+          seg_trace("seg_argreduce_rows_kernel T=%s op=%s AL=%d values=%d kind=%d cut=0 chunks=%d", E::name(), opn,
+                    (int)r.al, (int)(values != nullptr), L.kind, p.n_chunks);
+      });
 }
 
 static int ar_dispatch(const rua_layout* lay, const void* x, void* values, int64_t* index, int64_t H, int32_t dtype,
@@ -464,14 +434,12 @@ static int ar_dispatch(const rua_layout* lay, const void* x, void* values, int64
   if (seg_too_large(lay, H, es) || (double)lay->B * (double)H >= 1.0e18)
     return RUA_ERANGE;
   hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case RUA_F32:  return ar_launch_op<sm_f32>(*lay, x, values, index, H, dtype, op, ws, s);
-    case RUA_BF16: return ar_launch_op<sm_bf16>(*lay, x, values, index, H, dtype, op, ws, s);
-    case RUA_F16:  return ar_launch_op<sm_f16>(*lay, x, values, index, H, dtype, op, ws, s);
-    case RUA_F64:  return ar_launch_op<sm_f64>(*lay, x, values, index, H, dtype, op, ws, s);
-    case RUA_I64:  return ar_launch_op<ar_i64>(*lay, x, values, index, H, dtype, op, ws, s);
-  }
-  return RUA_EINVAL;
+#define RUA_AR(E)                                                                                                      \
+  (op == RUA_MAX ? ar_launch<E, RUA_MAX>(*lay, x, values, index, H, dtype, ws, s)                                      \
+                 : ar_launch<E, RUA_MIN>(*lay, x, values, index, H, dtype, ws, s))
+  if (dtype == RUA_I64) return RUA_AR(ar_i64);
+  RUA_DISPATCH_FLOAT(dtype, RUA_AR);
+#undef RUA_AR
 }
 
 // take / put move elements as bits: one instantiation per element size
@@ -481,11 +449,7 @@ static int take_launch(const rua_layout& L, const void* data, const int64_t* ind
   const int64_t total = L.B * H;
   const int64_t grid = (total + RUA_BLOCK - 1) / RUA_BLOCK;
   if (grid > 0x7fffffffLL) return RUA_ERANGE;
-  if (g_trace_on.load(std::memory_order_relaxed)) {
-    char rec[160];
-    snprintf(rec, sizeof rec, "seg_take_kernel esize=%d H=%lld kind=%d", (int)sizeof(U), (long long)H, L.kind);
-    trace_add(rec);
-  }
+  seg_trace("seg_take_kernel esize=%d H=%lld kind=%d", (int)sizeof(U), (long long)H, L.kind);
   hipLaunchKernelGGL((seg_take_kernel<U>), dim3((unsigned)grid), dim3(RUA_BLOCK), 0, s, L, (const U*)data, index, (U*)out,
                      H, total);
   return (int)hipGetLastError();
@@ -508,18 +472,12 @@ static int put_launch(const rua_layout& L, const void* src, const int64_t* index
   if (nblk > SEG_CUT_MAX_BLOCKS) return RUA_ERANGE;
   const int64_t grid = units * nblk;
   if (grid > 0x7fffffffLL) return RUA_ERANGE;
-  if (g_trace_on.load(std::memory_order_relaxed)) {
-    char rec[160];
-    snprintf(rec, sizeof rec, "seg_put_kernel esize=%d AL=%d kind=%d lpr=%d chunks=%d blocks=%d", (int)sizeof(U), (int)al,
-             L.kind, 1 << lpr_log2, (int)chunks, (int)nblk);
-    trace_add(rec);
-  }
-  if (al)
-    hipLaunchKernelGGL((seg_put_kernel<U, true>), dim3((unsigned)grid), dim3(RUA_BLOCK), 0, s, L, (const U*)src, index,
-                       (U*)out, H, (int)chunks, lpr_log2, (int)nblk);
-  else
-    hipLaunchKernelGGL((seg_put_kernel<U, false>), dim3((unsigned)grid), dim3(RUA_BLOCK), 0, s, L, (const U*)src, index,
-                       (U*)out, H, (int)chunks, lpr_log2, (int)nblk);
+  seg_trace("seg_put_kernel esize=%d AL=%d kind=%d lpr=%d chunks=%d blocks=%d", (int)sizeof(U), (int)al, L.kind,
+            1 << lpr_log2, (int)chunks, (int)nblk);
+  seg_with_al(al, [&](auto AL) {
+    hipLaunchKernelGGL((seg_put_kernel<U, decltype(AL)::value>), dim3((unsigned)grid), dim3(RUA_BLOCK), 0, s, L,
+                       (const U*)src, index, (U*)out, H, (int)chunks, lpr_log2, (int)nblk);
+  });
   return (int)hipGetLastError();
 }
 

@@ -26,14 +26,11 @@
 #include <atomic>
 #include <initializer_list>
 #include <type_traits>
-#include "rua_seg.h"
+#include "rua_seg_launch.h"
 
 #pragma clang fp contract(off)
 
 namespace rua {
-
-extern std::atomic<int> g_trace_on;        // the dispatch trace (rua_reduce.hip)
-void trace_add(const char* rec);
 
 constexpr int CV_SLOTS = 32;               // rows form: contiguous runs of tokens per workgroup; lanes form: tokens of a tile
 constexpr int CV_LPR = 8;                  // rows form: 16-byte lanes per row chunk (128 bytes)
@@ -475,18 +472,13 @@ static int cv_launch_k(const rua_layout& L, const void* xin, const void* pin, co
   if ((bases | small) % sizeof(raw) || (uint64_t)(uintptr_t)ws % sizeof(A)) return RUA_EALIGN;
   const cv_plan p = cv_make_plan(L, H, es);
   if (p.seg.n_chunks <= 0 || p.units <= 0) return RUA_ERANGE;
-  const bool tr = g_trace_on.load(std::memory_order_relaxed) != 0;
-  char rec[240];
 
   if (p.lanes) {
     const seg_lanes ln = seg_lanes_geometry(row_bytes, bases, L.B);
     if (!ln.grid) return RUA_ERANGE;
     const int64_t grid = WG ? p.parts : p.units;
-    if (tr) {
-      snprintf(rec, sizeof rec, "seg_conv_lanes_kernel T=%s K=%d W=%d H=%d rev=%d kind=%d bwd=%d cut=0 parts=%d",
-               E::name(), K, ln.W, (int)H, rev, L.kind, (int)WG, WG ? p.parts : 0);
-      trace_add(rec);
-    }
+    seg_trace("seg_conv_lanes_kernel T=%s K=%d W=%d H=%d rev=%d kind=%d bwd=%d cut=0 parts=%d", E::name(), K, ln.W,
+              (int)H, rev, L.kind, (int)WG, WG ? p.parts : 0);
     hipLaunchKernelGGL((seg_conv_lanes_kernel<E, K, WG>), dim3((unsigned)grid), dim3(RUA_BLOCK), 0, s, L,
                        (const char*)xin, (const char*)pin, (const raw*)weight, (const raw*)bias, (char*)out, (int)H,
                        ln.W, p.units, (A*)ws, rev);
@@ -500,27 +492,19 @@ static int cv_launch_k(const rua_layout& L, const void* xin, const void* pin, co
     const int64_t grid = parts * p.seg.n_chunks;
     if (grid > 0x7fffffffLL) return RUA_ERANGE;
     const bool al = row_bytes % 16 == 0 && bases % 16 == 0;
-    if (tr) {
-      snprintf(rec, sizeof rec, "seg_conv_rows_kernel T=%s K=%d AL=%d rev=%d kind=%d bwd=%d cut=%d blocks=%d chunks=%d parts=%d",
-               E::name(), K, (int)al, rev, L.kind, (int)WG, (int)cut, cut ? p.seg.maxblk : 0, p.seg.n_chunks,
-               WG ? (int)parts : 0);
-      trace_add(rec);
-    }
-#define RUA_CV_ROWS(ALV)                                                                                               \
-  hipLaunchKernelGGL((seg_conv_rows_kernel<E, K, ALV, WG>), dim3((unsigned)grid), dim3(RUA_BLOCK), 0, s, L,            \
-                     (const raw*)xin, (const raw*)pin, (const raw*)weight, (const raw*)bias, (raw*)out, H,             \
-                     p.seg.n_chunks, cut ? p.seg.maxblk : 0, units, (int)parts, (A*)ws, rev, (int)inplace,    \
-                     (int)(small % 16 == 0))
-    if (al) RUA_CV_ROWS(true); else RUA_CV_ROWS(false);
-#undef RUA_CV_ROWS
+    seg_trace("seg_conv_rows_kernel T=%s K=%d AL=%d rev=%d kind=%d bwd=%d cut=%d blocks=%d chunks=%d parts=%d", E::name(),
+              K, (int)al, rev, L.kind, (int)WG, (int)cut, cut ? p.seg.maxblk : 0, p.seg.n_chunks, WG ? (int)parts : 0);
+    seg_with_al(al, [&](auto AL) {
+      hipLaunchKernelGGL((seg_conv_rows_kernel<E, K, decltype(AL)::value, WG>), dim3((unsigned)grid), dim3(RUA_BLOCK), 0,
+                         s, L, (const raw*)xin, (const raw*)pin, (const raw*)weight, (const raw*)bias, (raw*)out, H,
+                         p.seg.n_chunks, cut ? p.seg.maxblk : 0, units, (int)parts, (A*)ws, rev, (int)inplace,
+                         (int)(small % 16 == 0));
+    });
   }
   int e = (int)hipGetLastError();
   if (e || !WG) return e;
   const int64_t n_out = (int64_t)(K + 1) * H;
-  if (tr) {
-    snprintf(rec, sizeof rec, "seg_conv_finish_kernel T=%s K=%d parts=%d chunks=%d", E::name(), K, p.parts, p.seg.n_chunks);
-    trace_add(rec);
-  }
+  seg_trace("seg_conv_finish_kernel T=%s K=%d parts=%d chunks=%d", E::name(), K, p.parts, p.seg.n_chunks);
   hipLaunchKernelGGL((seg_conv_finish_kernel<E>), dim3((unsigned)((n_out + RUA_BLOCK - 1) / RUA_BLOCK)), dim3(RUA_BLOCK),
                      0, s, (const A*)ws, (raw*)gw, (raw*)gb, H, K, p.seg.n_chunks, p.parts);
   return (int)hipGetLastError();
@@ -541,14 +525,9 @@ template <bool WG>
 static int cv_dispatch(const rua_layout* lay, const void* xin, const void* pin, const void* weight, const void* bias,
                        void* out, void* gw, void* gb, int64_t H, int32_t K, int32_t dtype, int rev, void* ws,
                        void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case RUA_F32:  return cv_launch<sm_f32, WG>(*lay, xin, pin, weight, bias, out, gw, gb, H, K, rev, ws, s);
-    case RUA_BF16: return cv_launch<sm_bf16, WG>(*lay, xin, pin, weight, bias, out, gw, gb, H, K, rev, ws, s);
-    case RUA_F16:  return cv_launch<sm_f16, WG>(*lay, xin, pin, weight, bias, out, gw, gb, H, K, rev, ws, s);
-    case RUA_F64:  return cv_launch<sm_f64, WG>(*lay, xin, pin, weight, bias, out, gw, gb, H, K, rev, ws, s);
-  }
-  return RUA_EINVAL;
+#define RUA_CV(E) cv_launch<E, WG>(*lay, xin, pin, weight, bias, out, gw, gb, H, K, rev, ws, (hipStream_t)stream)
+  RUA_DISPATCH_FLOAT(dtype, RUA_CV);
+#undef RUA_CV
 }
 
 // the layout, then H, the dtype and K

@@ -32,14 +32,11 @@
 #include <string.h>
 #include <atomic>
 #include <initializer_list>
-#include "rua_seg.h"
+#include "rua_seg_launch.h"
 
 #pragma clang fp contract(off)
 
 namespace rua {
-
-extern std::atomic<int> g_trace_on;        // the dispatch trace (rua_reduce.hip)
-void trace_add(const char* rec);
 
 // the geometry of rua_scan.hip, repeated (that file's bits are pinned by its own tests and it stays untouched): a gate
 // of 1 reproduces the cumsum bit for bit only while these agree with SC_* there
@@ -50,7 +47,6 @@ constexpr int LS_TILES = LS_BLOCK_TOK / LS_SLOTS;
 constexpr int LS_LPR = 8;                  // rows form: 16-byte lanes per row chunk (128 bytes)
 constexpr int LS_ROWS_UNR = 2;             // rows form: tiles in flight per workgroup (two accumulators per element)
 constexpr int LS_LANES_UNR = 2;            // lanes form: tiles in flight per half wave
-enum { LS_FULL = 0, LS_PARTIAL = 1, LS_FINISH = 2 };
 static_assert(LS_GROUP == 8 && LS_SLOTS == 32 && LS_BLOCK_TOK == 2048 && LS_TILES == 64,
               "the association order of rua_scan.hip: groups of 8, tiles of 32, blocks of 2 048");
 static_assert(LS_SLOTS == 4 * LS_GROUP && LS_SLOTS * LS_LPR == RUA_BLOCK && LS_GROUP * LS_LPR == RUA_WAVE,
@@ -216,7 +212,7 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_linear_scan_lanes_kernel(rua_la
 // ---------------------------------------------------------------- rows wider than one vector
 // The geometry of seg_cumsum_rows_kernel: a workgroup per (sequence x 128-byte column chunk), thread (q, l) is position
 // q of a tile and owns the l-th 16-byte vector of the chunk; the four group totals of a tile (pairs) cross the waves
-// through LDS, two buffers in turn.  mode LS_PARTIAL / LS_FINISH: the cut form, a pair per block and column in `ws`.
+// through LDS, two buffers in turn.  mode SEG_PARTIAL / SEG_FINISH: the cut form, a pair per block and column in `ws`.
 template <typename E, bool AL, bool BWD>
 __global__ __launch_bounds__(RUA_BLOCK) void seg_linear_scan_rows_kernel(rua_layout L, const typename E::raw* xin,
                                                                          const typename E::raw* gate, double gate_scalar,
@@ -238,20 +234,20 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_linear_scan_rows_kernel(rua_lay
   const int c = (int)(blockIdx.x % (unsigned)n_chunks);
   int64_t b = blockIdx.x / (unsigned)n_chunks;
   int blk = 0;
-  if (mode != LS_FULL) { blk = (int)(b % maxblk); b /= maxblk; }
+  if (mode != SEG_FULL) { blk = (int)(b % maxblk); b /= maxblk; }
   if (b >= L.B) return;
   const int64_t len = safe_len(L, b);
   // the cut form sized `ws` and the grid from the host's length bound: never walk past the maxblk blocks that exist
   const int64_t have_blk = (len + LS_BLOCK_TOK - 1) / LS_BLOCK_TOK;
-  const int64_t nblk = mode != LS_FULL && have_blk > maxblk ? maxblk : have_blk;
-  if (mode != LS_FULL && blk > 0 && blk >= nblk) return;     // workgroup-uniform
+  const int64_t nblk = mode != SEG_FULL && have_blk > maxblk ? maxblk : have_blk;
+  if (mode != SEG_FULL && blk > 0 && blk >= nblk) return;     // workgroup-uniform
   const int64_t col0 = (int64_t)c * CW + (int64_t)l * VE;
   const int nval = H - col0 >= VE ? VE : (H - col0 > 0 ? (int)(H - col0) : 0);
   const bool active = nval > 0;
-  const bool want_h = BWD && gout != nullptr && mode != LS_PARTIAL;
+  const bool want_h = BWD && gout != nullptr && mode != SEG_PARTIAL;
   const A gs = (A)gate_scalar;
   int64_t ub = 0, ue = len;                                  // positions along the scan
-  if (mode != LS_FULL) {
+  if (mode != SEG_FULL) {
     ub = (int64_t)blk * LS_BLOCK_TOK;
     ue = len < ub + LS_BLOCK_TOK ? len : ub + LS_BLOCK_TOK;
     if (ub > ue) ub = ue;
@@ -279,7 +275,7 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_linear_scan_rows_kernel(rua_lay
   PR base[VE], car[VE];
 #pragma unroll
   for (int e = 0; e < VE; ++e) base[e] = car[e] = ls_ident<A>();
-  if (mode == LS_FINISH) {
+  if (mode == SEG_FINISH) {
     for (int64_t k = 0; k < blk; ++k) {
       const PR* p = ws + ((((b * maxblk + k) * n_chunks + c) * LS_LPR + l) * VE);
 #pragma unroll
@@ -362,17 +358,17 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_linear_scan_rows_kernel(rua_lay
         o.e[e] = E::down(r);
         og.e[e] = (BWD && hash[k]) ? E::down(ls_pin(r * E::up(hh[k].e[e]))) : (raw)0;
       }
-      if (mode != LS_PARTIAL && rows[k] >= 0) {
+      if (mode != SEG_PARTIAL && rows[k] >= 0) {
         st(out, rows[k], o);
         if (want_h) st(gout, rows[k], og);
       }
-      if (mode == LS_FULL && (tile0 / LS_SLOTS + 1) % LS_TILES == 0) {      // the block ends: its total joins the base
+      if (mode == SEG_FULL && (tile0 / LS_SLOTS + 1) % LS_TILES == 0) {      // the block ends: its total joins the base
 #pragma unroll
         for (int e = 0; e < VE; ++e) { base[e] = ls_comb(base[e], car[e]); car[e] = ls_ident<A>(); }
       }
     }
   }
-  if (mode == LS_PARTIAL) {
+  if (mode == SEG_PARTIAL) {
     if (tid < LS_LPR) {
       PR* p = ws + ((((b * maxblk + blk) * n_chunks + c) * LS_LPR + l) * VE);
 #pragma unroll
@@ -410,60 +406,40 @@ static int ls_launch(const rua_layout& L, const void* x, const void* gate, doubl
   const int64_t row_bytes = H * (int64_t)sizeof(raw);
   const uint64_t bases = (uint64_t)(uintptr_t)x | (uint64_t)(uintptr_t)out | (uint64_t)(uintptr_t)gate |
                          (uint64_t)(uintptr_t)(gout ? h : nullptr) | (uint64_t)(uintptr_t)gout;
-  char rec[240];
   if (bases % sizeof(raw)) return RUA_EALIGN;                 // (elements themselves are always aligned)
   const char* gname = gate ? "tensor" : "scalar";
-  const bool tr = g_trace_on.load(std::memory_order_relaxed) != 0;
 
   if (row_bytes <= 16) {
     const seg_lanes ln = seg_lanes_geometry(row_bytes, bases, L.B);
-    const int W = ln.W;
-    const int64_t grid = ln.grid;
-    if (!grid) return RUA_ERANGE;
-    if (tr) {
-      const uint64_t own = (uint64_t)row_bytes | 16u;           // AL: the bases did not narrow the row's own access width
-      snprintf(rec, sizeof rec, "seg_linear_scan_lanes_kernel T=%s W=%d H=%d AL=%d rev=%d kind=%d gate=%s bwd=%d cut=0",
-               E::name(), W, (int)H, (int)(W == (int)(own & (~own + 1))), rev, L.kind, gname, (int)BWD);
-      trace_add(rec);
-    }
-    hipLaunchKernelGGL((seg_linear_scan_lanes_kernel<E, BWD>), dim3((unsigned)grid), dim3(RUA_BLOCK), 0, s, L,
-                       (const char*)x, (const char*)gate, gs, (const char*)h, (char*)out, (char*)gout, (int)H, W, rev);
+    if (!ln.grid) return RUA_ERANGE;
+    const uint64_t own = (uint64_t)row_bytes | 16u;             // AL: the bases did not narrow the row's own access width
+    seg_trace("seg_linear_scan_lanes_kernel T=%s W=%d H=%d AL=%d rev=%d kind=%d gate=%s bwd=%d cut=0", E::name(), ln.W,
+              (int)H, (int)(ln.W == (int)(own & (~own + 1))), rev, L.kind, gname, (int)BWD);
+    hipLaunchKernelGGL((seg_linear_scan_lanes_kernel<E, BWD>), dim3((unsigned)ln.grid), dim3(RUA_BLOCK), 0, s, L,
+                       (const char*)x, (const char*)gate, gs, (const char*)h, (char*)out, (char*)gout, (int)H, ln.W, rev);
     return (int)hipGetLastError();
   }
 
-  const seg_plan p = ls_make_plan(L, H, dtype);
-  const bool al = row_bytes % 16 == 0 && bases % 16 == 0;
-  const bool cut = ws != nullptr && p.maxblk > 0;
-  const int64_t grid = seg_rows_grid(L, p, cut);
-  if (!grid) return RUA_ERANGE;
-
-#define RUA_LS_ROWS(ALV, MODE)                                                                                         \
-  hipLaunchKernelGGL((seg_linear_scan_rows_kernel<E, ALV, BWD>), dim3((unsigned)grid), dim3(RUA_BLOCK), 0, s, L,       \
-                     (const raw*)x, (const raw*)gate, gs, (const raw*)h, (raw*)out, (raw*)gout, H, p.n_chunks, MODE,   \
-                     cut ? p.maxblk : 1, (PR*)ws, rev)
-  if (cut) {
-    if (tr) {
-      for (const char* phase : {"partial", "finish"}) {
-        snprintf(rec, sizeof rec,
-                 "seg_linear_scan_rows_kernel T=%s AL=%d rev=%d kind=%d gate=%s bwd=%d cut=1 phase=%s blocks=%d chunks=%d",
-                 E::name(), (int)al, rev, L.kind, gname, (int)BWD, phase, p.maxblk, p.n_chunks);
-        trace_add(rec);
-      }
-    }
-    if (al) RUA_LS_ROWS(true, LS_PARTIAL); else RUA_LS_ROWS(false, LS_PARTIAL);
-    int e = (int)hipGetLastError();
-    if (e) return e;
-    if (al) RUA_LS_ROWS(true, LS_FINISH); else RUA_LS_ROWS(false, LS_FINISH);
-    return (int)hipGetLastError();
-  }
-  if (tr) {
-    snprintf(rec, sizeof rec, "seg_linear_scan_rows_kernel T=%s AL=%d rev=%d kind=%d gate=%s bwd=%d cut=0 chunks=%d",
-             E::name(), (int)al, rev, L.kind, gname, (int)BWD, p.n_chunks);
-    trace_add(rec);
-  }
-  if (al) RUA_LS_ROWS(true, LS_FULL); else RUA_LS_ROWS(false, LS_FULL);
-#undef RUA_LS_ROWS
-  return (int)hipGetLastError();
+  const seg_rows r = seg_rows_form(ls_make_plan(L, H, dtype), L, row_bytes, bases, ws != nullptr);
+  const seg_plan& p = r.p;
+  if (!r.grid) return RUA_ERANGE;
+  return seg_launch_rows(
+      r,
+      [&](int mode) {
+        seg_with_al(r.al, [&](auto AL) {
+          hipLaunchKernelGGL((seg_linear_scan_rows_kernel<E, decltype(AL)::value, BWD>), dim3((unsigned)r.grid),
+                             dim3(RUA_BLOCK), 0, s, L, (const raw*)x, (const raw*)gate, gs, (const raw*)h, (raw*)out,
+                             (raw*)gout, H, p.n_chunks, mode, r.cut ? p.maxblk : 1, (PR*)ws, rev);
+        });
+      },
+      [&](const char* phase) {
+        if (phase)
+          seg_trace("seg_linear_scan_rows_kernel T=%s AL=%d rev=%d kind=%d gate=%s bwd=%d cut=1 phase=%s blocks=%d chunks=%d",
+                    E::name(), (int)r.al, rev, L.kind, gname, (int)BWD, phase, p.maxblk, p.n_chunks);
+        else
+          seg_trace("seg_linear_scan_rows_kernel T=%s AL=%d rev=%d kind=%d gate=%s bwd=%d cut=0 chunks=%d", E::name(),
+                    (int)r.al, rev, L.kind, gname, (int)BWD, p.n_chunks);
+      });
 }
 
 template <bool BWD>
@@ -477,16 +453,11 @@ static int ls_dispatch(const rua_layout* lay, const void* x, const void* gate, d
   if (out == gate || (BWD && h && out == h)) return RUA_EINVAL;
   if (BWD && gout && (!h || !gate || gout == x || gout == gate || gout == h || gout == out)) return RUA_EINVAL;
   if (seg_too_large(lay, H, es)) return RUA_ERANGE;
-  hipStream_t s = (hipStream_t)stream;
   // the backward runs the scan the other way
   const int rev = (reverse ? 1 : 0) ^ (BWD ? 1 : 0);
-  switch (dtype) {
-    case RUA_F32:  return ls_launch<sm_f32, BWD>(*lay, x, gate, gs, h, out, gout, H, dtype, rev, ws, s);
-    case RUA_BF16: return ls_launch<sm_bf16, BWD>(*lay, x, gate, gs, h, out, gout, H, dtype, rev, ws, s);
-    case RUA_F16:  return ls_launch<sm_f16, BWD>(*lay, x, gate, gs, h, out, gout, H, dtype, rev, ws, s);
-    case RUA_F64:  return ls_launch<sm_f64, BWD>(*lay, x, gate, gs, h, out, gout, H, dtype, rev, ws, s);
-  }
-  return RUA_EINVAL;
+#define RUA_LS(E) ls_launch<E, BWD>(*lay, x, gate, gs, h, out, gout, H, dtype, rev, ws, (hipStream_t)stream)
+  RUA_DISPATCH_FLOAT(dtype, RUA_LS);
+#undef RUA_LS
 }
 
 }  // namespace rua

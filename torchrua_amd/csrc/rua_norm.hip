@@ -23,14 +23,11 @@
 #include <stdint.h>
 #include <string.h>
 #include <atomic>
-#include "rua_seg.h"
+#include "rua_seg_launch.h"
 
 #pragma clang fp contract(off)
 
 namespace rua {
-
-extern std::atomic<int> g_trace_on;        // the dispatch trace (rua_reduce.hip)
-void trace_add(const char* rec);
 
 constexpr int NM_SLOTS = 32;               // parallel fold chains per (sequence, column)
 constexpr int NM_BLOCK_TOK = SEG_BLOCK_TOK; // tokens per block = 64 per slot
@@ -38,7 +35,6 @@ constexpr int NM_LPR = 8;                  // row forms: 16-byte lanes per row c
 constexpr int NM_ROWS_UNR = 4;             // row forms: rows in flight per thread
 constexpr int NM_LANES_UNR = 8;            // lanes form: tokens a lane keeps in registers (sequences up to 256 tokens)
 constexpr int NM_LDS_BUDGET = 64 * 1024;   // per workgroup: two workgroups per CU, no opt-in for large dynamic LDS
-enum { NM_FULL = 0, NM_PARTIAL = 1, NM_FINISH = 2 };
 enum { NM_STD = 0, NM_VM = 1, NM_BWD = 2 };  // standardize forward, var_mean (its first walk alone), standardize backward
 
 __device__ __forceinline__ float nm_sqrt(float v) { return sqrtf(v); }
@@ -272,7 +268,7 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_norm_lanes_kernel(rua_layout L,
 // A workgroup takes (sequence x 128-byte column chunk): thread (q, l) = (tid / 8, tid % 8) is slot q and owns the l-th
 // 16-byte vector of the chunk.  RESIDENT (len <= cap_rows): walk 1 parks every vector in LDS in the payload dtype — each
 // thread reads back exactly what it stored, so the slab needs no barrier — and walk 2 rewrites out of LDS: the payload
-// crosses HBM once.  Otherwise STREAMING: walk 2 reads global memory again.  mode NM_PARTIAL / NM_FINISH: the CUT form —
+// crosses HBM once.  Otherwise STREAMING: walk 2 reads global memory again.  mode SEG_PARTIAL / SEG_FINISH: the CUT form —
 // a workgroup per (sequence, block of 2 048 tokens, chunk) leaves its block's (mean, M2) (backward: the two sums) in
 // `ws`; a second launch joins them in block order — the block's n follows from the length — and rewrites the rows.
 // NM_VM has no walk 2: its finish is a grid of (sequence x chunk) workgroups that write [B, H].
@@ -303,24 +299,24 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_norm_rows_kernel(rua_layout L, 
   const int c = (int)(blockIdx.x % (unsigned)n_chunks);
   int64_t b = blockIdx.x / (unsigned)n_chunks;
   int blk = 0;
-  if (mode != NM_FULL) { blk = (int)(b % gridblk); b /= gridblk; }   // (gridblk: maxblk, or 1 for var_mean's finish)
+  if (mode != SEG_FULL) { blk = (int)(b % gridblk); b /= gridblk; }   // (gridblk: maxblk, or 1 for var_mean's finish)
   if (b >= L.B) return;
   const int64_t len = safe_len(L, b);
   // the cut form sized `ws` and the grid from the host's length bound: a CAT layout whose T_log understates a length
   // must not walk past the maxblk blocks that exist (rua.h: T_log has to be a true bound)
   const int64_t have_blk = (len + NM_BLOCK_TOK - 1) / NM_BLOCK_TOK;
-  const int64_t nblk = mode != NM_FULL && have_blk > maxblk ? maxblk : have_blk;
-  if (mode != NM_FULL && blk > 0 && blk >= nblk) return;   // workgroup-uniform
+  const int64_t nblk = mode != SEG_FULL && have_blk > maxblk ? maxblk : have_blk;
+  if (mode != SEG_FULL && blk > 0 && blk >= nblk) return;   // workgroup-uniform
   const int64_t col0 = (int64_t)c * CW + (int64_t)l * VE;
   const int nval = H - col0 >= VE ? VE : (H - col0 > 0 ? (int)(H - col0) : 0);
   const bool active = nval > 0;
   int64_t tb = 0, te = len;
-  if (mode != NM_FULL) {
+  if (mode != SEG_FULL) {
     tb = (int64_t)blk * NM_BLOCK_TOK;
     te = len < tb + NM_BLOCK_TOK ? len : tb + NM_BLOCK_TOK;
     if (tb > te) tb = te;
   }
-  const bool resident = mode == NM_FULL && OP != NM_VM && len <= cap_rows;
+  const bool resident = mode == SEG_FULL && OP != NM_VM && len <= cap_rows;
 
   auto ld = [&](const raw* base, int64_t row, Vec& v) {
     const raw* p = base + row * H + col0;
@@ -345,7 +341,7 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_norm_rows_kernel(rua_layout L, 
 #pragma unroll
   for (int e = 0; e < VE; ++e) { P[e] = (A)0; S[e] = (A)0; }
 
-  if (mode == NM_FINISH) {
+  if (mode == SEG_FINISH) {
     for (int64_t k = 0; k < nblk; ++k) {
       const A* pw = ws + ((((b * maxblk + k) * n_chunks + c) * NM_LPR + l) * VE) * 2;
       A p[VE], s[VE];
@@ -452,7 +448,7 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_norm_rows_kernel(rua_layout L, 
           for (int e = 0; e < VE; ++e) { p[e] = vp[0][e]; s[e] = vs[0][e]; }
         }
       }
-      if (mode == NM_PARTIAL) {
+      if (mode == SEG_PARTIAL) {
         if (tid < NM_LPR) {
           A* pw = ws + ((((b * maxblk + blk) * n_chunks + c) * NM_LPR + l) * VE) * 2;
 #pragma unroll
@@ -467,7 +463,7 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_norm_rows_kernel(rua_layout L, 
         }
       }
     }
-    if (mode == NM_PARTIAL) return;
+    if (mode == SEG_PARTIAL) return;
   }
   if (!active) return;
 
@@ -605,7 +601,6 @@ static int nm_launch(const rua_layout& L, const void* x, const void* g, void* ou
   const uint64_t bases = (uint64_t)(uintptr_t)x | (uint64_t)(uintptr_t)g | (uint64_t)(uintptr_t)out;
   const char* dir = BWD ? "_backward" : "";
   const A corr = (A)correction, eps = (A)eps_d;
-  char rec[200];
   if (bases % sizeof(raw)) return RUA_EALIGN;                 // (elements themselves are always aligned)
   if ((uint64_t)(uintptr_t)o1 % (OP == NM_VM ? sizeof(raw) : sizeof(A)) ||
       (uint64_t)(uintptr_t)o2 % (mean_acc ? sizeof(A) : sizeof(raw)))
@@ -613,68 +608,43 @@ static int nm_launch(const rua_layout& L, const void* x, const void* g, void* ou
 
   if (row_bytes <= 16) {
     const seg_lanes ln = seg_lanes_geometry(row_bytes, bases, L.B);
-    const int W = ln.W;
-    const int64_t grid = ln.grid;
-    if (!grid) return RUA_ERANGE;
-    if (g_trace_on.load(std::memory_order_relaxed)) {
-      snprintf(rec, sizeof rec, "seg_norm%s_lanes_kernel T=%s AL=%d W=%d H=%d kind=%d cut=0 op=%s", dir, E::name(),
-               (int)(W == 16), W, (int)H, L.kind, nm_opname(OP));
-      trace_add(rec);
-    }
-    hipLaunchKernelGGL((seg_norm_lanes_kernel<E, OP>), dim3((unsigned)grid), dim3(RUA_BLOCK), 0, s, L, (const char*)x,
-                       (const char*)g, (char*)out, o1, o2, (int)H, W, corr, eps, mean_acc);
+    if (!ln.grid) return RUA_ERANGE;
+    seg_trace("seg_norm%s_lanes_kernel T=%s AL=%d W=%d H=%d kind=%d cut=0 op=%s", dir, E::name(), (int)(ln.W == 16), ln.W,
+              (int)H, L.kind, nm_opname(OP));
+    hipLaunchKernelGGL((seg_norm_lanes_kernel<E, OP>), dim3((unsigned)ln.grid), dim3(RUA_BLOCK), 0, s, L, (const char*)x,
+                       (const char*)g, (char*)out, o1, o2, (int)H, ln.W, corr, eps, mean_acc);
     return (int)hipGetLastError();
   }
 
-  const seg_plan p = nm_make_plan(L, H, dtype);
-  const bool al = row_bytes % 16 == 0 && bases % 16 == 0;
-  const bool cut = ws != nullptr && p.maxblk > 0;
+  const seg_rows r = seg_rows_form(nm_make_plan(L, H, dtype), L, row_bytes, bases, ws != nullptr);
+  const seg_plan& p = r.p;
   constexpr int XCH_BYTES = (RUA_WAVES_PER_BLOCK * NM_LPR * (2 * VE + 1) * (int)sizeof(A) + 15) / 16 * 16;
   // the slab's cap from the LDS budget: what 64 KiB leave after the exchange area, in rows of 128 bytes (two slabs in
   // the backward), rounded down to whole rounds of the 32 slots — 480 rows forward, 224 backward
   constexpr int CAP = (NM_LDS_BUDGET - XCH_BYTES) / (128 * (BWD ? 2 : 1)) / NM_SLOTS * NM_SLOTS;
-  // resident when the sequences can be expected to fit a slab: the host's bound, or twice the average where a
-  // CattedSequence came without one.  A longer sequence streams inside the same launch (the result is the same bits).
-  const int64_t bound = sm_len_bound(L);
-  const int64_t expect = (L.kind == RUA_CAT && !(L.T_log > 0)) ? 2 * (L.n_rows / L.B) : bound;
-  int cap = 0;
-  if (!cut && OP != NM_VM && expect <= 1024) {
-    const int64_t need = (bound + NM_SLOTS - 1) / NM_SLOTS * NM_SLOTS;
-    cap = (int)(need < CAP ? need : CAP);
-  }
+  const int cap = OP != NM_VM ? seg_slab_cap(L, r.cut, NM_SLOTS, CAP) : 0;     // (var_mean has no second walk)
   const size_t lds = XCH_BYTES + (size_t)cap * 128 * (BWD ? 2 : 1);
-  const int64_t grid = seg_rows_grid(L, p, cut);
-  if (!grid) return RUA_ERANGE;
-
-#define RUA_NM_ROWS(ALV, MODE, GRIDBLK)                                                                                \
-  hipLaunchKernelGGL((seg_norm_rows_kernel<E, OP, ALV>), dim3((unsigned)(L.B * (int64_t)p.n_chunks * (GRIDBLK))),      \
-                     dim3(RUA_BLOCK), lds, s, L, (const raw*)x, (const raw*)g, (raw*)out, o1, o2, H, p.n_chunks, cap,   \
-                     MODE, cut ? p.maxblk : 1, GRIDBLK, (A*)ws, corr, eps, mean_acc)
-  const bool tr = g_trace_on.load(std::memory_order_relaxed) != 0;
-  if (cut) {
-    if (tr) {
-      snprintf(rec, sizeof rec, "seg_norm%s_stream_kernel T=%s AL=%d kind=%d cut=1 phase=partial cap=0 op=%s blocks=%d chunks=%d",
-               dir, E::name(), (int)al, L.kind, nm_opname(OP), p.maxblk, p.n_chunks);
-      trace_add(rec);
-      snprintf(rec, sizeof rec, "seg_norm%s_stream_kernel T=%s AL=%d kind=%d cut=1 phase=finish cap=0 op=%s blocks=%d chunks=%d",
-               dir, E::name(), (int)al, L.kind, nm_opname(OP), p.maxblk, p.n_chunks);
-      trace_add(rec);
-    }
-    if (al) RUA_NM_ROWS(true, NM_PARTIAL, p.maxblk); else RUA_NM_ROWS(false, NM_PARTIAL, p.maxblk);
-    int e = (int)hipGetLastError();
-    if (e) return e;
-    const int finblk = OP == NM_VM ? 1 : p.maxblk;           // var_mean's finish rewrites no rows: one workgroup per unit
-    if (al) RUA_NM_ROWS(true, NM_FINISH, finblk); else RUA_NM_ROWS(false, NM_FINISH, finblk);
-    return (int)hipGetLastError();
-  }
-  if (tr) {
-    snprintf(rec, sizeof rec, "seg_norm%s_%s_kernel T=%s AL=%d kind=%d cut=0 phase=full cap=%d op=%s chunks=%d", dir,
-             cap > 0 ? "resident" : "stream", E::name(), (int)al, L.kind, cap, nm_opname(OP), p.n_chunks);
-    trace_add(rec);
-  }
-  if (al) RUA_NM_ROWS(true, NM_FULL, 1); else RUA_NM_ROWS(false, NM_FULL, 1);
-#undef RUA_NM_ROWS
-  return (int)hipGetLastError();
+  if (!r.grid) return RUA_ERANGE;
+  return seg_launch_rows(
+      r,
+      [&](int mode) {
+        // blocks per unit in this launch's grid; var_mean's finish rewrites no rows: one workgroup per unit
+        const int gridblk = mode == SEG_FULL || (mode == SEG_FINISH && OP == NM_VM) ? 1 : p.maxblk;
+        seg_with_al(r.al, [&](auto AL) {
+          hipLaunchKernelGGL((seg_norm_rows_kernel<E, OP, decltype(AL)::value>),
+                             dim3((unsigned)(L.B * (int64_t)p.n_chunks * gridblk)), dim3(RUA_BLOCK), lds, s, L,
+                             (const raw*)x, (const raw*)g, (raw*)out, o1, o2, H, p.n_chunks, cap, mode,
+                             r.cut ? p.maxblk : 1, gridblk, (A*)ws, corr, eps, mean_acc);
+        });
+      },
+      [&](const char* phase) {
+        if (phase)
+          seg_trace("seg_norm%s_stream_kernel T=%s AL=%d kind=%d cut=1 phase=%s cap=0 op=%s blocks=%d chunks=%d", dir,
+                    E::name(), (int)r.al, L.kind, phase, nm_opname(OP), p.maxblk, p.n_chunks);
+        else
+          seg_trace("seg_norm%s_%s_kernel T=%s AL=%d kind=%d cut=0 phase=full cap=%d op=%s chunks=%d", dir,
+                    cap > 0 ? "resident" : "stream", E::name(), (int)r.al, L.kind, cap, nm_opname(OP), p.n_chunks);
+      });
 }
 
 template <typename E>
@@ -691,12 +661,7 @@ static int nm_launch_vm_backward(const rua_layout& L, const void* x, const void*
   if (parts < 1) parts = 1;
   const int64_t grid = L.B * (int64_t)parts;
   if (grid > 0x7fffffffLL) return RUA_ERANGE;
-  if (g_trace_on.load(std::memory_order_relaxed)) {
-    char rec[200];
-    snprintf(rec, sizeof rec, "seg_var_mean_backward_kernel T=%s AL=0 kind=%d cut=0 op=var_mean parts=%d", E::name(),
-             L.kind, parts);
-    trace_add(rec);
-  }
+  seg_trace("seg_var_mean_backward_kernel T=%s AL=0 kind=%d cut=0 op=var_mean parts=%d", E::name(), L.kind, parts);
   hipLaunchKernelGGL((seg_var_mean_backward_kernel<E>), dim3((unsigned)grid), dim3(RUA_BLOCK), 0, s, L, (const raw*)x,
                      mean, mean_acc, (const raw*)gvar, (const raw*)gmean, (raw*)out, H, parts, (A)correction);
   return (int)hipGetLastError();
@@ -717,14 +682,9 @@ static int nm_dispatch(const rua_layout* lay, const void* x, const void* g, void
   if (lay->B == 0 || lay->n_rows == 0 || H == 0) return 0;
   if (!x || (OP != NM_VM && !out) || (OP == NM_BWD && (!g || !o1))) return RUA_EINVAL;
   if (seg_too_large(lay, H, seg_esize(dtype, false))) return RUA_ERANGE;
-  hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case RUA_F32:  return nm_launch<sm_f32, OP>(*lay, x, g, out, o1, o2, H, dtype, correction, eps, mean_acc, ws, s);
-    case RUA_BF16: return nm_launch<sm_bf16, OP>(*lay, x, g, out, o1, o2, H, dtype, correction, eps, mean_acc, ws, s);
-    case RUA_F16:  return nm_launch<sm_f16, OP>(*lay, x, g, out, o1, o2, H, dtype, correction, eps, mean_acc, ws, s);
-    case RUA_F64:  return nm_launch<sm_f64, OP>(*lay, x, g, out, o1, o2, H, dtype, correction, eps, mean_acc, ws, s);
-  }
-  return RUA_EINVAL;
+#define RUA_NM(E) nm_launch<E, OP>(*lay, x, g, out, o1, o2, H, dtype, correction, eps, mean_acc, ws, (hipStream_t)stream)
+  RUA_DISPATCH_FLOAT(dtype, RUA_NM);
+#undef RUA_NM
 }
 
 }  // namespace rua
@@ -755,14 +715,10 @@ extern "C" int rua_segment_var_mean_backward(const rua_layout* lay, const void* 
   if (lay->B == 0 || lay->n_rows == 0 || H == 0) return 0;
   if (!data || !mean || !grad_in) return RUA_EINVAL;
   if (seg_too_large(lay, H, seg_esize(dtype, false))) return RUA_ERANGE;
-  hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case RUA_F32:  return nm_launch_vm_backward<sm_f32>(*lay, data, mean, macc, grad_var, grad_mean, grad_in, H, correction, s);
-    case RUA_BF16: return nm_launch_vm_backward<sm_bf16>(*lay, data, mean, macc, grad_var, grad_mean, grad_in, H, correction, s);
-    case RUA_F16:  return nm_launch_vm_backward<sm_f16>(*lay, data, mean, macc, grad_var, grad_mean, grad_in, H, correction, s);
-    case RUA_F64:  return nm_launch_vm_backward<sm_f64>(*lay, data, mean, macc, grad_var, grad_mean, grad_in, H, correction, s);
-  }
-  return RUA_EINVAL;
+#define RUA_NM_VMB(E)                                                                                                  \
+  nm_launch_vm_backward<E>(*lay, data, mean, macc, grad_var, grad_mean, grad_in, H, correction, (hipStream_t)stream)
+  RUA_DISPATCH_FLOAT(dtype, RUA_NM_VMB);
+#undef RUA_NM_VMB
 }
 
 extern "C" int rua_segment_standardize(const rua_layout* lay, const void* data, void* out, void* rstd, int64_t H,

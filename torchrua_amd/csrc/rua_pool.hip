@@ -27,14 +27,11 @@
 #include <stdint.h>
 #include <string.h>
 #include <atomic>
-#include "rua_seg.h"
+#include "rua_seg_launch.h"
 
 #pragma clang fp contract(off)
 
 namespace rua {
-
-extern std::atomic<int> g_trace_on;        // the dispatch trace (rua_reduce.hip)
-void trace_add(const char* rec);
 
 constexpr int PL_SLOTS = 32;               // parallel fold chains per (sequence, column)
 constexpr int PL_BLOCK_TOK = SEG_BLOCK_TOK; // tokens per block = 64 per slot
@@ -568,8 +565,6 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_pool_backward_kernel(
 }
 
 // ---------------------------------------------------------------- host side
-static bool pl_trace() { return g_trace_on.load(std::memory_order_relaxed) != 0; }
-
 template <typename E>
 static int pl_forward(const rua_layout& L, const void* v, const void* sc, void* out, int oacc, void* lse, int64_t H,
                       int64_t D, hipStream_t s) {
@@ -582,18 +577,14 @@ static int pl_forward(const rua_layout& L, const void* v, const void* sc, void* 
   if (((uint64_t)(uintptr_t)v | (uint64_t)(uintptr_t)sc) % sizeof(raw) || (uint64_t)(uintptr_t)lse % sizeof(A) ||
       (uint64_t)(uintptr_t)out % (oacc ? sizeof(A) : sizeof(raw)))
     return RUA_EALIGN;
-  char rec[200];
 
   if (row_bytes <= 16) {
     const seg_lanes ln = seg_lanes_geometry(row_bytes, (uint64_t)(uintptr_t)v, L.B);
     const int W = ln.W;
     const int64_t grid = ln.grid;
     if (!grid) return RUA_ERANGE;
-    if (pl_trace()) {
-      snprintf(rec, sizeof rec, "seg_pool_lanes_kernel T=%s AL=%d W=%d H=%d D=%d kind=%d", E::name(), (int)(W == 16), W,
-               (int)H, (int)D, L.kind);
-      trace_add(rec);
-    }
+    seg_trace("seg_pool_lanes_kernel T=%s AL=%d W=%d H=%d D=%d kind=%d", E::name(), (int)(W == 16), W, (int)H, (int)D,
+              L.kind);
     hipLaunchKernelGGL((seg_pool_lanes_kernel<E>), dim3((unsigned)grid), dim3(RUA_BLOCK), 0, s, L, (const char*)v,
                        (const raw*)sc, out, oacc, (A*)lse, (int)H, (int)D, (int)G, W);
     return (int)hipGetLastError();
@@ -604,11 +595,8 @@ static int pl_forward(const rua_layout& L, const void* v, const void* sc, void* 
   const bool lane = D % VE == 0;
   const int64_t grid = L.B * (int64_t)n_chunks;
   if (row_bytes + 127 > 0x7fffffffLL * 128 || grid > 0x7fffffffLL) return RUA_ERANGE;
-  if (pl_trace()) {
-    snprintf(rec, sizeof rec, "seg_pool_rows_kernel T=%s AL=%d lane=%d D=%lld kind=%d chunks=%d", E::name(), (int)al,
-             (int)lane, (long long)D, L.kind, n_chunks);
-    trace_add(rec);
-  }
+  seg_trace("seg_pool_rows_kernel T=%s AL=%d lane=%d D=%lld kind=%d chunks=%d", E::name(), (int)al, (int)lane,
+            (long long)D, L.kind, n_chunks);
 #define RUA_PL_ROWS(ALV, LANEV)                                                                                        \
   hipLaunchKernelGGL((seg_pool_rows_kernel<E, ALV, LANEV>), dim3((unsigned)grid), dim3(RUA_BLOCK), 0, s, L,            \
                      (const raw*)v, (const raw*)sc, out, oacc, (A*)lse, H, D, G, n_chunks)
@@ -631,18 +619,14 @@ static int pl_backward(const rua_layout& L, const void* go, const void* v, const
   if (all % sizeof(raw) || (uint64_t)(uintptr_t)lse % sizeof(A) ||
       (uint64_t)(uintptr_t)out % (oacc ? sizeof(A) : sizeof(raw)))
     return RUA_EALIGN;
-  char rec[200];
 
   if (row_bytes <= 16) {
     const seg_lanes ln = seg_lanes_geometry(row_bytes, wide, L.B);
     const int W = ln.W;
     const int64_t grid = ln.grid;
     if (!grid) return RUA_ERANGE;
-    if (pl_trace()) {
-      snprintf(rec, sizeof rec, "seg_pool_backward_kernel T=%s AL=%d form=lanes W=%d H=%d D=%d kind=%d", E::name(),
-               (int)(W == 16), W, (int)H, (int)D, L.kind);
-      trace_add(rec);
-    }
+    seg_trace("seg_pool_backward_kernel T=%s AL=%d form=lanes W=%d H=%d D=%d kind=%d", E::name(), (int)(W == 16), W,
+              (int)H, (int)D, L.kind);
     hipLaunchKernelGGL((seg_pool_backward_lanes_kernel<E>), dim3((unsigned)grid), dim3(RUA_BLOCK), 0, s, L,
                        (const char*)v, (const raw*)sc, out, oacc, (const raw*)go, (const A*)lse, (char*)gv,
                        (raw*)gs, (int)H, (int)D, (int)G, W);
@@ -655,11 +639,8 @@ static int pl_backward(const rua_layout& L, const void* go, const void* v, const
   const int64_t DU = vec ? D / VE : D;
   int S = 1;
   while (S < RUA_WAVE && S < DU) S <<= 1;
-  if (pl_trace()) {
-    snprintf(rec, sizeof rec, "seg_pool_backward_kernel T=%s AL=%d form=team UE=%d S=%d D=%lld kind=%d", E::name(), (int)al,
-             vec ? VE : 1, S, (long long)D, L.kind);
-    trace_add(rec);
-  }
+  seg_trace("seg_pool_backward_kernel T=%s AL=%d form=team UE=%d S=%d D=%lld kind=%d", E::name(), (int)al, vec ? VE : 1,
+            S, (long long)D, L.kind);
 #define RUA_PL_BWD(ALV, UEV)                                                                                           \
   hipLaunchKernelGGL((seg_pool_backward_kernel<E, ALV, UEV>), dim3((unsigned)L.B), dim3(RUA_BLOCK), 0, s, L,           \
                      (const raw*)v, (const raw*)sc, out, oacc, (const raw*)go, (const A*)lse, (raw*)gv, (raw*)gs,       \
@@ -698,14 +679,9 @@ extern "C" int rua_segment_softmax_pool(const rua_layout* lay, const void* value
   if (lay->B == 0 || lay->n_rows == 0 || H == 0) return 0;
   if (!values || !scores || !out) return RUA_EINVAL;
   if (seg_too_large(lay, H, seg_esize(dtype, false))) return RUA_ERANGE;
-  hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case RUA_F32:  return pl_forward<sm_f32>(*lay, values, scores, out, oacc, lse, H, D, s);
-    case RUA_BF16: return pl_forward<sm_bf16>(*lay, values, scores, out, oacc, lse, H, D, s);
-    case RUA_F16:  return pl_forward<sm_f16>(*lay, values, scores, out, oacc, lse, H, D, s);
-    case RUA_F64:  return pl_forward<sm_f64>(*lay, values, scores, out, oacc, lse, H, D, s);
-  }
-  return RUA_EINVAL;
+#define RUA_PL(E) pl_forward<E>(*lay, values, scores, out, oacc, lse, H, D, (hipStream_t)stream)
+  RUA_DISPATCH_FLOAT(dtype, RUA_PL);
+#undef RUA_PL
 }
 
 extern "C" int rua_segment_softmax_pool_backward(const rua_layout* lay, const void* grad_out, const void* values,
@@ -724,12 +700,8 @@ extern "C" int rua_segment_softmax_pool_backward(const rua_layout* lay, const vo
   if (!grad_values && !grad_scores) return 0;
   if (!grad_out || !values || !scores || !out || !lse) return RUA_EINVAL;
   if (seg_too_large(lay, H, seg_esize(dtype, false))) return RUA_ERANGE;
-  hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case RUA_F32:  return pl_backward<sm_f32>(*lay, grad_out, values, scores, out, oacc, lse, grad_values, grad_scores, H, D, s);
-    case RUA_BF16: return pl_backward<sm_bf16>(*lay, grad_out, values, scores, out, oacc, lse, grad_values, grad_scores, H, D, s);
-    case RUA_F16:  return pl_backward<sm_f16>(*lay, grad_out, values, scores, out, oacc, lse, grad_values, grad_scores, H, D, s);
-    case RUA_F64:  return pl_backward<sm_f64>(*lay, grad_out, values, scores, out, oacc, lse, grad_values, grad_scores, H, D, s);
-  }
-  return RUA_EINVAL;
+#define RUA_PL(E)                                                                                                      \
+  pl_backward<E>(*lay, grad_out, values, scores, out, oacc, lse, grad_values, grad_scores, H, D, (hipStream_t)stream)
+  RUA_DISPATCH_FLOAT(dtype, RUA_PL);
+#undef RUA_PL
 }

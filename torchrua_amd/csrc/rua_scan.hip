@@ -30,14 +30,11 @@
 #include <stdint.h>
 #include <string.h>
 #include <atomic>
-#include "rua_seg.h"
+#include "rua_seg_launch.h"
 
 #pragma clang fp contract(off)
 
 namespace rua {
-
-extern std::atomic<int> g_trace_on;        // the dispatch trace (rua_reduce.hip)
-void trace_add(const char* rec);
 
 constexpr int SC_GROUP = 8;                // positions scanned by doubling steps
 constexpr int SC_SLOTS = 32;               // positions of a tile = 4 groups
@@ -46,7 +43,6 @@ constexpr int SC_TILES = SC_BLOCK_TOK / SC_SLOTS;
 constexpr int SC_LPR = 8;                  // rows form: 16-byte lanes per row chunk (128 bytes)
 constexpr int SC_ROWS_UNR = 4;             // rows form: tiles in flight per workgroup (one barrier for the four)
 constexpr int SC_LANES_UNR = 4;            // lanes form: tiles in flight per half wave
-enum { SC_FULL = 0, SC_PARTIAL = 1, SC_FINISH = 2 };
 static_assert(SC_SLOTS == 4 * SC_GROUP && SC_SLOTS * SC_LPR == RUA_BLOCK && SC_GROUP * SC_LPR == RUA_WAVE,
               "a group is a wave of the rows form, a tile is its workgroup");
 
@@ -54,10 +50,6 @@ static_assert(SC_SLOTS == 4 * SC_GROUP && SC_SLOTS * SC_LPR == RUA_BLOCK && SC_G
 template <typename B> struct sc_float : B {
   static __device__ __forceinline__ typename B::acc ident() { return (typename B::acc)(-0.0); }
 };
-using sc_f32 = sc_float<sm_f32>;
-using sc_f64 = sc_float<sm_f64>;
-using sc_bf16 = sc_float<sm_bf16>;
-using sc_f16 = sc_float<sm_f16>;
 struct sc_i64 {                            // unsigned accumulation: the sum wraps
   using raw = int64_t; using acc = unsigned long long;
   static __device__ __forceinline__ acc up(raw v) { return (acc)v; }
@@ -174,7 +166,7 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_cumsum_lanes_kernel(rua_layout 
 // owns the l-th 16-byte vector of the chunk.  A group is the 8 slots of one wave (doubling steps by shuffles over 8, 16
 // and 32 lanes); the four group totals of a tile cross the waves through LDS — four tiles per barrier, two buffers in
 // turn, so one barrier per 128 rows.  Base and carry are kept by every thread (the same values in all of them).
-// mode SC_PARTIAL / SC_FINISH: the CUT form — a workgroup per (sequence, block of 2 048 positions, chunk) leaves its
+// mode SEG_PARTIAL / SEG_FINISH: the CUT form — a workgroup per (sequence, block of 2 048 positions, chunk) leaves its
 // block's total in `ws`, and a second launch adds the totals of the blocks before its own and scans the block.
 // AL = false: rows or bases off 16 bytes — the same geometry with elementwise accesses.
 template <typename E, bool AL>
@@ -194,19 +186,19 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_cumsum_rows_kernel(rua_layout L
   const int c = (int)(blockIdx.x % (unsigned)n_chunks);
   int64_t b = blockIdx.x / (unsigned)n_chunks;
   int blk = 0;
-  if (mode != SC_FULL) { blk = (int)(b % maxblk); b /= maxblk; }
+  if (mode != SEG_FULL) { blk = (int)(b % maxblk); b /= maxblk; }
   if (b >= L.B) return;
   const int64_t len = safe_len(L, b);
   // the cut form sized `ws` and the grid from the host's length bound: a CAT layout whose T_log understates a length
   // must not walk past the maxblk blocks that exist (rua.h: T_log has to be a true bound)
   const int64_t have_blk = (len + SC_BLOCK_TOK - 1) / SC_BLOCK_TOK;
-  const int64_t nblk = mode != SC_FULL && have_blk > maxblk ? maxblk : have_blk;
-  if (mode != SC_FULL && blk > 0 && blk >= nblk) return;     // workgroup-uniform
+  const int64_t nblk = mode != SEG_FULL && have_blk > maxblk ? maxblk : have_blk;
+  if (mode != SEG_FULL && blk > 0 && blk >= nblk) return;     // workgroup-uniform
   const int64_t col0 = (int64_t)c * CW + (int64_t)l * VE;
   const int nval = H - col0 >= VE ? VE : (H - col0 > 0 ? (int)(H - col0) : 0);
   const bool active = nval > 0;
   int64_t ub = 0, ue = len;                                  // positions along the scan
-  if (mode != SC_FULL) {
+  if (mode != SEG_FULL) {
     ub = (int64_t)blk * SC_BLOCK_TOK;
     ue = len < ub + SC_BLOCK_TOK ? len : ub + SC_BLOCK_TOK;
     if (ub > ue) ub = ue;
@@ -234,7 +226,7 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_cumsum_rows_kernel(rua_layout L
   A base[VE], car[VE];
 #pragma unroll
   for (int e = 0; e < VE; ++e) base[e] = car[e] = E::ident();
-  if (mode == SC_FINISH) {
+  if (mode == SEG_FINISH) {
     for (int64_t k = 0; k < blk; ++k) {
       const A* p = ws + ((((b * maxblk + k) * n_chunks + c) * SC_LPR + l) * VE);
 #pragma unroll
@@ -295,14 +287,14 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_cumsum_rows_kernel(rua_layout L
                                    xch[buf][k][3][l][e], w);
         o.e[e] = E::down(pre + v[k][e]);
       }
-      if (mode != SC_PARTIAL && rows[k] >= 0) st(rows[k], o);
-      if (mode == SC_FULL && (tile0 / SC_SLOTS + 1) % SC_TILES == 0) {      // the block ends: its total joins the base
+      if (mode != SEG_PARTIAL && rows[k] >= 0) st(rows[k], o);
+      if (mode == SEG_FULL && (tile0 / SC_SLOTS + 1) % SC_TILES == 0) {      // the block ends: its total joins the base
 #pragma unroll
         for (int e = 0; e < VE; ++e) { base[e] = base[e] + car[e]; car[e] = E::ident(); }
       }
     }
   }
-  if (mode == SC_PARTIAL) {
+  if (mode == SEG_PARTIAL) {
     if (tid < SC_LPR) {
       A* p = ws + ((((b * maxblk + blk) * n_chunks + c) * SC_LPR + l) * VE);
 #pragma unroll
@@ -336,58 +328,38 @@ static int sc_launch(const rua_layout& L, const void* x, void* out, int64_t H, i
   using A = typename E::acc;
   const int64_t row_bytes = H * (int64_t)sizeof(raw);
   const uint64_t bases = (uint64_t)(uintptr_t)x | (uint64_t)(uintptr_t)out;
-  char rec[200];
   if (bases % sizeof(raw)) return RUA_EALIGN;                 // (elements themselves are always aligned)
 
   if (row_bytes <= 16) {
     const seg_lanes ln = seg_lanes_geometry(row_bytes, bases, L.B);
-    const int W = ln.W;
-    const int64_t grid = ln.grid;
-    if (!grid) return RUA_ERANGE;
-    if (g_trace_on.load(std::memory_order_relaxed)) {
-      const uint64_t own = (uint64_t)row_bytes | 16u;           // AL: the bases did not narrow the row's own access width
-      snprintf(rec, sizeof rec, "seg_cumsum_lanes_kernel T=%s W=%d H=%d AL=%d rev=%d kind=%d", E::name(), W, (int)H,
-               (int)(W == (int)(own & (~own + 1))), rev, L.kind);
-      trace_add(rec);
-    }
-    hipLaunchKernelGGL((seg_cumsum_lanes_kernel<E>), dim3((unsigned)grid), dim3(RUA_BLOCK), 0, s, L, (const char*)x,
-                       (char*)out, (int)H, W, rev);
+    if (!ln.grid) return RUA_ERANGE;
+    const uint64_t own = (uint64_t)row_bytes | 16u;             // AL: the bases did not narrow the row's own access width
+    seg_trace("seg_cumsum_lanes_kernel T=%s W=%d H=%d AL=%d rev=%d kind=%d", E::name(), ln.W, (int)H,
+              (int)(ln.W == (int)(own & (~own + 1))), rev, L.kind);
+    hipLaunchKernelGGL((seg_cumsum_lanes_kernel<E>), dim3((unsigned)ln.grid), dim3(RUA_BLOCK), 0, s, L, (const char*)x,
+                       (char*)out, (int)H, ln.W, rev);
     return (int)hipGetLastError();
   }
 
-  const seg_plan p = sc_make_plan(L, H, dtype);
-  const bool al = row_bytes % 16 == 0 && bases % 16 == 0;
-  const bool cut = ws != nullptr && p.maxblk > 0;
-  const int64_t grid = seg_rows_grid(L, p, cut);
-  if (!grid) return RUA_ERANGE;
-
-#define RUA_SC_ROWS(ALV, MODE)                                                                                         \
-  hipLaunchKernelGGL((seg_cumsum_rows_kernel<E, ALV>), dim3((unsigned)grid), dim3(RUA_BLOCK), 0, s, L, (const raw*)x,   \
-                     (raw*)out, H, p.n_chunks, MODE, cut ? p.maxblk : 1, (A*)ws, rev)
-  const bool tr = g_trace_on.load(std::memory_order_relaxed) != 0;
-  if (cut) {
-    if (tr) {
-      snprintf(rec, sizeof rec, "seg_cumsum_rows_kernel T=%s AL=%d rev=%d kind=%d cut=1 phase=partial blocks=%d chunks=%d",
-               E::name(), (int)al, rev, L.kind, p.maxblk, p.n_chunks);
-      trace_add(rec);
-      snprintf(rec, sizeof rec, "seg_cumsum_rows_kernel T=%s AL=%d rev=%d kind=%d cut=1 phase=finish blocks=%d chunks=%d",
-               E::name(), (int)al, rev, L.kind, p.maxblk, p.n_chunks);
-      trace_add(rec);
-    }
-    if (al) RUA_SC_ROWS(true, SC_PARTIAL); else RUA_SC_ROWS(false, SC_PARTIAL);
-    int e = (int)hipGetLastError();
-    if (e) return e;
-    if (al) RUA_SC_ROWS(true, SC_FINISH); else RUA_SC_ROWS(false, SC_FINISH);
-    return (int)hipGetLastError();
-  }
-  if (tr) {
-    snprintf(rec, sizeof rec, "seg_cumsum_rows_kernel T=%s AL=%d rev=%d kind=%d cut=0 chunks=%d", E::name(), (int)al, rev,
-             L.kind, p.n_chunks);
-    trace_add(rec);
-  }
-  if (al) RUA_SC_ROWS(true, SC_FULL); else RUA_SC_ROWS(false, SC_FULL);
-#undef RUA_SC_ROWS
-  return (int)hipGetLastError();
+  const seg_rows r = seg_rows_form(sc_make_plan(L, H, dtype), L, row_bytes, bases, ws != nullptr);
+  const seg_plan& p = r.p;
+  if (!r.grid) return RUA_ERANGE;
+  return seg_launch_rows(
+      r,
+      [&](int mode) {
+        seg_with_al(r.al, [&](auto AL) {
+          hipLaunchKernelGGL((seg_cumsum_rows_kernel<E, decltype(AL)::value>), dim3((unsigned)r.grid), dim3(RUA_BLOCK), 0,
+                             s, L, (const raw*)x, (raw*)out, H, p.n_chunks, mode, r.cut ? p.maxblk : 1, (A*)ws, rev);
+        });
+      },
+      [&](const char* phase) {
+        if (phase)
+          seg_trace("seg_cumsum_rows_kernel T=%s AL=%d rev=%d kind=%d cut=1 phase=%s blocks=%d chunks=%d", E::name(),
+                    (int)r.al, rev, L.kind, phase, p.maxblk, p.n_chunks);
+        else
+          seg_trace("seg_cumsum_rows_kernel T=%s AL=%d rev=%d kind=%d cut=0 chunks=%d", E::name(), (int)r.al, rev, L.kind,
+                    p.n_chunks);
+      });
 }
 
 static int sc_dispatch(const rua_layout* lay, const void* x, void* out, int64_t H, int32_t dtype, int32_t reverse,
@@ -398,16 +370,12 @@ static int sc_dispatch(const rua_layout* lay, const void* x, void* out, int64_t 
   if (lay->B == 0 || lay->n_rows == 0 || H == 0) return 0;
   if (!x || !out) return RUA_EINVAL;
   if (seg_too_large(lay, H, es)) return RUA_ERANGE;
-  hipStream_t s = (hipStream_t)stream;
-  const int rev = reverse ? 1 : 0;
-  switch (dtype) {
-    case RUA_F32:  return sc_launch<sc_f32>(*lay, x, out, H, dtype, rev, ws, s);
-    case RUA_BF16: return sc_launch<sc_bf16>(*lay, x, out, H, dtype, rev, ws, s);
-    case RUA_F16:  return sc_launch<sc_f16>(*lay, x, out, H, dtype, rev, ws, s);
-    case RUA_F64:  return sc_launch<sc_f64>(*lay, x, out, H, dtype, rev, ws, s);
-    case RUA_I64:  return sc_launch<sc_i64>(*lay, x, out, H, dtype, rev, ws, s);
-  }
-  return RUA_EINVAL;
+#define RUA_SC(E) sc_launch<E>(*lay, x, out, H, dtype, reverse ? 1 : 0, ws, (hipStream_t)stream)
+#define RUA_SC_FLOAT(B) RUA_SC(sc_float<B>)
+  if (dtype == RUA_I64) return RUA_SC(sc_i64);
+  RUA_DISPATCH_FLOAT(dtype, RUA_SC_FLOAT);
+#undef RUA_SC_FLOAT
+#undef RUA_SC
 }
 
 }  // namespace rua

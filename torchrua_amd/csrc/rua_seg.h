@@ -2,7 +2,8 @@
 // rua_linear_scan.hip, rua_pool.hip, rua_norm.hip, rua_conv.hip, rua_compress.hip, rua_join.hip, rua_repeat.hip) share:
 // the element types, the clamped sequence length, the padding test and fill, the block range of the cut form, rows
 // moved as bits, narrow-row accesses and the exp / log / inf / nan / shuffle one-liners.  Their host side — checks, cut
-// plan, lanes geometry, access width — is rua_seg_plan.h; the offsets scan of compress and repeat is rua_seg_scan.h.
+// plan, lanes geometry, access width — is rua_seg_plan.h, what the fold operators' launchers do after it (trace, dtype
+// switch, the sequencing of a rows launch) rua_seg_launch.h; the offsets scan of compress and repeat is rua_seg_scan.h.
 #pragma once
 #include "rua_dev.h"
 #include "rua_seg_plan.h"

@@ -1,7 +1,8 @@
 // rua_seg_plan.h — what the per-sequence operators (softmax, cumsum, argreduce, linear_scan, softmax_pool, norm, conv,
 // compress, join, repeat_interleave) decide BEFORE their first HIP call, as plain host C++ (no HIP header): the element
-// size, the layout and entry checks, the cut plan, the launch geometry of the lanes form, the access width of the
-// operators that move rows as bits and the plan of the offsets scan.  One place for all of them: a new operator of the
+// size, the layout and entry checks, the cut plan, the form of a rows launch and the slab rule of the two-walk
+// operators, the launch geometry of the lanes form, the access width of the operators that move rows as bits and the
+// plan of the offsets scan.  One place for all of them: a new operator of the
 // family takes these and adds only its kernels, its pointer checks and the bytes it keeps per (block, padded column).
 #pragma once
 #include <stdint.h>
@@ -14,6 +15,8 @@ constexpr int64_t SEG_CUT_MAX_UNITS = 1024;     // fewer (sequence x chunk) unit
 constexpr int64_t SEG_CUT_MIN_LEN = 4 * SEG_BLOCK_TOK;   // ... when the sequences are this long: cut them across workgroups
 constexpr int64_t SEG_CUT_MAX_BLOCKS = 0x7fffffff / SEG_CUT_MAX_UNITS;   // units x blocks has to fit a grid
 constexpr int SEG_WAVES_PER_BLOCK = 4;          // (rua_seg.h checks it against RUA_WAVES_PER_BLOCK)
+// the `mode` of a rows kernel: the whole sequence, or the two launches of the cut form
+enum { SEG_FULL = 0, SEG_PARTIAL = 1, SEG_FINISH = 2 };
 
 // bytes of an element; 0 = the family does not take the dtype (`allow_i64`: the operators that only add or compare)
 static int seg_esize(int32_t dtype, bool allow_i64) {
@@ -92,6 +95,27 @@ static seg_plan seg_make_plan(const rua_layout& L, int64_t H, int es, int ws_byt
 static int64_t seg_rows_grid(const rua_layout& L, const seg_plan& p, bool cut) {
   const int64_t grid = L.B * (int64_t)p.n_chunks * (cut ? p.maxblk : 1);
   return p.n_chunks <= 0 || grid > 0x7fffffffLL ? 0 : grid;
+}
+
+// what a rows-form launcher decides after its plan: `al`, every access a whole aligned 16-byte vector (`bases`: the
+// addresses ORed together); `cut`, the cut form (the plan asks for it and the caller brought the workspace); the grid of
+// the launch (seg_rows_grid; a cut grid always fits: fewer than SEG_CUT_MAX_UNITS units x at most SEG_CUT_MAX_BLOCKS)
+struct seg_rows { seg_plan p; bool al; bool cut; int64_t grid; };
+static seg_rows seg_rows_form(const seg_plan& p, const rua_layout& L, int64_t row_bytes, uint64_t bases, bool ws_given) {
+  const bool cut = ws_given && p.maxblk > 0;
+  return {p, row_bytes % 16 == 0 && bases % 16 == 0, cut, seg_rows_grid(L, p, cut)};
+}
+
+// rows of the LDS slab of the two-walk operators (softmax, norm), 0 = stream.  Resident when the sequences can be
+// expected to fit a slab: the host's bound, or twice the average where a CattedSequence came without one; the bound in
+// whole rounds of `slots` rows, at most `most`.  A longer sequence streams inside the same launch (the same bits).
+// L.B > 0.
+static int seg_slab_cap(const rua_layout& L, bool cut, int slots, int64_t most) {
+  const int64_t bound = sm_len_bound(L);
+  const int64_t expect = (L.kind == RUA_CAT && !(L.T_log > 0)) ? 2 * (L.n_rows / L.B) : bound;
+  if (cut || expect > 1024) return 0;
+  const int64_t need = (bound + slots - 1) / slots * slots;
+  return (int)(need < most ? need : most);
 }
 
 // bytes per access of the operators that move rows as bits: the widest power of two, up to 16, that divides the row and

@@ -21,14 +21,11 @@
 #include <stdint.h>
 #include <string.h>
 #include <atomic>
-#include "rua_seg.h"
+#include "rua_seg_launch.h"
 
 #pragma clang fp contract(off)
 
 namespace rua {
-
-extern std::atomic<int> g_trace_on;        // the dispatch trace (rua_reduce.hip)
-void trace_add(const char* rec);
 
 constexpr int SM_SLOTS = 32;               // parallel fold chains per (sequence, column)
 constexpr int SM_BLOCK_TOK = SEG_BLOCK_TOK; // tokens per block = 64 per slot
@@ -37,7 +34,6 @@ constexpr int SM_ROWS_UNR = 4;             // row forms: rows in flight per thre
 constexpr int SM_LANES_UNR = 8;            // lanes form: tokens a lane keeps in registers (sequences up to 256 tokens)
 constexpr int SM_CAP_FWD = 512;            // resident rows of a slab: 512 x 128 B = 64 KiB, two workgroups per CU
 constexpr int SM_CAP_BWD = 256;            // the backward keeps y AND g
-enum { SM_FULL = 0, SM_PARTIAL = 1, SM_FINISH = 2 };
 
 // ---------------------------------------------------------------- the fold
 // online (max, sum): one exp per element.  NaN and +inf poison the sum (torch: the whole column of the sequence is NaN);
@@ -202,7 +198,7 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_softmax_lanes_kernel(rua_layout
 // 16-byte vector of the chunk.  RESIDENT (len <= cap_rows): walk 1 parks every vector in LDS in the payload dtype —
 // each thread reads back exactly what it stored, so the slab needs no barrier — and walk 2 normalises out of LDS: the
 // payload crosses HBM once.  Otherwise STREAMING: walk 2 reads global memory again (the same workgroup, so L2 / the
-// Infinity Cache may serve it).  mode SM_PARTIAL / SM_FINISH: the CUT form — a workgroup per (sequence, block of 2 048
+// Infinity Cache may serve it).  mode SEG_PARTIAL / SEG_FINISH: the CUT form — a workgroup per (sequence, block of 2 048
 // tokens, chunk) leaves its block's (max, sum) in `ws`, and a second launch folds them in block order and normalises.
 // AL = false: rows or bases off 16 bytes — the same geometry with elementwise accesses.
 template <typename E, bool BWD, bool AL>
@@ -226,24 +222,24 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_softmax_rows_kernel(rua_layout 
   const int c = (int)(blockIdx.x % (unsigned)n_chunks);
   int64_t b = blockIdx.x / (unsigned)n_chunks;
   int blk = 0;
-  if (mode != SM_FULL) { blk = (int)(b % maxblk); b /= maxblk; }
+  if (mode != SEG_FULL) { blk = (int)(b % maxblk); b /= maxblk; }
   if (b >= L.B) return;
   const int64_t len = safe_len(L, b);
   // the cut form sized `ws` and the grid from the host's length bound: a CAT layout whose T_log understates a length
   // must not walk past the maxblk blocks that exist (rua.h: T_log has to be a true bound for a right result)
   const int64_t have_blk = (len + SM_BLOCK_TOK - 1) / SM_BLOCK_TOK;
-  const int64_t nblk = mode != SM_FULL && have_blk > maxblk ? maxblk : have_blk;
-  if (mode != SM_FULL && blk > 0 && blk >= nblk) return;   // workgroup-uniform
+  const int64_t nblk = mode != SEG_FULL && have_blk > maxblk ? maxblk : have_blk;
+  if (mode != SEG_FULL && blk > 0 && blk >= nblk) return;   // workgroup-uniform
   const int64_t col0 = (int64_t)c * CW + (int64_t)l * VE;
   const int nval = H - col0 >= VE ? VE : (H - col0 > 0 ? (int)(H - col0) : 0);
   const bool active = nval > 0;
   int64_t tb = 0, te = len;
-  if (mode != SM_FULL) {
+  if (mode != SEG_FULL) {
     tb = (int64_t)blk * SM_BLOCK_TOK;
     te = len < tb + SM_BLOCK_TOK ? len : tb + SM_BLOCK_TOK;
     if (tb > te) tb = te;
   }
-  const bool resident = mode == SM_FULL && len <= cap_rows;
+  const bool resident = mode == SEG_FULL && len <= cap_rows;
 
   auto ld = [&](const raw* base, int64_t row, Vec& v) {
     const raw* p = base + row * H + col0;
@@ -268,7 +264,7 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_softmax_rows_kernel(rua_layout 
 #pragma unroll
   for (int e = 0; e < VE; ++e) { M[e] = -seg_inf<A>(); S[e] = (A)0; }
 
-  if (mode == SM_FINISH) {
+  if (mode == SEG_FINISH) {
     for (int64_t k = 0; k < nblk; ++k) {
       const A* p = ws + ((((b * maxblk + k) * n_chunks + c) * SM_LPR + l) * VE) * 2;
 #pragma unroll
@@ -362,7 +358,7 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_softmax_rows_kernel(rua_layout 
           s[e] = vs[0];
         }
       }
-      if (mode == SM_PARTIAL) {
+      if (mode == SEG_PARTIAL) {
         if (tid < SM_LPR) {
           A* p = ws + ((((b * maxblk + blk) * n_chunks + c) * SM_LPR + l) * VE) * 2;
 #pragma unroll
@@ -376,7 +372,7 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_softmax_rows_kernel(rua_layout 
         }
       }
     }
-    if (mode == SM_PARTIAL) return;
+    if (mode == SEG_PARTIAL) return;
   }
   if (!active) return;
   if constexpr (!BWD) {
@@ -444,45 +440,24 @@ static int sm_launch(const rua_layout& L, const void* x, const void* g, void* ou
   const int64_t row_bytes = H * (int64_t)sizeof(raw);
   const uint64_t bases = (uint64_t)(uintptr_t)x | (uint64_t)(uintptr_t)g | (uint64_t)(uintptr_t)out;
   const char* dir = BWD ? "_backward" : "";
-  char rec[200];
   if (bases % sizeof(raw)) return RUA_EALIGN;                 // (elements themselves are always aligned)
 
   if (row_bytes <= 16) {
     const seg_lanes ln = seg_lanes_geometry(row_bytes, bases, L.B);
-    const int W = ln.W;
-    const int64_t grid = ln.grid;
-    if (!grid) return RUA_ERANGE;
-    if (g_trace_on.load(std::memory_order_relaxed)) {
-      snprintf(rec, sizeof rec, "seg_softmax%s_lanes_kernel T=%s W=%d H=%d log=%d kind=%d", dir, E::name(), W, (int)H, lg,
-               L.kind);
-      trace_add(rec);
-    }
-    hipLaunchKernelGGL((seg_softmax_lanes_kernel<E, BWD>), dim3((unsigned)grid), dim3(RUA_BLOCK), 0, s, L, (const char*)x,
-                       (const char*)g, (char*)out, (int)H, W, lg);
+    if (!ln.grid) return RUA_ERANGE;
+    seg_trace("seg_softmax%s_lanes_kernel T=%s W=%d H=%d log=%d kind=%d", dir, E::name(), ln.W, (int)H, lg, L.kind);
+    hipLaunchKernelGGL((seg_softmax_lanes_kernel<E, BWD>), dim3((unsigned)ln.grid), dim3(RUA_BLOCK), 0, s, L,
+                       (const char*)x, (const char*)g, (char*)out, (int)H, ln.W, lg);
     return (int)hipGetLastError();
   }
 
-  const seg_plan p = sm_make_plan(L, H, dtype);
-  const bool al = row_bytes % 16 == 0 && bases % 16 == 0;
-  const bool cut = ws != nullptr && p.maxblk > 0;
+  const seg_rows r = seg_rows_form(sm_make_plan(L, H, dtype), L, row_bytes, bases, ws != nullptr);
+  const seg_plan& p = r.p;
   constexpr int XCH_BYTES = RUA_WAVES_PER_BLOCK * SM_LPR * VE * 2 * (int)sizeof(A);
-  // resident when the sequences can be expected to fit a slab: the host's bound, or twice the average where a
-  // CattedSequence came without one.  A longer sequence streams inside the same launch (the result is the same bits).
-  const int64_t bound = sm_len_bound(L);
-  const int64_t expect = (L.kind == RUA_CAT && !(L.T_log > 0)) ? 2 * (L.n_rows / L.B) : bound;
-  int cap = 0;
-  if (!cut && expect <= 1024) {
-    const int64_t most = BWD ? SM_CAP_BWD : SM_CAP_FWD;
-    const int64_t need = (bound + SM_SLOTS - 1) / SM_SLOTS * SM_SLOTS;
-    cap = (int)(need < most ? need : most);
-  }
+  int cap = seg_slab_cap(L, r.cut, SM_SLOTS, BWD ? SM_CAP_BWD : SM_CAP_FWD);
   size_t lds = XCH_BYTES + (size_t)cap * 128 * (BWD ? 2 : 1);
-  const int64_t grid = seg_rows_grid(L, p, cut);
-  if (!grid) return RUA_ERANGE;
+  if (!r.grid) return RUA_ERANGE;
 
-#define RUA_SM_ROWS(ALV, MODE)                                                                                         \
-  hipLaunchKernelGGL((seg_softmax_rows_kernel<E, BWD, ALV>), dim3((unsigned)grid), dim3(RUA_BLOCK), lds, s, L,          \
-                     (const raw*)x, (const raw*)g, (raw*)out, H, p.n_chunks, cap, MODE, cut ? p.maxblk : 1, (A*)ws, lg)
   if (lds > 64 * 1024) {
     // more than 64 KiB of dynamic LDS has to be asked for, once per kernel AND DEVICE (the attribute belongs to the
     // device's copy of the function); where the runtime refuses, a smaller slab.  A device number beyond the table
@@ -492,14 +467,15 @@ static int sm_launch(const rua_layout& L, const void* x, const void* g, void* ou
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = -1; }
     std::atomic<int> never{0};
-    std::atomic<int>& st = dev >= 0 && dev < MAX_DEV ? big_ok[al ? 1 : 0][dev] : never;
+    std::atomic<int>& st = dev >= 0 && dev < MAX_DEV ? big_ok[r.al ? 1 : 0][dev] : never;
     int v = st.load(std::memory_order_relaxed);
     if (v == 0) {
       const int want = XCH_BYTES + (BWD ? SM_CAP_BWD * 2 : SM_CAP_FWD) * 128;
-      const hipError_t e = al ? hipFuncSetAttribute((const void*)seg_softmax_rows_kernel<E, BWD, true>,
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, want)
-                              : hipFuncSetAttribute((const void*)seg_softmax_rows_kernel<E, BWD, false>,
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, want);
+      hipError_t e = hipSuccess;
+      seg_with_al(r.al, [&](auto AL) {
+        e = hipFuncSetAttribute((const void*)seg_softmax_rows_kernel<E, BWD, decltype(AL)::value>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, want);
+      });
       v = e == hipSuccess ? 1 : -1;
       if (e != hipSuccess) (void)hipGetLastError();
       st.store(v, std::memory_order_relaxed);
@@ -509,30 +485,23 @@ static int sm_launch(const rua_layout& L, const void* x, const void* g, void* ou
       lds = XCH_BYTES + (size_t)cap * 128 * (BWD ? 2 : 1);
     }
   }
-  const bool tr = g_trace_on.load(std::memory_order_relaxed) != 0;
-  if (cut) {
-    if (tr) {
-      snprintf(rec, sizeof rec, "seg_softmax%s_stream_kernel T=%s AL=%d log=%d kind=%d cut=1 phase=partial blocks=%d chunks=%d",
-               dir, E::name(), (int)al, lg, L.kind, p.maxblk, p.n_chunks);
-      trace_add(rec);
-      snprintf(rec, sizeof rec, "seg_softmax%s_stream_kernel T=%s AL=%d log=%d kind=%d cut=1 phase=finish blocks=%d chunks=%d",
-               dir, E::name(), (int)al, lg, L.kind, p.maxblk, p.n_chunks);
-      trace_add(rec);
-    }
-    if (al) RUA_SM_ROWS(true, SM_PARTIAL); else RUA_SM_ROWS(false, SM_PARTIAL);
-    int e = (int)hipGetLastError();
-    if (e) return e;
-    if (al) RUA_SM_ROWS(true, SM_FINISH); else RUA_SM_ROWS(false, SM_FINISH);
-    return (int)hipGetLastError();
-  }
-  if (tr) {
-    snprintf(rec, sizeof rec, "seg_softmax%s_%s_kernel T=%s AL=%d log=%d kind=%d cut=0 cap=%d chunks=%d", dir,
-             cap > 0 ? "resident" : "stream", E::name(), (int)al, lg, L.kind, cap, p.n_chunks);
-    trace_add(rec);
-  }
-  if (al) RUA_SM_ROWS(true, SM_FULL); else RUA_SM_ROWS(false, SM_FULL);
-#undef RUA_SM_ROWS
-  return (int)hipGetLastError();
+  return seg_launch_rows(
+      r,
+      [&](int mode) {
+        seg_with_al(r.al, [&](auto AL) {
+          hipLaunchKernelGGL((seg_softmax_rows_kernel<E, BWD, decltype(AL)::value>), dim3((unsigned)r.grid),
+                             dim3(RUA_BLOCK), lds, s, L, (const raw*)x, (const raw*)g, (raw*)out, H, p.n_chunks, cap, mode,
+                             r.cut ? p.maxblk : 1, (A*)ws, lg);
+        });
+      },
+      [&](const char* phase) {
+        if (phase)
+          seg_trace("seg_softmax%s_stream_kernel T=%s AL=%d log=%d kind=%d cut=1 phase=%s blocks=%d chunks=%d", dir,
+                    E::name(), (int)r.al, lg, L.kind, phase, p.maxblk, p.n_chunks);
+        else
+          seg_trace("seg_softmax%s_%s_kernel T=%s AL=%d log=%d kind=%d cut=0 cap=%d chunks=%d", dir,
+                    cap > 0 ? "resident" : "stream", E::name(), (int)r.al, lg, L.kind, cap, p.n_chunks);
+      });
 }
 
 template <bool BWD>
@@ -544,15 +513,9 @@ static int sm_dispatch(const rua_layout* lay, const void* x, const void* g, void
   if (lay->B == 0 || lay->n_rows == 0 || H == 0) return 0;
   if (!x || !out || (BWD && !g)) return RUA_EINVAL;
   if (seg_too_large(lay, H, es)) return RUA_ERANGE;
-  hipStream_t s = (hipStream_t)stream;
-  const int l = lg ? 1 : 0;
-  switch (dtype) {
-    case RUA_F32:  return sm_launch<sm_f32, BWD>(*lay, x, g, out, H, dtype, l, ws, s);
-    case RUA_BF16: return sm_launch<sm_bf16, BWD>(*lay, x, g, out, H, dtype, l, ws, s);
-    case RUA_F16:  return sm_launch<sm_f16, BWD>(*lay, x, g, out, H, dtype, l, ws, s);
-    case RUA_F64:  return sm_launch<sm_f64, BWD>(*lay, x, g, out, H, dtype, l, ws, s);
-  }
-  return RUA_EINVAL;
+#define RUA_SM(E) sm_launch<E, BWD>(*lay, x, g, out, H, dtype, lg ? 1 : 0, ws, (hipStream_t)stream)
+  RUA_DISPATCH_FLOAT(dtype, RUA_SM);
+#undef RUA_SM
 }
 
 }  // namespace rua
