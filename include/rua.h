@@ -901,7 +901,7 @@ int rua_host_pack_scans(const int64_t* lens, int64_t B, const int64_t* batch_siz
 
 /* Introspection: ABI version and the gfx target the code objects were built for. */
 /* Dispatch trace, for tests: while on, every launch of a segmented-reduce kernel (rua_segment_reduce, rua_pack_reduce,
- * rua_segment_reduce_backward, rua_fill_empty) appends one record on the host — the kernel template's name as spelled
+ * rua_segment_reduce_backward, rua_fill_empty) and of the row mover (rua_move_rows) appends one record on the host — the kernel template's name as spelled
  * in rua_reduce_impl.h, then key=value pairs that tell its instantiations apart.  The log is process-global, holds the
  * newest 512 records and costs one relaxed load per dispatch while off.  rua_debug_trace switches it and returns the
  * previous state; rua_debug_trace_take copies whole records, one per line, into `buf`, removes them from the log and
@@ -921,6 +921,16 @@ enum { RUA_PLAN_SEGMENT_REDUCE, RUA_PLAN_PACK_REDUCE, RUA_PLAN_BACKWARD };      
 int64_t rua_debug_reduce_plan(int32_t call, const rua_layout* lay, const rua_layout* pack, int64_t H, int32_t dtype,
                               int32_t op, int32_t include_self, int64_t split_rows, int32_t present, int32_t align,
                               char* buf, int64_t cap);
+/* The plan of a rua_move_rows call, without the call: the ONE record the call would append to the trace — the kernel
+ * family (move_rows_kernel, move_rows_narrow_kernel, move_rows_span_kernel, seq_copy_kernel, pack_tile_lds_kernel,
+ * pack_tile_vec_kernel, pack_roll_tile_kernel, pack_roll_steps_kernel), its template arguments, grid, per_xcd and the
+ * run-time launch parameters — after the same validation and the same plan (csrc/rua_move_plan.h).  Launches nothing and
+ * touches no device.  `dst_addr` / `src_addr` stand in for the payload pointers (only their alignment matters; 0 = NULL);
+ * of the layouts only scalars, the null-ness of pointers and whether two of them are equal are read.  Returns the bytes
+ * written to `buf` (no terminator; 0: nothing to launch), the call's own RUA_E*, or RUA_ERANGE (`cap`). */
+int64_t rua_debug_move_plan(const rua_layout* dst, const rua_layout* src, int32_t tmap, int64_t tmap_arg,
+                            uint64_t dst_addr, uint64_t src_addr, int64_t row_bytes, int64_t pad_row, int32_t flags,
+                            char* buf, int64_t cap);
 int rua_abi_version(void);
 const char* rua_build_target(void);
 

@@ -150,6 +150,8 @@ SYMBOLS = {
     'rua_debug_trace_take': (c_int64, [c_char_p, c_int64]),
     'rua_debug_reduce_plan': (c_int64, [c_int32, POINTER(RuaLayout), POINTER(RuaLayout), c_int64, c_int32, c_int32, c_int32,
                                         c_int64, c_int32, c_int32, c_char_p, c_int64]),
+    'rua_debug_move_plan': (c_int64, [POINTER(RuaLayout), POINTER(RuaLayout), c_int32, c_int64, c_uint64, c_uint64, c_int64,
+                                      c_int64, c_int32, c_char_p, c_int64]),
     'rua_abi_version': (c_int, []),
     'rua_build_target': (c_char_p, []),
 }

@@ -443,7 +443,7 @@ def lay_padded(kind: int, lens: Optional[Tensor], B: int, T_phys: int, T_log: in
     return lay
 
 
-NARROW_ROW_BYTES = 64      # rows up to this get the tile table (rua_move.hip: TILE_MAX_ROW_BYTES)
+NARROW_ROW_BYTES = 64      # rows up to this get the tile table (rua_move_plan.h: TILE_MAX_ROW_BYTES)
 TILE_MIN_LIVE_INV = 4       # ... when at least one cell in this many is a live token
 
 

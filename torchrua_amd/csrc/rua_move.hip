@@ -16,30 +16,16 @@
 #include <stdlib.h>
 #include <string.h>
 #include <atomic>
+#include <type_traits>
 #include "rua_dev.h"
+#include "rua_move_plan.h"      // the thresholds, the launch geometry and WHICH of the kernels below takes a call
 
 namespace rua {
 
-#ifndef RUA_MOVE_BLOCK        // developer knobs for A/B builds (scripts/pack_ab.py)
-#define RUA_MOVE_BLOCK 256
-#endif
-#ifndef RUA_MOVE_UNROLL
+#ifndef RUA_MOVE_UNROLL       // developer knob for A/B builds (scripts/pack_ab.py), like RUA_MOVE_BLOCK
 #define RUA_MOVE_UNROLL 4
 #endif
-constexpr int MOVE_BLOCK = RUA_MOVE_BLOCK;          // threads per workgroup of the generic mover
-constexpr int MOVE_TILE = MOVE_BLOCK;               // one lane per row in phase 1
 constexpr int UNROLL = RUA_MOVE_UNROLL;             // row groups in flight per wave in phase 2
-constexpr int64_t MOVE_TILE_BYTES = 16 << 10;       // destination bytes one workgroup takes (rows: a power of two, 4..256)
-constexpr int64_t MOVE_SPAN_MIN_TILES = 2048;       // launches at least this large give every XCD one contiguous span ...
-constexpr int64_t MOVE_SPAN_MIN_TILES_DENSE = 1 << 19;   // ... when the destination is padded (two thirds of a pad's
-// traffic is stores, and a span per XCD is worth 11-13 % to them at every size measured); a gather into a dense
-// destination (C / P) only draws level from ~8 GB up and LOSES 2-5 % below (cfg2's 0.5 GB: 183 -> 173 us with plain
-// blockIdx order; gpurun_out/r4j/midsize_ab.txt, r4k/span_ab.txt -> profiles/r04_span_ab.txt)
-// The (rank x time) tiles of narrow rows have their own rule (profiles/r04_narrow_span_ab.txt): neighbouring tiles share
-// the 128-byte lines their 512-byte runs straddle, and only a span keeps the two on one XCD's L2.  Pack and the roll
-// tiles gain at every size (16-byte rows: 3.0 -> 4.5 and 3.7 -> 4.4-4.6 TB/s; 32: 3.7 -> 4.9 and 4.5 -> 5.0); P.cat,
-// whose stores are whole 1-KiB runs either way, gains from ~8 GB (4-9 %) and loses 2-8 % at 1-3 GB.
-constexpr int64_t TILE_SPAN_MIN_TILES_FROM_PACK = 1 << 18;
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
@@ -344,7 +330,6 @@ __global__ __launch_bounds__(BLOCK) void move_rows_kernel(rua_layout D, rua_layo
 // loads — the aligned vectors that overlap it, its first and last vector holding a few bytes of its neighbours — and laid
 // down in LDS at its own offset in dword pieces; then the whole span is stored with aligned 16-byte lanes.  Fill rows are
 // laid down as the pattern.  Both sides of HBM see aligned full lanes; what is off-boundary happens inside LDS.
-constexpr int SPAN_TILE_BYTES = 16 << 10;
 template <bool NT>
 __global__ __launch_bounds__(RUA_BLOCK) void move_rows_span_kernel(rua_layout D, rua_layout S, int32_t tmap, int64_t targ,
                                                                    char* __restrict__ dst, const char* __restrict__ src,
@@ -500,7 +485,6 @@ __global__ __launch_bounds__(RUA_BLOCK) void move_rows_narrow_kernel(rua_layout 
 // there), four vectors in flight per lane; runs whose two ends are not a multiple of 4 bytes apart (rows of 1 or 2
 // bytes: bool masks, int16) go through a byte shift in registers (copy_bytes_any).  The launcher takes it when no
 // sequence can be a large share of the launch (one wave walks a whole sequence).
-constexpr int SEQ_PER_WAVE = 8;        // at narrow rows; rows from 256 bytes up (odd widths) give a wave ONE sequence
 // A run of bytes copied by NTHR threads with 16-byte lanes, WHATEVER the two addresses' alignment: the destination is
 // brought to a dword boundary by a few single bytes, then every lane stores an aligned-to-4 dwordx4 assembled from FIVE
 // aligned source dwords shifted by the two addresses' distance mod 4 (v_alignbyte: rows of 1 or 2 bytes, 6, 18 ...),
@@ -661,7 +645,6 @@ __global__ __launch_bounds__(RUA_BLOCK) void seq_copy_kernel(rua_layout D, rua_l
 // wide rows keep the generic kernel.)  Phase 1 needs no search: rank r is live at time t iff r < bsz[t].
 constexpr int TR_MAX = 128;       // a tile is (1 << TRL) ranks x (1 << TTL) time steps, TRL = 4 .. 7, TTL = 4 .. 7 (rua_layout::tile_t_log2)
 constexpr int TT_MAX = 128;
-constexpr int64_t TILE_MAX_ROW_BYTES = 64;       // rows up to this take the tile kernel (pack_tile_lds_kernel)
 
 // [r4] A tile's life is one chain of dependent loads in front of its payload, and eight resident workgroups per CU
 // cannot feed the HBM through it when the chain carries 8 KiB (32-byte rows, 16 x 16 tiles: 4.3 TB/s for the pack, 3.6
@@ -684,8 +667,8 @@ constexpr int64_t TILE_MAX_ROW_BYTES = 64;       // rows up to this take the til
 // [c TT - s, (c + 1) TT - s) — whole lines on the batch-major side, except where a sequence begins and ends.  The
 // PackedSequence side pays: a tile touches TT + R - 1 time steps, and at the R - 1 steps on either edge only some of
 // the sixteen ranks (the cheap kind of misalignment, above).  The host builds the tile table for the shifted windows
-// (chunk c needs the ranks alive at step c TT - (R - 1)) and says so in rua_layout::tile_t_log2 bits 16..23.
-constexpr int TILE_SHIFT_MAX = 8;                // R <= 8: rows of 16 bytes
+// (chunk c needs the ranks alive at step c TT - (R - 1)) and says so in rua_layout::tile_t_log2 bits 16..23
+// (TILE_SHIFT_MAX, rua_move_plan.h: R <= 8, rows of 16 bytes).
 struct TileTables {
   int64_t obase[TR_MAX];  // batch-major storage row of the rank's window start: first row of the sequence - shift + t0
   int64_t olen[TR_MAX];   // the sequence's length (0: no such sequence)
@@ -696,8 +679,6 @@ struct TileTables {
   int64_t pboff[TT_MAX + TILE_SHIFT_MAX];  // first PackedSequence row of time step t0 - (R - 1) + k
   int64_t pbsz[TT_MAX + TILE_SHIFT_MAX];   // sequences alive at that step (0 before 0 and past T)
 };
-constexpr int TILE_FULL_GRID = 1 << 24;   // rua_layout::tile_t_log2 bit 24: tiles cover the whole (sequence x step) grid
-constexpr int TILE_STEP_ROWS = 1 << 25;   // ... bit 25: tiles of ONE time step x (1 << bits 8-15) ranks (pack_roll_steps_kernel)
 
 template <int TTL, int TRL>
 __device__ __forceinline__ void tile_tables(const rua_layout& Pk, const rua_layout& Ot, int64_t tile, TileTables& tb,
@@ -1075,406 +1056,112 @@ __global__ __launch_bounds__(RUA_BLOCK) void pack_roll_steps_kernel(rua_layout P
   }
 }
 
-static int launch_roll_tiles(int vec, hipStream_t s, const rua_layout& Pk, int32_t tmap, int64_t targ, char* dst,
-                             const char* src, int64_t row_bytes, uint4 fp, bool xcd_span) {
-  const int64_t per_xcd = xcd_span ? (Pk.n_tiles + 7) / 8 : 0;
-  const int64_t grid = xcd_span ? per_xcd * 8 : Pk.n_tiles;
-  if (grid > 0x7fffffffLL) return RUA_ERANGE;
-  const int64_t lpr = (row_bytes + vec - 1) / vec;
-  const int ttl = (Pk.tile_t_log2 & 0xff) == 0 ? 4 : (Pk.tile_t_log2 & 0xff);
-  if (ttl < 4 || ttl > 6 || vec != 16) return RUA_EINVAL;
-  const dim3 g((unsigned)grid), b(RUA_BLOCK);
-  switch (ttl) {
-    case 4: hipLaunchKernelGGL((pack_roll_tile_kernel<16, 4>), g, b, 0, s, Pk, tmap, targ, dst, src, row_bytes, lpr, fp, per_xcd); break;
-    case 5: hipLaunchKernelGGL((pack_roll_tile_kernel<16, 5>), g, b, 0, s, Pk, tmap, targ, dst, src, row_bytes, lpr, fp, per_xcd); break;
-    default: hipLaunchKernelGGL((pack_roll_tile_kernel<16, 6>), g, b, 0, s, Pk, tmap, targ, dst, src, row_bytes, lpr, fp, per_xcd); break;
+extern std::atomic<int> g_trace_on;        // the dispatch trace (rua_reduce.hip)
+void trace_add(const char* rec);
+static inline bool tracing() { return g_trace_on.load(std::memory_order_relaxed) != 0; }
+
+// ---- the launcher: a plan (rua_move_plan.h) says WHAT to launch; these helpers turn its run-time values into the
+// kernels' template arguments, one compile-time value per generic lambda — the instantiations that exist, no more.
+template <int V> using int_c = std::integral_constant<int, V>;
+#define RUA_V(x) decltype(x)::value
+template <typename F> static void with_bool(bool v, F&& f) { if (v) f(std::true_type{}); else f(std::false_type{}); }
+template <typename F> static void with_vec(int vec, F&& f) {
+  switch (vec) { case 16: return f(int_c<16>{}); case 8: return f(int_c<8>{}); case 4: return f(int_c<4>{}); case 2: return f(int_c<2>{}); }
+  f(int_c<1>{});
+}
+// rows per tile of move_rows_kernel: 16-byte lanes get every size (FINE); the narrower lanes and the tail form 16 / 64 / 256
+template <bool FINE, typename F> static void with_tile_rows(int rows, F&& f) {
+  if constexpr (FINE)
+    switch (rows) { case 4: return f(int_c<4>{}); case 8: return f(int_c<8>{}); case 32: return f(int_c<32>{}); case 128: return f(int_c<128>{}); }
+  switch (rows) { case 16: return f(int_c<16>{}); case 64: return f(int_c<64>{}); default: return f(int_c<MOVE_TILE>{}); }
+}
+template <typename F> static void with_ttl(int ttl, F&& f) {       // 16 / 32 / 64 time steps per tile
+  switch (ttl) { case 4: return f(int_c<4>{}); case 5: return f(int_c<5>{}); default: return f(int_c<6>{}); }
+}
+// the (VEC, TTL, TRL) of pack_tile_lds_kernel: 16 ranks at any width; 64 x 128 (2-byte rows), 128 x 128 (1) ...
+template <typename F> static void with_lds_tile(int vec, int ttl, int trl, F&& f) {
+  if (trl == 6) return f(int_c<2>{}, int_c<7>{}, int_c<6>{});
+  if (trl == 7) return f(int_c<1>{}, int_c<7>{}, int_c<7>{});
+  with_vec(vec, [&](auto v) { with_ttl(ttl, [&](auto tt) { f(v, tt, int_c<4>{}); }); });
+}
+// ... and the (RB, TTL, TRL) of pack_tile_vec_kernel (tile_shape_narrow, and 16-byte rows into a PackedSequence)
+template <typename F> static void with_vec_tile(int vec, int ttl, F&& f) {
+  if (vec == 16) return f(int_c<16>{}, int_c<6>{}, int_c<4>{});
+  if (vec == 8) return ttl == 7 ? f(int_c<8>{}, int_c<7>{}, int_c<4>{}) : f(int_c<8>{}, int_c<6>{}, int_c<5>{});
+  return ttl == 7 ? f(int_c<4>{}, int_c<7>{}, int_c<5>{}) : f(int_c<4>{}, int_c<6>{}, int_c<6>{});
+}
+
+static int launch_move_rows(const MoveRowsPlan& P, hipStream_t s, const rua_layout& D, const rua_layout& S, int32_t tmap,
+                            int64_t targ, char* dst, const char* src, int64_t row_bytes, const void* fill16, int64_t pad_row) {
+  const uint32_t* f16 = (const uint32_t*)fill16;
+  const uint4 fp = f16 ? make_uint4(f16[0], f16[1], f16[2], f16[3]) : make_uint4(0, 0, 0, 0);
+  const dim3 g(P.grid), b(P.block);
+  const rua_layout &Pk = P.to_pack ? D : S, &Ot = P.to_pack ? S : D;     // the tile kernels: the PackedSequence and its other side
+  switch (P.form) {
+    case MOVE_TILES_LDS:
+      with_bool(P.to_pack, [&](auto tp) { with_lds_tile(P.vec, P.ttl, P.trl, [&](auto v, auto tt, auto tr) {
+        hipLaunchKernelGGL((pack_tile_lds_kernel<RUA_V(v), RUA_V(tp), RUA_V(tt), RUA_V(tr)>), g, b, (size_t)P.lds, s, Pk, Ot,
+                           dst, src, row_bytes, P.lpr, P.per_xcd, P.R, P.phase, fp);
+      }); }); break;
+    case MOVE_TILES_VEC:
+      with_bool(P.to_pack, [&](auto tp) { with_vec_tile(P.vec, P.ttl, [&](auto v, auto tt, auto tr) {
+        hipLaunchKernelGGL((pack_tile_vec_kernel<RUA_V(v), RUA_V(tp), RUA_V(tt), RUA_V(tr)>), g, b, 0, s, Pk, Ot, dst, src, P.per_xcd, fp);
+      }); }); break;
+    case MOVE_ROLL_STEPS:
+      with_bool(P.nt, [&](auto nt) { hipLaunchKernelGGL(pack_roll_steps_kernel<RUA_V(nt)>, g, b, 0, s, D, targ, dst, src, row_bytes, P.trl, P.per_xcd); }); break;
+    case MOVE_SEQ_COPY:
+      with_bool(P.nt, [&](auto nt) { hipLaunchKernelGGL(seq_copy_kernel<RUA_V(nt)>, g, b, 0, s, D, S, tmap, targ, dst, src, row_bytes, fp, P.spw); }); break;
+    case MOVE_NARROW:
+      with_vec(P.vec, [&](auto v) { with_bool(P.scatter, [&](auto sc) { with_bool(P.nt, [&](auto nt) {
+        hipLaunchKernelGGL((move_rows_narrow_kernel<RUA_V(v), RUA_V(sc), RUA_V(nt), NARROW_CH>), g, b, 0, s, D, S, tmap, targ, dst, src, fp, pad_row, P.per_xcd);
+      }); }); }); break;
+    case MOVE_ROLL_TILES:
+      with_ttl(P.ttl, [&](auto tt) { hipLaunchKernelGGL((pack_roll_tile_kernel<16, RUA_V(tt)>), g, b, 0, s, D, tmap, targ, dst, src, row_bytes, P.lpr, fp, P.per_xcd); }); break;
+    case MOVE_SPAN:
+      with_bool(P.nt, [&](auto nt) {
+        hipLaunchKernelGGL(move_rows_span_kernel<RUA_V(nt)>, g, b, 0, s, D, S, tmap, targ, dst, src, (int)row_bytes, P.tile_rows, fp, pad_row, P.per_xcd);
+      }); break;
+    case MOVE_ROWS:
+      with_bool(P.nt, [&](auto nt) {
+        auto go = [&](auto v, auto sc, auto rpt, auto tr, auto t8) {
+          hipLaunchKernelGGL((move_rows_kernel<RUA_V(v), RUA_V(sc), RUA_V(nt), RUA_V(rpt), RUA_V(tr), MOVE_BLOCK, UNROLL, RUA_V(t8)>),
+                             g, b, 0, s, D, S, tmap, targ, dst, src, row_bytes, P.lpr, P.lp_log2, P.cpr, fp, pad_row, P.per_xcd);
+        };
+        if (P.rpt > 1) return go(int_c<16>{}, std::false_type{}, int_c<NARROW_RPT>{}, int_c<MOVE_TILE>{}, std::false_type{});
+        with_bool(P.scatter, [&](auto sc) {
+          if (P.tail8) return with_tile_rows<false>(P.tile_rows, [&](auto tr) { go(int_c<16>{}, sc, int_c<1>{}, tr, std::true_type{}); });
+          with_vec(P.vec, [&](auto v) { with_tile_rows<RUA_V(v) == 16>(P.tile_rows, [&](auto tr) { go(v, sc, int_c<1>{}, tr, std::false_type{}); }); });
+        });
+      }); break;
   }
   return (int)hipGetLastError();
 }
 
-// the tile shapes beyond 16 ranks: rows of ONE vector below 16 bytes (see launch_pack_tiles)
-static inline bool tile_shape_narrow(int vec, int64_t lpr, int ttl, int trl) {
-  return lpr == 1 && ((vec == 8 && trl == 5 && ttl == 6) || (vec == 4 && trl == 6 && ttl == 6) ||
-                      (vec == 8 && trl == 4 && ttl == 7) || (vec == 4 && trl == 5 && ttl == 7) ||   // out of a PackedSequence
-                      (vec == 2 && trl == 6 && ttl == 7) || (vec == 1 && trl == 7 && ttl == 7));
-}
-static inline bool tile_shape_exists(int vec, int64_t row_bytes, int code) {
-  const int ttl = (code & 0xff) == 0 ? 4 : (code & 0xff), trl = ((code >> 8) & 0xff) == 0 ? 4 : ((code >> 8) & 0xff);
-  return (trl == 4 && ttl >= 4 && ttl <= 6) || tile_shape_narrow(vec, (row_bytes + vec - 1) / vec, ttl, trl);
-}
-
-template <bool TO_PACK>
-static int launch_pack_tiles(int vec, hipStream_t s, const rua_layout& Pk, const rua_layout& Ot, char* dst,
-                             const char* src, int64_t row_bytes, bool xcd_span, uint4 fp) {
-  const int64_t per_xcd = xcd_span ? (Pk.n_tiles + 7) / 8 : 0;
-  const int64_t grid = xcd_span ? per_xcd * 8 : Pk.n_tiles;
-  if (grid > 0x7fffffffLL) return RUA_ERANGE;
-  const int64_t lpr = (row_bytes + vec - 1) / vec;
-  const dim3 g((unsigned)grid), b(RUA_BLOCK);
-  const int ttl = (Pk.tile_t_log2 & 0xff) == 0 ? 4 : (Pk.tile_t_log2 & 0xff);      // (0: a caller of ABI <= 3, 16 x 16 tiles)
-  const int trl = ((Pk.tile_t_log2 >> 8) & 0xff) == 0 ? 4 : ((Pk.tile_t_log2 >> 8) & 0xff);
-  // tile shapes that exist: 16 ranks x 16 / 32 / 64 steps for any vector width, and — [r5] rows of ONE vector below 16
-  // bytes — 32 x 64 (8-byte rows), 64 x 64 (4), 64 x 128 (2), 128 x 128 (1): 16 KiB of payload per tile at every width,
-  // runs of 128 .. 512 bytes on both sides
-  const bool shape16 = trl == 4 && ttl >= 4 && ttl <= 6;
-  const bool shape_narrow = tile_shape_narrow(vec, lpr, ttl, trl);
-  if (!shape16 && !shape_narrow) return RUA_EINVAL;
-  const bool full_grid = (Pk.tile_t_log2 & TILE_FULL_GRID) != 0;
-  if (full_grid && (TO_PACK || (Ot.kind != RUA_LEFT && Ot.kind != RUA_RIGHT))) return RUA_EINVAL;
-  // the batch-major side's runs start on 128-byte lines (TileTables): R rows per line, if the host built the table for
-  // it, the rows divide a line and the payload's own address does not spoil it (its offset inside a line, in rows)
-  int R = (int)((Pk.tile_t_log2 >> 16) & 0xff);
-  const uintptr_t major = TO_PACK ? (uintptr_t)src : (uintptr_t)dst;
-  int64_t phase = 0;
-  // ... and only where the batch-major side is the one WRITTEN (P.cat): what costs is a partial-line STORE — the shifted
-  // windows trade whole lines on the batch-major side for fragments on the PackedSequence's, so they gain 2-20 % for
-  // P.cat and LOSE 6-15 % for the pack, whose packed-side fragments would then be the stores (same-box A/B of both
-  // directions at 16 / 32 / 64-byte rows: profiles/r04_tile_shift_ab.txt)
-  if (TO_PACK || full_grid || R < 2 || R > TILE_SHIFT_MAX || (R & (R - 1)) != 0 || R * row_bytes != 128 || (major & 127) % (uintptr_t)row_bytes != 0) R = 1;
-  else phase = (int64_t)((major & 127) / (uintptr_t)row_bytes);
-#ifdef RUA_TILE_NO_SHIFT          // developer A/B build
-  R = 1; phase = 0;
-#endif
-  const size_t lds = (size_t)((((int64_t)1 << (ttl + trl)) + ((int64_t)1 << trl)) * lpr) * vec;   // the staged tile + one padding row per rank
-  if (lds > (48u << 10)) return RUA_EINVAL;                            // (the host picks the tile by row width: 32 KiB staged at most)
-#define RUA_LAUNCH_T(VEC, TTLV, TRLV) \
-  hipLaunchKernelGGL((pack_tile_lds_kernel<VEC, TO_PACK, TTLV, TRLV>), g, b, lds, s, Pk, Ot, dst, src, row_bytes, lpr, per_xcd, R, phase, fp)
-#define RUA_LAUNCH(VEC)                                                             \
-  switch (ttl) {             /* (32 ranks per tile were measured too at >= 16-byte rows: slower, not instantiated) */ \
-    case 4: RUA_LAUNCH_T(VEC, 4, 4); break;                                         \
-    case 5: RUA_LAUNCH_T(VEC, 5, 4); break;                                         \
-    default: RUA_LAUNCH_T(VEC, 6, 4); break;                                        \
+// ONE record per plan: the kernel family, its template arguments as launch_move_rows instantiates them, the geometry
+// and the run-time arguments that are the plan's.  The trace and rua_debug_move_plan both print through it.
+static void format_move_plan(const MoveRowsPlan& P, char* rec, size_t cap) {
+  const long long px = P.per_xcd, lpr = P.lpr;
+  rec[0] = 0;
+  switch (P.form) {
+    case MOVE_TILES_LDS:
+      snprintf(rec, cap, "pack_tile_lds_kernel VEC=%d TO_PACK=%d TTL=%d TRL=%d grid=%u per_xcd=%lld lds=%d lpr=%lld R=%d phase=%lld",
+               P.vec, (int)P.to_pack, P.ttl, P.trl, P.grid, px, P.lds, lpr, P.R, (long long)P.phase); break;
+    case MOVE_TILES_VEC:
+      snprintf(rec, cap, "pack_tile_vec_kernel RB=%d TO_PACK=%d TTL=%d TRL=%d grid=%u per_xcd=%lld", P.vec, (int)P.to_pack, P.ttl, P.trl, P.grid, px); break;
+    case MOVE_ROLL_STEPS: snprintf(rec, cap, "pack_roll_steps_kernel NT=%d grid=%u per_xcd=%lld trl=%d", (int)P.nt, P.grid, px, P.trl); break;
+    case MOVE_SEQ_COPY: snprintf(rec, cap, "seq_copy_kernel NT=%d grid=%u spw=%d", (int)P.nt, P.grid, P.spw); break;
+    case MOVE_NARROW:
+      snprintf(rec, cap, "move_rows_narrow_kernel VEC=%d SCATTER=%d NT=%d CH=%d grid=%u per_xcd=%lld", P.vec, (int)P.scatter, (int)P.nt, NARROW_CH, P.grid, px); break;
+    case MOVE_ROLL_TILES: snprintf(rec, cap, "pack_roll_tile_kernel VEC=16 TTL=%d grid=%u per_xcd=%lld lpr=%lld", P.ttl, P.grid, px, lpr); break;
+    case MOVE_SPAN: snprintf(rec, cap, "move_rows_span_kernel NT=%d grid=%u per_xcd=%lld tile_rows=%d", (int)P.nt, P.grid, px, P.tile_rows); break;
+    case MOVE_ROWS:
+      snprintf(rec, cap, "move_rows_kernel VEC=%d SCATTER=%d NT=%d RPT=%d TROWS=%d TAIL8=%d grid=%u per_xcd=%lld lpr=%lld lp_log2=%d cpr=%d",
+               P.vec, (int)P.scatter, (int)P.nt, P.rpt, P.tile_rows, (int)P.tail8, P.grid, px, lpr, P.lp_log2, P.cpr); break;
   }
-  // 16-byte rows INTO a PackedSequence take the lane-group kernel too (one cell per lane, relative liveness tables: +4 %
-  // over the staged kernel, r5r); out of one the staged kernel's line-aligned windows are worth more (-5 % without them)
-  if (TO_PACK && vec == 16 && lpr == 1 && trl == 4 && ttl == 6 && !full_grid) {
-    hipLaunchKernelGGL((pack_tile_vec_kernel<16, TO_PACK, 6, 4>), g, b, 0, s, Pk, Ot, dst, src, per_xcd, fp);
-    return (int)hipGetLastError();
-  }
-  if (shape_narrow) {
-    switch (vec) {
-      // (the taller tiles — 16 x 128 at 8 bytes, 32 x 128 at 4 — are what the host asks for OUT of a PackedSequence: the
-      // batch-major side is then the one written, and its runs are 1 KiB / 512 B instead of 512 / 256)
-      case 8: if (ttl == 7) hipLaunchKernelGGL((pack_tile_vec_kernel<8, TO_PACK, 7, 4>), g, b, 0, s, Pk, Ot, dst, src, per_xcd, fp);
-              else hipLaunchKernelGGL((pack_tile_vec_kernel<8, TO_PACK, 6, 5>), g, b, 0, s, Pk, Ot, dst, src, per_xcd, fp);
-              break;
-      case 4: if (ttl == 7) hipLaunchKernelGGL((pack_tile_vec_kernel<4, TO_PACK, 7, 5>), g, b, 0, s, Pk, Ot, dst, src, per_xcd, fp);
-              else hipLaunchKernelGGL((pack_tile_vec_kernel<4, TO_PACK, 6, 6>), g, b, 0, s, Pk, Ot, dst, src, per_xcd, fp);
-              break;
-      case 2: RUA_LAUNCH_T(2, 7, 6); break;
-      default: RUA_LAUNCH_T(1, 7, 7); break;
-    }
-    return (int)hipGetLastError();
-  }
-  switch (vec) {
-    case 16: RUA_LAUNCH(16); break;
-    case 8:  RUA_LAUNCH(8); break;
-    case 4:  RUA_LAUNCH(4); break;
-    case 2:  RUA_LAUNCH(2); break;
-    default: RUA_LAUNCH(1); break;
-  }
-#undef RUA_LAUNCH
-#undef RUA_LAUNCH_T
-  return (int)hipGetLastError();
-}
-
-static int check_layout(const rua_layout* L, bool is_dst) {
-  if (!L) return RUA_EINVAL;
-  if (L->B < 0 || L->n_rows < 0) return RUA_EINVAL;
-  switch (L->kind) {
-    case RUA_CAT:
-      if (L->lens && !L->off) return RUA_EINVAL;
-      return 0;
-    case RUA_LEFT:
-    case RUA_RIGHT:
-      return L->T_phys >= 0 ? 0 : RUA_EINVAL;
-    case RUA_PACK:
-      if (L->T > 0 && !L->boff) return RUA_EINVAL;
-      return 0;
-    case RUA_LIST:
-      if (!is_dst) return RUA_EINVAL;
-      if (L->n_rows > 0 && !L->tptr) return RUA_EINVAL;
-      return 0;
-  }
-  return RUA_EINVAL;
-}
-
-constexpr int NARROW_RPT = 4;
-constexpr int NARROW_CH = 8;         // rows in flight per lane of move_rows_narrow_kernel
-
-template <bool SCATTER, bool NT>
-static int launch_narrow(int vec, int64_t n_rows, hipStream_t s, const rua_layout& D, const rua_layout& S, int32_t tmap,
-                         int64_t targ, char* dst, const char* src, uint4 fp, int64_t pad_row, bool xcd_span) {
-  const int64_t per_tile = (int64_t)RUA_BLOCK * NARROW_CH;
-  const int64_t ntiles = (n_rows + per_tile - 1) / per_tile;
-  const int64_t per_xcd = xcd_span ? (ntiles + 7) / 8 : 0;
-  const int64_t grid = xcd_span ? per_xcd * 8 : ntiles;
-  if (grid > 0x7fffffffLL) return RUA_ERANGE;
-  const dim3 g((unsigned)grid), b(RUA_BLOCK);
-#define RUA_LAUNCH_N(VEC) \
-  hipLaunchKernelGGL((move_rows_narrow_kernel<VEC, SCATTER, NT, NARROW_CH>), g, b, 0, s, D, S, tmap, targ, dst, src, fp, pad_row, per_xcd)
-  switch (vec) {
-    case 16: RUA_LAUNCH_N(16); break;
-    case 8:  RUA_LAUNCH_N(8); break;
-    case 4:  RUA_LAUNCH_N(4); break;
-    case 2:  RUA_LAUNCH_N(2); break;
-    default: RUA_LAUNCH_N(1); break;
-  }
-#undef RUA_LAUNCH_N
-  return (int)hipGetLastError();
-}
-
-template <bool SCATTER, bool NT>
-static int launch_move(int vec, int64_t n_rows, hipStream_t s, const rua_layout& D, const rua_layout& S, int32_t tmap,
-                       int64_t targ, char* dst, const char* src, int64_t row_bytes, uint4 fp, int64_t pad_row,
-                       bool narrow_same_pack, int tile_rows, bool xcd_span, bool tail8 = false) {
-  if (tail8) vec = 16;
-  const int64_t lpr = (row_bytes + vec - 1) / vec;
-  int lp_log2 = 0;
-  while ((1 << lp_log2) < lpr && lp_log2 < 6) ++lp_log2;
-  const int cpr = (int)((lpr + RUA_WAVE - 1) / RUA_WAVE);
-  const dim3 b(MOVE_BLOCK);
-  if (narrow_same_pack) {   // vec == 16, gather: see move_rows_kernel<..., RPT>
-    const int64_t nt4 = (n_rows + MOVE_TILE * NARROW_RPT - 1) / (MOVE_TILE * NARROW_RPT);
-    hipLaunchKernelGGL((move_rows_kernel<16, false, NT, NARROW_RPT>), dim3((unsigned)nt4), b, 0, s, D, S, tmap, targ, dst,
-                       src, row_bytes, lpr, lp_log2, cpr, fp, pad_row, (int64_t)0);
-    return (int)hipGetLastError();
-  }
-  const int64_t ntiles = (n_rows + tile_rows - 1) / tile_rows;
-  const int64_t per_xcd = xcd_span ? (ntiles + 7) / 8 : 0;
-  const int64_t grid = xcd_span ? per_xcd * 8 : ntiles;
-  if (grid > 0x7fffffffLL) return RUA_ERANGE;
-  const dim3 g((unsigned)grid);
-#define RUA_LAUNCH_T(VEC, TR) \
-  hipLaunchKernelGGL((move_rows_kernel<VEC, SCATTER, NT, 1, TR>), g, b, 0, s, D, S, tmap, targ, dst, src, row_bytes, lpr, lp_log2, cpr, fp, pad_row, per_xcd)
-  // 16-byte rows get every tile size; the narrower vector widths (odd row sizes) a coarser choice
-#define RUA_LAUNCH16()                         \
-  switch (tile_rows) {                         \
-    case 4: RUA_LAUNCH_T(16, 4); break;        \
-    case 8: RUA_LAUNCH_T(16, 8); break;        \
-    case 16: RUA_LAUNCH_T(16, 16); break;      \
-    case 32: RUA_LAUNCH_T(16, 32); break;      \
-    case 64: RUA_LAUNCH_T(16, 64); break;      \
-    case 128: RUA_LAUNCH_T(16, 128); break;    \
-    default: RUA_LAUNCH_T(16, MOVE_TILE); break; \
-  }
-#define RUA_LAUNCH(VEC)                        \
-  switch (tile_rows) {                         \
-    case 16: RUA_LAUNCH_T(VEC, 16); break;     \
-    case 64: RUA_LAUNCH_T(VEC, 64); break;     \
-    default: RUA_LAUNCH_T(VEC, MOVE_TILE); break; \
-  }
-#define RUA_LAUNCH_TAIL(TR) \
-  hipLaunchKernelGGL((move_rows_kernel<16, SCATTER, NT, 1, TR, MOVE_BLOCK, UNROLL, true>), g, b, 0, s, D, S, tmap, targ, dst, src, row_bytes, lpr, lp_log2, cpr, fp, pad_row, per_xcd)
-  if (tail8) {
-    switch (tile_rows) {
-      case 16: RUA_LAUNCH_TAIL(16); break;
-      case 64: RUA_LAUNCH_TAIL(64); break;
-      default: RUA_LAUNCH_TAIL(MOVE_TILE); break;
-    }
-    return (int)hipGetLastError();
-  }
-#undef RUA_LAUNCH_TAIL
-  switch (vec) {
-    case 16: RUA_LAUNCH16(); break;
-    case 8:  RUA_LAUNCH(8); break;
-    case 4:  RUA_LAUNCH(4); break;
-    case 2:  RUA_LAUNCH(2); break;
-    default: RUA_LAUNCH(1); break;
-  }
-#undef RUA_LAUNCH
-#undef RUA_LAUNCH16
-#undef RUA_LAUNCH_T
-  return (int)hipGetLastError();
-}
-
-}  // namespace rua
-
-using namespace rua;
-
-extern "C" int rua_move_rows(const rua_layout* dst, const rua_layout* src, int32_t tmap, int64_t tmap_arg,
-                             void* dst_data, const void* src_data, int64_t row_bytes, const void* fill16,
-                             int64_t pad_row, int32_t flags, void* stream) {
-  int e;
-  if ((e = check_layout(dst, true)) != 0) return e;
-  if ((e = check_layout(src, false)) != 0) return e;
-  if (tmap < RUA_T_SHIFT || tmap > RUA_T_ZERO || row_bytes < 0) return RUA_EINVAL;
-  if (dst->n_rows == 0 || row_bytes == 0) return 0;
-  if (!dst_data || !src_data) return RUA_EINVAL;
-  if (pad_row < -1 || pad_row >= src->n_rows) return RUA_EINVAL;
-
-  // widest power-of-two access that divides the row size and both base addresses
-  const uint64_t mix = (uint64_t)row_bytes | (uint64_t)(uintptr_t)dst_data | (uint64_t)(uintptr_t)src_data | 16u;
-  const int vec = (int)(mix & (~mix + 1));
-
-  uint4 fp = make_uint4(0, 0, 0, 0);
-  if (fill16) {
-    const uint32_t* f = (const uint32_t*)fill16;
-    fp = make_uint4(f[0], f[1], f[2], f[3]);
-  }
-  hipStream_t s = (hipStream_t)stream;
-  // narrow rows between a PackedSequence and a batch-major layout: (rank x time) tiles
-  const int span_flags = RUA_MOVE_XCD_SPAN_ON | RUA_MOVE_XCD_SPAN_OFF | RUA_MOVE_NO_TAIL8 | RUA_MOVE_NO_NARROW;
-  if ((flags & ~span_flags) == 0 && tmap == RUA_T_SHIFT && tmap_arg == 0 && row_bytes <= TILE_MAX_ROW_BYTES) {
-    const bool to_pack = dst->kind == RUA_PACK && (src->kind == RUA_CAT || src->kind == RUA_LEFT || src->kind == RUA_RIGHT);
-    // [r5] a padded destination takes the tiles too when the caller asks for the FULL (sequence x step) grid
-    // (rua_layout::tile_t_log2 bit 24): every slot is then written, tokens and fill, in the one pass
-    const bool full_grid = src->kind == RUA_PACK && (src->tile_t_log2 & TILE_FULL_GRID) != 0;
-    const bool from_pack = src->kind == RUA_PACK && (dst->kind == RUA_CAT || (full_grid && pad_row < 0 &&
-                                                     (dst->kind == RUA_LEFT || dst->kind == RUA_RIGHT)));
-    const rua_layout* pk = to_pack ? dst : src;
-    // (a table built for a tile shape this vector width has no kernel for — rows of 8 bytes at a base that is only
-    // 4-byte aligned, say — is simply not used)
-    if ((to_pack || from_pack) && (pk->tile_start || full_grid) && pk->bsz && pk->n_tiles > 0 && pk->boff &&
-        (!full_grid || (!to_pack && dst->kind != RUA_CAT)) && !(pk->tile_t_log2 & TILE_STEP_ROWS) &&
-        tile_shape_exists(vec, row_bytes, pk->tile_t_log2)) {
-      bool span = pk->n_tiles >= (to_pack || full_grid ? MOVE_SPAN_MIN_TILES : TILE_SPAN_MIN_TILES_FROM_PACK);
-      if (flags & RUA_MOVE_XCD_SPAN_ON) span = true;
-      if (flags & RUA_MOVE_XCD_SPAN_OFF) span = false;
-      return to_pack ? launch_pack_tiles<true>(vec, s, *dst, *src, (char*)dst_data, (const char*)src_data, row_bytes, span, fp)
-                     : launch_pack_tiles<false>(vec, s, *src, *dst, (char*)dst_data, (const char*)src_data, row_bytes, span, fp);
-    }
-  }
-  const bool big = (double)dst->n_rows * (double)row_bytes >= (double)(512ll << 20);
-  const bool nt = (flags & RUA_MOVE_NT_ON) ? true : (flags & RUA_MOVE_NT_OFF) ? false : big;
-  char* d = (char*)dst_data;
-  const char* c = (const char*)src_data;
-  // Launch geometry (profiles/r02_copy_probe.txt, r02_mover_geometry.txt): HBM rewards a launch whose
-  // in-flight addresses form a small window sweeping the destination in order, so a workgroup takes only ~16 KiB
-  // of destination rows (workgroups are dispatched in blockIdx order), and on big launches every XCD sweeps ONE
-  // contiguous span of the destination instead of every eighth tile.  At the north-star shape (1 KiB rows):
-  // 256-row tiles 5.6 TB/s -> 16-row tiles 6.15 TB/s for C->P, 5.3 -> 6.1 for P->C.
-  int tile_rows = MOVE_TILE;
-  for (int64_t tb = MOVE_TILE * row_bytes; tile_rows > 4 && tb > MOVE_TILE_BYTES; tb >>= 1) tile_rows >>= 1;
-  const int tsel = (flags >> 4) & 0xf;               // developer override: RUA_MOVE_TILE_LOG2 / RUA_MOVE_XCD_SPAN_*
-  if (tsel >= 2 && tsel <= 8) tile_rows = 1 << tsel;
-  if (tile_rows > MOVE_BLOCK) tile_rows = MOVE_BLOCK;
-  // rows that are a multiple of 8 but not of 16 bytes: 16-byte lanes at 8-byte-aligned addresses + an 8-byte tail
-  // (RUA_MOVE_NO_TAIL8, a developer flag, keeps the 8-byte lanes for A/B runs)
-  // Only rows that really END in an 8-byte piece: vec == 8 also comes from a base pointer that is only 8-byte aligned
-  // under rows of a multiple of 16 bytes (a view at a storage offset), and those have no tail — they keep 8-byte lanes.
-  const bool tail8 = vec == 8 && (row_bytes & 15) == 8 && row_bytes >= 24 && !(flags & RUA_MOVE_NO_TAIL8);
-  if (vec != 16) tile_rows = tile_rows <= 16 ? 16 : tile_rows <= 64 ? 64 : MOVE_TILE;
-  const int64_t nr = dst->n_rows;
-  const bool padded_dst = dst->kind == RUA_LEFT || dst->kind == RUA_RIGHT;
-  bool xcd_span = (nr + tile_rows - 1) / tile_rows >= (padded_dst ? MOVE_SPAN_MIN_TILES : MOVE_SPAN_MIN_TILES_DENSE);
-  if (flags & RUA_MOVE_XCD_SPAN_ON) xcd_span = true;
-  if (flags & RUA_MOVE_XCD_SPAN_OFF) xcd_span = false;
-  // [r5] a roll inside one PackedSequence, time step by time step, when the caller handed over the table of one-step tiles
-  if (dst->kind == RUA_PACK && src->kind == RUA_PACK && (dst->tile_t_log2 & TILE_STEP_ROWS) && dst->tile_start && dst->bsz &&
-      dst->boff && dst->boff == src->boff && dst->sorted == src->sorted && dst->len_add == 0 && src->len_add == 0 &&
-      dst->T == src->T && dst->T > 0 && dst->n_tchunks == dst->T && dst->n_tiles > 0 && tmap == RUA_T_ROLL && pad_row < 0 &&
-      (flags & ~(RUA_MOVE_XCD_SPAN_ON | RUA_MOVE_XCD_SPAN_OFF)) == 0) {
-    bool span = dst->n_tiles >= MOVE_SPAN_MIN_TILES_DENSE;
-    if (flags & RUA_MOVE_XCD_SPAN_ON) span = true;
-    if (flags & RUA_MOVE_XCD_SPAN_OFF) span = false;
-    const int64_t per_xcd = span ? (dst->n_tiles + 7) / 8 : 0;
-    const int64_t grid = span ? per_xcd * 8 : dst->n_tiles;
-    if (grid > 0x7fffffffLL) return RUA_ERANGE;
-    const int trl = (dst->tile_t_log2 >> 8) & 0xff;
-    if (nt) hipLaunchKernelGGL(pack_roll_steps_kernel<true>, dim3((unsigned)grid), dim3(RUA_BLOCK), 0, s, *dst, tmap_arg, d, c, row_bytes, trl, per_xcd);
-    else hipLaunchKernelGGL(pack_roll_steps_kernel<false>, dim3((unsigned)grid), dim3(RUA_BLOCK), 0, s, *dst, tmap_arg, d, c, row_bytes, trl, per_xcd);
-    return (int)hipGetLastError();
-  }
-  // [r5] narrow rows between two batch-major layouts: the segmented memcpy (seq_copy_kernel)
-  {
-    const bool major_d = dst->kind == RUA_CAT || dst->kind == RUA_LEFT || dst->kind == RUA_RIGHT;
-    const bool major_s = src->kind == RUA_CAT || src->kind == RUA_LEFT || src->kind == RUA_RIGHT;
-    const bool same_lens = dst->lens == src->lens && dst->len_add == src->len_add;
-    // the longest sequence either side can hold: the storage's own T for the padded layouts, the caller's hint for a
-    // CattedSequence (rua_layout::T_log, 0 = unknown).  One wave walks a sequence whole: none may be a large share
-    const int64_t long_d = dst->kind == RUA_CAT ? dst->T_log : dst->T_phys;
-    const int64_t long_s = src->kind == RUA_CAT ? src->T_log : src->T_phys;
-    const int64_t longest = long_d > long_s ? long_d : long_s;
-    const bool balanced = long_d > 0 && long_s > 0 && dst->B >= 4096 && longest <= nr / 1024;
-    // (rows wider than 64 bytes that are not a multiple of 16 were tried here too: one wave per sequence streams at the
-    // walk's 4.5 - 5.4 TB/s whatever the alignment, below what tiles in destination order give: move_rows_span_kernel)
-    if (major_d && major_s && !(flags & (RUA_MOVE_SCATTER | RUA_MOVE_NO_NARROW)) && tsel == 0 && pad_row < 0 &&
-        row_bytes <= 64 && dst->B == src->B && (tmap == RUA_T_SHIFT || (tmap == RUA_T_ROLL && same_lens)) && balanced &&
-        (dst->kind != RUA_CAT || dst->off || !dst->lens) && (src->kind != RUA_CAT || src->off || !src->lens)) {
-      // sequences per wave: about 16 KiB of tokens (8 at narrow rows, 1 from a few hundred bytes per row up)
-      const int64_t seq_bytes = nr / (dst->B > 0 ? dst->B : 1) * row_bytes;
-      const int spw = seq_bytes >= 8192 ? 1 : seq_bytes >= 4096 ? 2 : seq_bytes >= 2048 ? 4 : SEQ_PER_WAVE;
-      const int64_t waves = (dst->B + spw - 1) / spw;
-      const int64_t grid = (waves + RUA_WAVES_PER_BLOCK - 1) / RUA_WAVES_PER_BLOCK;
-      if (grid > 0x7fffffffLL) return RUA_ERANGE;
-      if (nt) hipLaunchKernelGGL(seq_copy_kernel<true>, dim3((unsigned)grid), dim3(RUA_BLOCK), 0, s, *dst, *src, tmap, tmap_arg, d, c, row_bytes, fp, spw);
-      else hipLaunchKernelGGL(seq_copy_kernel<false>, dim3((unsigned)grid), dim3(RUA_BLOCK), 0, s, *dst, *src, tmap, tmap_arg, d, c, row_bytes, fp, spw);
-      return (int)hipGetLastError();
-    }
-  }
-  // [r5] rows of one vector (1-D payloads: 1 .. 16 bytes): a lane per row from resolution to store, eight rows in flight
-  // per lane (move_rows_narrow_kernel).  The roll tiles below keep 16-byte rows inside one PackedSequence.
-  const bool one_vec = row_bytes == vec && !(flags & RUA_MOVE_NO_NARROW) && tsel == 0;
-  if (one_vec) {
-    const int64_t per_tile = (int64_t)RUA_BLOCK * NARROW_CH;
-    bool span = (nr + per_tile - 1) / per_tile >= (padded_dst ? MOVE_SPAN_MIN_TILES : MOVE_SPAN_MIN_TILES_DENSE);
-    if (flags & RUA_MOVE_XCD_SPAN_ON) span = true;
-    if (flags & RUA_MOVE_XCD_SPAN_OFF) span = false;
-    const bool roll_tiles = vec == 16 && dst->kind == RUA_PACK && src->kind == RUA_PACK && dst->tile_start && dst->bsz &&
-                            !(dst->tile_t_log2 & TILE_STEP_ROWS) &&
-                            dst->boff == src->boff && !(flags & RUA_MOVE_SCATTER);
-    if (!roll_tiles) {
-      if (flags & RUA_MOVE_SCATTER)
-        return nt ? launch_narrow<true, true>(vec, nr, s, *dst, *src, tmap, tmap_arg, d, c, fp, pad_row, span)
-                  : launch_narrow<true, false>(vec, nr, s, *dst, *src, tmap, tmap_arg, d, c, fp, pad_row, span);
-      return nt ? launch_narrow<false, true>(vec, nr, s, *dst, *src, tmap, tmap_arg, d, c, fp, pad_row, span)
-                : launch_narrow<false, false>(vec, nr, s, *dst, *src, tmap, tmap_arg, d, c, fp, pad_row, span);
-    }
-  }
-  if (flags & RUA_MOVE_SCATTER)
-    return nt ? launch_move<true, true>(vec, nr, s, *dst, *src, tmap, tmap_arg, d, c, row_bytes, fp, pad_row, false, tile_rows, xcd_span, tail8)
-              : launch_move<true, false>(vec, nr, s, *dst, *src, tmap, tmap_arg, d, c, row_bytes, fp, pad_row, false, tile_rows, xcd_span, tail8);
-  // roll / rev inside ONE PackedSequence with rows of at most 32 B (3.1 -> 3.9 TB/s; no gain at 64 B): RPT rows per lane (the kernel's `same_pack` test)
-  const bool narrow_same_pack = vec == 16 && row_bytes <= 32 && dst->kind == RUA_PACK && src->kind == RUA_PACK &&
-                                dst->bsz && dst->boff && dst->boff == src->boff && dst->sorted == src->sorted &&
-                                dst->len_add == 0 && src->len_add == 0 && dst->T == src->T && dst->T > 0;
-  // ... and on the (rank x time) tiles when the caller handed the tile table over (pack_roll_tile_kernel)
-  if (narrow_same_pack && dst->tile_start && !(dst->tile_t_log2 & TILE_STEP_ROWS) && dst->n_tiles > 0 && dst->lens && dst->sorted &&
-      pad_row < 0 && (flags & ~(RUA_MOVE_XCD_SPAN_ON | RUA_MOVE_XCD_SPAN_OFF)) == 0 &&
-      (tmap == RUA_T_ROLL || tmap == RUA_T_REV_S || tmap == RUA_T_REV_D || tmap == RUA_T_SHIFT)) {
-    bool span = dst->n_tiles >= MOVE_SPAN_MIN_TILES;
-    if (flags & RUA_MOVE_XCD_SPAN_ON) span = true;
-    if (flags & RUA_MOVE_XCD_SPAN_OFF) span = false;
-    return launch_roll_tiles(vec, s, *dst, tmap, tmap_arg, d, c, row_bytes, fp, span);
-  }
-  // [r5] a gather of rows that are a multiple of 4 but not of 16 bytes: the destination tile goes through LDS and leaves as
-  // one aligned span (move_rows_span_kernel)
-  // ([r5, late] and of rows that ARE a multiple of 16 bytes but not of a 128-byte line — 2 000-byte rows, H = 1 000 in
-  // bf16: the row mover's 16-byte lanes are aligned there, but every wave instruction straddles one line more than it
-  // fills and every row boundary is two partial lines; as a span the tile is stored in whole lines)
-  const bool off16 = (row_bytes & 15) != 0 && (row_bytes & 3) == 0;
-  // (from 1 KiB up: at 640 / 656-byte rows the row mover is level or ahead — 5.41 / 5.40 against 5.36 / 5.00 TB/s for the
-  // pack, profiles/r05_span16_ab.txt)
-  const bool off128 = (row_bytes & 15) == 0 && (row_bytes & 127) != 0 && row_bytes > 1024;
-  if ((off16 || off128) && row_bytes >= 64 && row_bytes <= SPAN_TILE_BYTES / 2 &&
-      ((uintptr_t)dst_data & 15) == 0 && ((uintptr_t)src_data & 15) == 0 && tsel == 0 && !(flags & RUA_MOVE_NO_TAIL8)) {
-    // rows per tile: a multiple of 2 (rows of 8 mod 16 bytes) or 4 (4 / 12 mod 16), so that every tile starts on a
-    // 16-byte boundary (any number of rows of whole vectors: only the two ends of a tile are partial lines then); as many
-    // as fit 16 KiB of LDS (16 rows of 1 000 bytes, 8 of 2 000), one resolving lane each
-    int step = (row_bytes & 7) ? 4 : 2;
-    if (off128) step = 1;
-    int trows = (int)(SPAN_TILE_BYTES / row_bytes) / step * step;
-    if (trows > RUA_BLOCK) trows = RUA_BLOCK / step * step;
-    if (trows > 0) {        // (a line-aligned tile of some widths would not fit the 16 KiB: the row mover takes those)
-      const int64_t ntiles = (nr + trows - 1) / trows;
-      bool span = ntiles >= (padded_dst ? MOVE_SPAN_MIN_TILES : MOVE_SPAN_MIN_TILES_DENSE);
-      if (flags & RUA_MOVE_XCD_SPAN_ON) span = true;
-      if (flags & RUA_MOVE_XCD_SPAN_OFF) span = false;
-      const int64_t per_xcd = span ? (ntiles + 7) / 8 : 0;
-      const int64_t grid = span ? per_xcd * 8 : ntiles;
-      if (grid > 0x7fffffffLL) return RUA_ERANGE;
-      if (nt) hipLaunchKernelGGL(move_rows_span_kernel<true>, dim3((unsigned)grid), dim3(RUA_BLOCK), 0, s, *dst, *src, tmap, tmap_arg, d, c, (int)row_bytes, trows, fp, pad_row, per_xcd);
-      else hipLaunchKernelGGL(move_rows_span_kernel<false>, dim3((unsigned)grid), dim3(RUA_BLOCK), 0, s, *dst, *src, tmap, tmap_arg, d, c, (int)row_bytes, trows, fp, pad_row, per_xcd);
-      return (int)hipGetLastError();
-    }
-  }
-  return nt ? launch_move<false, true>(vec, nr, s, *dst, *src, tmap, tmap_arg, d, c, row_bytes, fp, pad_row, narrow_same_pack, tile_rows, xcd_span, tail8)
-            : launch_move<false, false>(vec, nr, s, *dst, *src, tmap, tmap_arg, d, c, row_bytes, fp, pad_row, narrow_same_pack, tile_rows, xcd_span, tail8);
 }
 
 // ---------------------------------------------------------------------------------------------
-// Backward of a row scatter  rows_of(src)[list] = value  (rua_setitem_backward, include/rua.h): gather-and-zero.
+// Backward of a row scatter rows_of(src)[list] = value  (rua_setitem_backward, include/rua.h): gather-and-zero.
 // A wave takes 64 consecutive list entries; each lane resolves ONE of them into a storage row of `src` with the mover's own
 // resolve_wave_rows<true> (a LIST layout takes none of its cooperative searches: every lane reads its own pair and maps it —
 // exactly the rows the scatter wrote, -1 for an entry that names no token); then the wave walks the 64 rows, UNR row groups in
@@ -1482,11 +1169,6 @@ extern "C" int rua_move_rows(const rua_layout* dst, const rua_layout* src, int32
 //   grad_value[j] = grad[r] (zeros when r < 0)      and      grad_raw[r] = 0.
 // `grad` is only read and `grad_raw` only written, so repeated rows are race-free (two lanes may store the same zeros)
 // and the result does not depend on the order of the waves.  The stores to grad_value are contiguous per wave (64 rows).
-namespace rua {
-
-extern std::atomic<int> g_trace_on;        // the dispatch trace (rua_reduce.hip)
-void trace_add(const char* rec);
-
 constexpr int SETITEM_BWD_UNROLL = 4;
 
 template <int VEC, bool NT, bool TAIL8>
@@ -1567,46 +1249,31 @@ __global__ __launch_bounds__(RUA_BLOCK) void setitem_backward_kernel(rua_layout 
   }
 }
 
-template <bool NT>
-static int launch_setitem_backward(int vec, bool tail8, hipStream_t s, const rua_layout& D, const rua_layout& S,
+static int launch_setitem_backward(const SetitemBackwardPlan& P, hipStream_t s, const rua_layout& D, const rua_layout& S,
                                    const char* grad, char* gval, char* graw, int64_t row_bytes) {
-  if (tail8) vec = 16;
-  const int64_t lpr = (row_bytes + vec - 1) / vec;
-  int lp_log2 = 0;
-  while ((1 << lp_log2) < lpr && lp_log2 < 6) ++lp_log2;
-  const int cpr = (int)((lpr + RUA_WAVE - 1) / RUA_WAVE);
-  const int64_t waves = (D.n_rows + RUA_WAVE - 1) / RUA_WAVE;
-  const int64_t grid = (waves + RUA_WAVES_PER_BLOCK - 1) / RUA_WAVES_PER_BLOCK;
-  if (grid > 0x7fffffffLL) return RUA_ERANGE;
-  const dim3 g((unsigned)grid), b(RUA_BLOCK);
-  if (g_trace_on.load(std::memory_order_relaxed)) {
+  if (tracing()) {
     char rec[160];
-    snprintf(rec, sizeof rec, "setitem_backward_kernel VEC=%d NT=%d TAIL8=%d value=%d raw=%d", vec, (int)NT, (int)tail8,
-             gval != nullptr, graw != nullptr);
+    snprintf(rec, sizeof rec, "setitem_backward_kernel VEC=%d NT=%d TAIL8=%d value=%d raw=%d", P.vec, (int)P.nt, (int)P.tail8, gval != nullptr, graw != nullptr);
     trace_add(rec);
   }
-#define RUA_LAUNCH_S(VEC, T8) \
-  hipLaunchKernelGGL((setitem_backward_kernel<VEC, NT, T8>), g, b, 0, s, D, S, grad, gval, graw, row_bytes, lpr, lp_log2, cpr)
-  if (tail8) { RUA_LAUNCH_S(16, true); return (int)hipGetLastError(); }
-  switch (vec) {
-    case 16: RUA_LAUNCH_S(16, false); break;
-    case 8:  RUA_LAUNCH_S(8, false); break;
-    case 4:  RUA_LAUNCH_S(4, false); break;
-    case 2:  RUA_LAUNCH_S(2, false); break;
-    default: RUA_LAUNCH_S(1, false); break;
-  }
-#undef RUA_LAUNCH_S
+  const dim3 g(P.grid), b(RUA_BLOCK);
+  with_bool(P.nt, [&](auto nt) {
+    auto go = [&](auto v, auto t8) {
+      hipLaunchKernelGGL((setitem_backward_kernel<RUA_V(v), RUA_V(nt), RUA_V(t8)>), g, b, 0, s, D, S, grad, gval, graw, row_bytes,
+                         P.lpr, P.lp_log2, P.cpr);
+    };
+    if (P.tail8) return go(int_c<16>{}, std::true_type{});
+    with_vec(P.vec, [&](auto v) { go(v, std::false_type{}); });
+  });
   return (int)hipGetLastError();
 }
 
 // `nbytes` from src to dst through the row mover's own streaming geometry: the bytes seen as ONE sequence of 1-KiB rows
 // (what C.roll(0) launches at the north-star shape: 16-row tiles in destination order, an XCD span on big launches),
 // and the last, shorter piece as a row of its own.
-constexpr int64_t COPY_ROW_BYTES = 1024;
 static int stream_copy(void* dst, const void* src, int64_t nbytes, void* stream) {
   auto flat = [](int64_t rows) {
-    rua_layout L;
-    memset(&L, 0, sizeof L);
+    rua_layout L = {};
     L.kind = RUA_LEFT; L.n_rows = rows; L.B = 1; L.T_phys = rows; L.T_log = rows; L.len_add = rows;
     return L;
   };
@@ -1618,20 +1285,46 @@ static int stream_copy(void* dst, const void* src, int64_t nbytes, void* stream)
   }
   if (tail > 0) {
     const rua_layout L = flat(1);
-    return rua_move_rows(&L, &L, RUA_T_SHIFT, 0, (char*)dst + rows * COPY_ROW_BYTES,
-                         (const char*)src + rows * COPY_ROW_BYTES, tail, nullptr, -1, 0, stream);
+    return rua_move_rows(&L, &L, RUA_T_SHIFT, 0, (char*)dst + rows * COPY_ROW_BYTES, (const char*)src + rows * COPY_ROW_BYTES, tail,
+                         nullptr, -1, 0, stream);
   }
   return 0;
 }
 
 }  // namespace rua
 
+using namespace rua;
+
+// plan, trace if on, launch
+extern "C" int rua_move_rows(const rua_layout* dst, const rua_layout* src, int32_t tmap, int64_t tmap_arg, void* dst_data,
+                             const void* src_data, int64_t row_bytes, const void* fill16, int64_t pad_row, int32_t flags,
+                             void* stream) {
+  const MoveRowsPlan P = plan_move_rows(dst, src, tmap, tmap_arg, (uintptr_t)dst_data, (uintptr_t)src_data, row_bytes, pad_row, flags);
+  if (P.err || P.form == MOVE_NONE) return P.err;
+  if (tracing()) { char rec[256]; format_move_plan(P, rec, sizeof rec); trace_add(rec); }
+  return launch_move_rows(P, (hipStream_t)stream, *dst, *src, tmap, tmap_arg, (char*)dst_data, (const char*)src_data, row_bytes,
+                          fill16, pad_row);
+}
+
+// the same validation, plan and record, and no launch: the payload ADDRESSES stand in for the pointers
+extern "C" int64_t rua_debug_move_plan(const rua_layout* dst, const rua_layout* src, int32_t tmap, int64_t tmap_arg,
+                                       uint64_t dst_addr, uint64_t src_addr, int64_t row_bytes, int64_t pad_row, int32_t flags,
+                                       char* buf, int64_t cap) {
+  const MoveRowsPlan P = plan_move_rows(dst, src, tmap, tmap_arg, (uintptr_t)dst_addr, (uintptr_t)src_addr, row_bytes, pad_row, flags);
+  if (P.err) return P.err;
+  char rec[256];
+  format_move_plan(P, rec, sizeof rec);
+  const int64_t n = (int64_t)strlen(rec);
+  if (!buf || n > cap) return RUA_ERANGE;
+  memcpy(buf, rec, (size_t)n);
+  return n;
+}
+
 extern "C" int rua_setitem_backward(const rua_layout* list, const rua_layout* src, const void* grad, void* grad_value,
                                     void* grad_raw, int64_t row_bytes, int32_t flags, void* stream) {
   int e;
   if (!list || list->kind != RUA_LIST) return RUA_EINVAL;
-  if ((e = check_layout(list, true)) != 0) return e;
-  if ((e = check_layout(src, false)) != 0) return e;
+  if ((e = check_layout(list, true)) != 0 || (e = check_layout(src, false)) != 0) return e;
   if (row_bytes < 0 || (flags & ~(RUA_MOVE_NT_ON | RUA_MOVE_NT_OFF)) != 0) return RUA_EINVAL;
   if (grad_raw && grad_raw == grad) return RUA_EINVAL;
   if (!grad && list->n_rows > 0) return RUA_EINVAL;
@@ -1640,20 +1333,15 @@ extern "C" int rua_setitem_backward(const rua_layout* list, const rua_layout* sr
     // every row nobody names is a copy of the same row of `grad`: the streaming copy first, the named rows are zeroed behind it
     if (!grad) return RUA_EINVAL;
     if ((double)src->n_rows * (double)row_bytes >= 9.0e18) return RUA_ERANGE;
-    if (g_trace_on.load(std::memory_order_relaxed)) trace_add("setitem_backward_copy");
+    if (tracing()) trace_add("setitem_backward_copy");
     if ((e = stream_copy(grad_raw, grad, src->n_rows * row_bytes, stream)) != 0) return e;
   }
   if (list->n_rows == 0) return 0;
-
-  // widest power-of-two access that divides the row size and all three base addresses (the mover's rule)
-  const uint64_t mix = (uint64_t)row_bytes | (uint64_t)(uintptr_t)grad | (uint64_t)(uintptr_t)grad_value |
-                       (uint64_t)(uintptr_t)grad_raw | 16u;
-  const int vec = (int)(mix & (~mix + 1));
-  const bool tail8 = vec == 8 && (row_bytes & 15) == 8 && row_bytes >= 24;
+  // the mover's rules: the lane width from the row size and all three base addresses, streaming by the larger output
   const int64_t dst_rows = grad_raw && src->n_rows > list->n_rows ? src->n_rows : list->n_rows;
-  const bool big = (double)dst_rows * (double)row_bytes >= (double)(512ll << 20);
-  const bool nt = (flags & RUA_MOVE_NT_ON) ? true : (flags & RUA_MOVE_NT_OFF) ? false : big;
-  hipStream_t s = (hipStream_t)stream;
-  return nt ? launch_setitem_backward<true>(vec, tail8, s, *list, *src, (const char*)grad, (char*)grad_value, (char*)grad_raw, row_bytes)
-            : launch_setitem_backward<false>(vec, tail8, s, *list, *src, (const char*)grad, (char*)grad_value, (char*)grad_raw, row_bytes);
+  const SetitemBackwardPlan P = plan_setitem_backward(list->n_rows, dst_rows, row_bytes,
+                                                      (uintptr_t)grad | (uintptr_t)grad_value | (uintptr_t)grad_raw, flags);
+  if (P.err) return P.err;
+  return launch_setitem_backward(P, (hipStream_t)stream, *list, *src, (const char*)grad, (char*)grad_value, (char*)grad_raw,
+                                 row_bytes);
 }

@@ -37,12 +37,7 @@ inline int reduce_team_waves(int64_t n_rows, int64_t B, int lp_log2, int64_t uni
   return groups >= 4 * 4 ? 4 : groups >= 4 * 2 ? 2 : 1;
 }
 
-// log2 of the lanes a row of `lpr` lanes occupies in a wave instruction (6: the whole wave, or more than one)
-inline int lanes_log2(int64_t lpr) {
-  int lp_log2 = 0;
-  while ((1 << lp_log2) < lpr && lp_log2 < 6) ++lp_log2;
-  return lp_log2;
-}
+// (lanes_log2, the lanes a row occupies in a wave instruction: rua_wave.h)
 // streaming (non-temporal) accesses for a payload that cannot stay in cache
 inline bool reduce_nt(int64_t n_rows, int64_t H, int esize) {
   return (double)n_rows * (double)H * (double)esize >= (double)(512ll << 20);
