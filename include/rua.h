@@ -799,6 +799,62 @@ int rua_segment_repeat_sum(const rua_layout* src, const rua_layout* dst, const i
                            const int64_t* counts, int64_t uniform, void* grad_src, const void* grad_dst, int64_t H,
                            int32_t dtype, void* stream);
 
+/* Per-sequence STABLE sort / argsort, and the per-sequence permutation that goes with it (an EXTENSION, added to ABI 6
+ * — the version number did not move: the reference cannot put the tokens of a sequence in order; its users pad with
+ * +inf and call torch.sort along dim 1, which is wrong when the payload holds inf or NaN, or run two global stable
+ * sorts).  For every sequence b of `lay` (ANY layout) and column h, over t < len[b]:
+ *   indices[row(b,t), h] = the token position — NOT a storage row: the same number in every layout — of the element
+ *                          of rank t; int64, in the storage layout of `data`
+ *   values[row(b,t), h]  = data[row(b, indices[row(b,t), h]), h], the input's BITS (values == NULL: argsort, nothing but
+ *                          the indices is written)
+ * under ONE total order on (key, position): a NaN is greater than every number (ascending: NaNs last; descending: first),
+ * -0.0 == +0.0, and equal keys — all NaNs among themselves too — keep ascending position in BOTH directions:
+ * torch.sort(seq, dim=0, stable=True, descending=d) of every sequence on its own.  RUA_F32 / RUA_F64 / RUA_BF16 / RUA_F16
+ * and RUA_I64; any other dtype: RUA_EINVAL.  Because the order is total, the bits depend on nothing but the sequence —
+ * not on the layout, the kernel form or the alignment.  Padding rows of a LEFT / RIGHT input are never read and are
+ * zeros in both outputs; an empty sequence contributes nothing; lengths are clamped to the storage and every row is
+ * range-checked.
+ * An element is (key image, position), sorted ascending as a whole: the image is the value's bits with the sign
+ * flipped (negative floats inverted), every NaN the all-ones maximum, -0 taken as +0, int64 biased by 2^63; `descending`
+ * inverts the image.  2- and 4-byte values pack image and position into one 64-bit word, 8-byte values keep 64 + 32 bits.
+ * Three forms by the length bound (CAT: T_log or n_rows, LEFT / RIGHT: T_phys, PACK: T):
+ *   lanes   bound <= 64: a (sequence, column) on G = 8 / 16 / 32 / 64 lanes (the power of two that holds the bound),
+ *           64 / G of them per wave, a bitonic network of cross-lane exchanges — no LDS;
+ *   block   bound <= 2 048 (rua_sort_block_len()): a workgroup per (sequence, column), a bitonic network over an LDS slab
+ *           of the next power of two above the length (16 KiB, 24 KiB for 8-byte values);
+ *   merge   longer: the block kernel sorts every block of 2 048 tokens — CAT: B + ceil(n_rows / 2 048) units per column,
+ *           so a long sequence among short ones costs what its rows cost; other layouts B * ceil(bound / 2 048) — and
+ *           leaves the runs of sequences longer than a block in the workspace; then ceil(log2(ceil(bound / 2 048)))
+ *           launches of a rank merge over a FLAT grid, a thread per storage element: an element of a left run goes to
+ *           its offset plus the lower bound of its key in the right run, one of a right run to its offset plus the
+ *           upper bound in the left run; the last pass of every sequence writes `values` / `indices` themselves.  The
+ *           first workspace word holds the passes any sequence needs: a launch beyond it returns at once.
+ * A CAT layout's T_log, where given (> 0), must be a TRUE upper bound of every length.  A bound of 2^31 or more is
+ * refused (RUA_ERANGE): positions are 31 bits.  rua_sort_ws_bytes(lay, H, dtype) =
+ *   256 + 2 * pad256(n_rows * H * 8) + (8-byte values: 2 * pad256(n_rows * H * 4))     pad256 = up to a multiple of 256
+ * bytes when bound > 2 048, else 0.  `ws` must be 256-byte aligned; merge form without it: RUA_EINVAL.
+ * Checks, before any HIP call: a null or inconsistent layout, H < 0 or an unknown dtype RUA_EINVAL (ws_bytes: 0); the
+ * bound RUA_ERANGE; B == 0, H == 0 or n_rows == 0 return 0; a null data / indices, or outputs that alias the input or
+ * each other, RUA_EINVAL; a misaligned pointer RUA_EALIGN.  Trace: `seg_sort_lanes_kernel | seg_sort_block_kernel dtype=
+ * H= G= kind= values= desc= passes=`, `seg_sort_merge_kernel pass= of= run=`.
+ * rua_segment_reorder: the per-sequence permutation; elements move as BITS (elem_bytes 1 / 2 / 4 / 8, else RUA_EINVAL).
+ *   per_row != 0: index [n_rows] int64, rows of H elements:    out[row(b,t)] = data[row(b, index[row(b,t)])]
+ *   per_row == 0: index [n_rows, H] int64:                     out[row(b,t), h] = data[row(b, index[row(b,t), h]), h]
+ *   inverse != 0: the scatter,                                 out[row(b, index[row(b,t)])] = data[row(b,t)]
+ * A position outside [0, len[b]) is never dereferenced: the gather writes zeros there, the scatter drops the element;
+ * padding rows are never read and are zeros in `out`.  The gather writes `out` completely in one launch; the scatter
+ * zeroes `out` on the stream first.  `index` must hold a permutation per sequence for the scatter to be defined
+ * (a repeated position: one of the writers wins).  Per row a thread group owns a row (one lane for rows of one
+ * vector, eight lanes of 16 bytes otherwise) with the widest access that divides the row and both bases; per element
+ * a thread per element.  Checks as above.  Trace: `seg_reorder_rows_kernel form= W= row_bytes= kind= inverse=`,
+ * `seg_reorder_elems_kernel elem_bytes= H= kind= inverse=`. */
+int64_t rua_sort_block_len(void);
+int64_t rua_sort_ws_bytes(const rua_layout* lay, int64_t H, int32_t dtype);
+int rua_segment_sort(const rua_layout* lay, const void* data, void* values /* NULL: argsort */, int64_t* indices,
+                     int64_t H, int32_t dtype, int32_t descending, void* ws, void* stream);
+int rua_segment_reorder(const rua_layout* lay, const void* data, const int64_t* index, void* out, int64_t H,
+                        int32_t elem_bytes, int32_t per_row, int32_t inverse, void* stream);
+
 /* Per-sequence argmax / argmin with the selected values (an EXTENSION, added to ABI 6 — the version number did not
  * move: the reference has no position-returning reduction; its users pad with -inf and call torch.argmax along dim 1).
  * For every sequence b of `lay` (ANY layout) and column h, over t < len[b] (op = RUA_MAX or RUA_MIN, anything else:

@@ -132,6 +132,12 @@ SYMBOLS = {
                                         c_int64, c_void_p]),
     'rua_segment_repeat_sum': (c_int, [POINTER(RuaLayout), POINTER(RuaLayout), c_void_p, c_void_p, c_int64, c_void_p,
                                        c_void_p, c_int64, c_int32, c_void_p]),
+    'rua_sort_block_len': (c_int64, []),
+    'rua_sort_ws_bytes': (c_int64, [POINTER(RuaLayout), c_int64, c_int32]),
+    'rua_segment_sort': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p,
+                                 c_void_p]),
+    'rua_segment_reorder': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32,
+                                    c_void_p]),
     'rua_argreduce_ws_bytes': (c_int64, [POINTER(RuaLayout), c_int64, c_int32]),
     'rua_segment_argreduce': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p,
                                       c_void_p]),

@@ -1538,6 +1538,102 @@ def take(data: Tensor, index: Tensor, lay: M.Lay, hidden) -> Tensor:
     return launch_take(lay, _plain(data), index, tuple(hidden))
 
 
+# ------------------------------------------------------------------ per-sequence stable sort / reorder (an extension)
+_SORT_SUPPORT = 'sort / argsort support'
+
+
+def launch_sort(lay: M.Lay, data: Tensor, descending: bool, hidden: Tuple[int, ...],
+                want_values: bool = True) -> Tuple[Optional[Tensor], Tensor]:
+    """rua_segment_sort: (values or None, indices), both of the storage shape of `data` and written completely by the
+    call — padding rows as zeros.  One launch for sequences up to a block (rua_sort_block_len), one plus the merge passes
+    of the length bound for longer ones; nothing is read back."""
+    code = _require_dtype(data, L.SCAN_DTYPES, _SORT_SUPPORT)
+    dev, H = data.device, _prod(hidden)
+    if data.numel() != lay.n_rows * H:
+        raise L.RuaError(f'sort: the payload has {data.numel()} elements, its layout {lay.n_rows} rows of {H}')
+    data = data.contiguous()
+    indices = torch.empty(tuple(data.shape), dtype=torch.int64, device=dev)
+    values = torch.empty_like(data) if want_values else None
+    if data.numel() == 0:
+        return values, indices
+    ws = _workspace('rua_sort_ws_bytes', lay, H, code, dev)
+    _call('sort' if want_values else 'argsort', 'rua_segment_sort', dev, lay.ref(), L.ptr(data), L.ptr(values),
+          L.ptr(indices), H, code, int(bool(descending)), L.ptr(ws))
+    return values, indices
+
+
+def launch_reorder(lay: M.Lay, data: Tensor, index: Tensor, hidden: Tuple[int, ...], per_row: bool,
+                   inverse: bool) -> Tensor:
+    """rua_segment_reorder: a new payload of the storage shape of `data` — the gather out[b, t] = data[b, index[b, t]]
+    or, with `inverse`, the scatter out[b, index[b, t]] = data[b, t]; per row (`index` holds one position per storage
+    row) or per element (one per element).  Bits move; positions outside a sequence give zeros; padding rows are zeros."""
+    dev = L.require_device(data, index)
+    if data.element_size() not in (1, 2, 4, 8):
+        raise L.RuaError(f'reorder moves elements of 1, 2, 4 or 8 bytes; got {data.dtype}')
+    H = _prod(hidden)
+    if data.numel() != lay.n_rows * H or index.dtype != torch.int64 or index.numel() != lay.n_rows * (1 if per_row else H):
+        raise L.RuaError(f'reorder: the payload has {data.numel()} elements and the index {index.numel()} ({index.dtype}); '
+                         f'the layout has {lay.n_rows} rows of {H}')
+    data, index = data.contiguous(), _plain(index).contiguous()
+    out = torch.empty_like(data)
+    if out.numel() == 0:
+        return out
+    flat = data.view(torch.uint8) if data.dtype == torch.bool else data
+    _call('reorder_inverse' if inverse else 'reorder', 'rua_segment_reorder', dev, lay.ref(), L.ptr(flat), L.ptr(index),
+          L.ptr(out), H, data.element_size(), int(bool(per_row)), int(bool(inverse)))
+    return out
+
+
+class _Reorder(torch.autograd.Function):
+    """payload -> payload permuted inside every sequence: linear, its adjoint is the same permutation the other way
+    round (gather <-> scatter), so derivatives of every order exist.  Saves ONLY the index."""
+
+    @staticmethod
+    def forward(ctx, data: Tensor, index: Tensor, lay: M.Lay, hidden, per_row: bool, inverse: bool):
+        ctx.args = (lay, tuple(hidden), bool(per_row), bool(inverse))
+        ctx.save_for_backward(index)
+        return launch_reorder(lay, data, index, hidden, per_row, inverse)
+
+    @staticmethod
+    def backward(ctx, grad: Tensor):
+        index, = ctx.saved_tensors
+        lay, hidden, per_row, inverse = ctx.args
+        return reorder(grad, index, lay, hidden, per_row, not inverse), None, None, None, None, None
+
+
+class _Sort(torch.autograd.Function):
+    """(values, indices) of every sequence in order.  Saves ONLY the indices; the backward scatters the gradient back
+    through them per element (reorder, inverse), whose own backward is the gather and so on."""
+
+    @staticmethod
+    def forward(ctx, data: Tensor, lay: M.Lay, descending: bool, hidden):
+        values, indices = launch_sort(lay, data, descending, hidden)
+        ctx.lay, ctx.hidden = lay, tuple(hidden)
+        ctx.save_for_backward(indices)
+        ctx.mark_non_differentiable(indices)
+        return values, indices
+
+    @staticmethod
+    def backward(ctx, grad: Tensor, _grad_indices):
+        indices, = ctx.saved_tensors
+        return reorder(grad, indices, ctx.lay, ctx.hidden, False, True), None, None, None
+
+
+def sort(data: Tensor, lay: M.Lay, descending: bool, hidden, want_values: bool = True) -> Tuple[Optional[Tensor], Tensor]:
+    _require_dtype(data, L.SCAN_DTYPES, _SORT_SUPPORT)
+    if want_values and _wants_grad(data):
+        # contiguous HERE, before the Function (as in reduce()): a copy made inside forward() would carry no history
+        return _Sort.apply(data.contiguous(), lay, bool(descending), tuple(hidden))
+    return launch_sort(lay, _plain(data), bool(descending), tuple(hidden), want_values)
+
+
+def reorder(data: Tensor, index: Tensor, lay: M.Lay, hidden, per_row: bool, inverse: bool) -> Tensor:
+    L.require_device(data, index)
+    if _wants_grad(data):
+        return _Reorder.apply(data.contiguous(), index, lay, tuple(hidden), bool(per_row), bool(inverse))
+    return launch_reorder(lay, _plain(data), index, tuple(hidden), bool(per_row), bool(inverse))
+
+
 # ------------------------------------------------------------------ scatter-sum of rows (adjoint of a row gather)
 def index_buckets(index: Tensor, S: int) -> Tuple[Tensor, Tensor]:
     """(counts[S], perm[M]): the entries of `index` bucketed by destination, every bucket in ascending entry order
