@@ -665,6 +665,54 @@ int rua_segment_compress_plan(const rua_layout* lay, const void* mask, int32_t* 
 int rua_segment_compress_move(const rua_layout* small, const rua_layout* big, const int32_t* rank, void* small_data,
                               void* big_data, int64_t row_bytes, int32_t expand, void* stream);
 
+/* Per-sequence unique_consecutive — collapse every run of equal consecutive tokens INSIDE a sequence to its first token
+ * and say how long the run was (an EXTENSION, added to ABI 6 — the version number did not move: stock torch offers
+ * torch.unique_consecutive per sequence in a Python loop; a global call merges a run across the border of two
+ * sequences).  The inverse of rua_segment_repeat_*.  It reuses the compress pair: the caller runs
+ *   rua_segment_runs_heads -> rua_segment_compress_plan (rank, new_lens) [-> rua_segment_runs_inverse]
+ *   -> ONE read-back of new_lens -> rua_segment_compress_move (the values) [-> rua_segment_runs_counts]
+ * and nothing here synchronises.
+ * rua_segment_runs_heads: the only kernel that reads the payload.  For the storage row j of every token (b, t) of `lay`
+ * (ANY layout) it writes head[j] (one byte per storage row, n_rows bytes) = 1 when t == 0 or the row differs from the
+ * row of token (b, t - 1), else 0; padding rows of a LEFT / RIGHT storage are neither read nor written.  The
+ * predecessor's row comes from the layout's own row formula, so a sequence's first token is compared with nothing.  `eq`
+ * is the equality rule: RUA_F32 / RUA_BF16 / RUA_F16 / RUA_F64 compare element by element as IEEE does (a NaN differs
+ * from everything, itself included; -0.0 equals +0.0; row_bytes must be a multiple of the element size), RUA_RUNS_BITS
+ * compares bits.  Rows are row_bytes wide.  Two compares: rows of at most 16 bytes take one vector load of the row and
+ * one of its predecessor, a lane per token, in the geometry of the offsets scan (form=lanes|rows|long|cut by the length
+ * bound, as rua_segment_compress_plan; no workspace: a block needs nothing from the blocks before it); wider rows give
+ * a workgroup per sequence (form=long) or per block of 2 048 tokens of one (form=cut, the same rule), 32 tokens x 8
+ * lanes, every lane a 16-byte piece of each 128-byte chunk, combined by ballot, stopping at the first chunk that
+ * differs.  Accesses are the widest power of two, up to 16 bytes, that divides row_bytes and the base address.  The
+ * payload is read at most twice — a row, and the same row as its successor's predecessor — and no [N, H] temporary
+ * exists.  Checks, before any HIP call: a null or inconsistent layout or row_bytes < 0 RUA_EINVAL; a length bound of
+ * 2^31 or more RUA_ERANGE; an `eq` that is neither, or a float rule with a row that is no multiple of its element,
+ * RUA_EINVAL; B == 0 or n_rows == 0 returns 0; a null head, a null payload (row_bytes > 0) or head == data RUA_EINVAL.
+ * Trace: `seg_runs_heads_lanes_kernel` / `seg_runs_heads_rows_kernel form= G= kind= cut= blocks= phase=whole W=
+ * row_bytes=`.
+ * rua_segment_runs_inverse: inverse[j] (int64, n_rows entries) = #{s <= t : head[row(b, s)] != 0} - 1 for the row j of
+ * token (b, t) — the index of the token's run inside its sequence — and 0 for a padding row; new_lens[b] = the number of
+ * heads (what rua_segment_compress_plan writes too; B entries).  The offsets scan of rua_segment_compress_plan over the
+ * same mask: its four forms, its workspace rule (rua_compress_ws_bytes; ws == NULL = do not cut) and its checks, in its
+ * order; a pointer that is not aligned to its element RUA_EALIGN.  Trace: `seg_runs_inverse_kernel form=lanes|rows|
+ * long|cut G= kind= cut= blocks= phase=whole|count|finish`.
+ * rua_segment_runs_counts: `big` is the input's layout, `small` the result's (any two kinds, the same B), `rank` the
+ * plan's table.  counts[row_small(b, r)] (int64, small's n_rows entries) = start(b, r + 1) - start(b, r), where
+ * start(b, r) is the position of the head of rank r in sequence b of big and start(b, R_b) = the length of that
+ * sequence; padding rows of a LEFT / RIGHT small are zeros.  Two launches and no atomics (a long run costs what a short
+ * one does): the heads of big leave their positions in `starts` (int32, small's n_rows entries, laid out like counts;
+ * caller-given scratch), then every run reads its own and its successor's.  Both walk in the geometry of the offsets
+ * scan, the first over big, the second over small.  Checks: the entry checks of the plan for `big`, then for `small`;
+ * different B RUA_EINVAL; B == 0 or a small without rows returns 0; a null pointer or two that alias RUA_EINVAL; a
+ * misaligned one RUA_EALIGN.  Trace: `seg_runs_counts_kernel form= G= kind= cut= blocks= phase=starts|diff`. */
+#define RUA_RUNS_BITS 0x100   /* `eq` of rua_segment_runs_heads: rows are equal when their bits are */
+int rua_segment_runs_heads(const rua_layout* lay, const void* data, int64_t row_bytes, int32_t eq, void* head,
+                           void* stream);
+int rua_segment_runs_inverse(const rua_layout* lay, const void* head, int64_t* inverse, int64_t* new_lens, void* ws,
+                             void* stream);
+int rua_segment_runs_counts(const rua_layout* small, const rua_layout* big, const int32_t* rank, int32_t* starts,
+                            int64_t* counts, void* stream);
+
 /* Per-sequence join and unjoin — concatenate ragged batches along time, and cut one at per-sequence boundaries (an
  * EXTENSION, added to ABI 6 — the version number did not move: the reference's users loop over B pairs with torch.cat,
  * or gather through an index built with repeat_interleave, and call a constructor again; for a CattedSequence only).

@@ -1163,6 +1163,56 @@ def expand(data: Tensor, rank: Tensor, small: M.Lay, big: M.Lay, hidden, small_s
     return launch_compress_move(small, big, rank, _plain(data), tuple(hidden), tuple(big_shape), True)
 
 
+# ------------------------------------------------------------------ per-sequence unique_consecutive (an extension)
+def launch_runs_heads(lay: M.Lay, data: Tensor, hidden: Tuple[int, ...]) -> Tensor:
+    """rua_segment_runs_heads: a bool per storage row of `lay` — whether the token is the first of its sequence or
+    differs from its predecessor in it (IEEE equality for the float dtypes, bits otherwise).  One launch, the only one
+    that reads the payload; what launch_compress_plan scans.  Padding rows are not written."""
+    dev = L.require_device(data)
+    if data.is_complex() or data.element_size() not in (1, 2, 4, 8):
+        raise L.RuaError(f'unique_consecutive compares elements of 1, 2, 4 or 8 bytes that are not complex; got {data.dtype}')
+    data = _plain(data).contiguous()
+    head = torch.empty(lay.n_rows, dtype=torch.bool, device=dev)
+    if lay.B == 0 or lay.n_rows == 0:
+        return head
+    _call('runs_heads', 'rua_segment_runs_heads', dev, lay.ref(), L.ptr(data), _prod(hidden) * data.element_size(),
+          L.DTYPES.get(data.dtype, L.RUNS_BITS), L.ptr(head))
+    return head
+
+
+def launch_runs_inverse(lay: M.Lay, head: Tensor, lead_shape: Sequence[int], cut: bool = True) -> Tensor:
+    """rua_segment_runs_inverse: int64 of the storage's token dimensions — the index of every token's run inside its
+    sequence, zeros in padding rows — from the head mask; one launch (two for cut sequences)."""
+    dev = L.require_device(head)
+    if head.dtype != torch.bool or head.numel() != lay.n_rows or not head.is_contiguous():
+        raise L.RuaError('runs inverse: the head mask is a contiguous torch.bool tensor with one value per storage row')
+    inverse = torch.empty(tuple(lead_shape), dtype=torch.int64, device=dev)
+    if inverse.numel() != lay.n_rows:
+        raise L.RuaError(f'runs inverse: the token dimensions {tuple(lead_shape)} do not hold {lay.n_rows} storage rows')
+    if lay.B == 0 or lay.n_rows == 0:
+        return inverse
+    ws = _workspace('rua_compress_ws_bytes', lay, None, None, dev, cut)
+    lens = torch.empty(lay.B, dtype=torch.int64, device=dev)     # (the scan's sums: the plan's new lengths again)
+    _call('runs_inverse', 'rua_segment_runs_inverse', dev, lay.ref(), L.ptr(head), L.ptr(inverse), L.ptr(lens), L.ptr(ws))
+    return inverse
+
+
+def launch_runs_counts(small: M.Lay, big: M.Lay, rank: Tensor, lead_shape: Sequence[int]) -> Tensor:
+    """rua_segment_runs_counts: int64 of the token dimensions of the RESULT's storage — the length of every run, zeros
+    in padding rows — from the plan's rank table; two small launches, no atomics."""
+    dev = L.require_device(rank)
+    if rank.dtype != torch.int32 or rank.numel() != big.n_rows or not rank.is_contiguous():
+        raise L.RuaError('runs counts: the rank table is a contiguous int32 tensor with one entry per storage row')
+    counts = torch.empty(tuple(lead_shape), dtype=torch.int64, device=dev)
+    if counts.numel() != small.n_rows:
+        raise L.RuaError(f'runs counts: the token dimensions {tuple(lead_shape)} do not hold {small.n_rows} storage rows')
+    if big.B == 0 or small.n_rows == 0:
+        return counts
+    starts = torch.empty(small.n_rows, dtype=torch.int32, device=dev)
+    _call('runs_counts', 'rua_segment_runs_counts', dev, small.ref(), big.ref(), L.ptr(rank), L.ptr(starts), L.ptr(counts))
+    return counts
+
+
 # ------------------------------------------------------------------ per-sequence repeat_interleave (an extension)
 def launch_repeat_plan(lay: M.Lay, counts: Tensor, cut: bool = True) -> Tuple[Tensor, Tensor]:
     """rua_segment_repeat_plan: (first int64 [storage rows of `lay`], new_lens int64 [B + 1]) from int64 counts with one

@@ -42,8 +42,9 @@ that are each other's backward, so derivatives of every order exist.  Only the i
 no int64 index, not the mask.  Gradients of dropped tokens and of padding rows are exact zeros, whatever the payload
 holds there (NaN, inf).  Integer and bool payloads pass through without a graph.
 
-Out of scope: selection by index lists or top-k, per-column masks, a fused `unique_consecutive` / CTC collapse (that is
-a mask built with `roll` and `!=`), returning the dropped tokens as well.
+Out of scope: selection by index lists or top-k, per-column masks, returning the dropped tokens as well.  Collapsing
+runs of equal tokens (the CTC collapse) is `z.unique_consecutive()` (unique.py), which builds its mask on the device
+and goes through this plan and move.
 """
 from typing import Tuple
 

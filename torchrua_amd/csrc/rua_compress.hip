@@ -37,6 +37,7 @@ struct cp_scan {
   using sum_t = int32_t;
   using val_t = bool;
   static constexpr bool COUNTS_INVALID = false;
+  static constexpr int32_t PAD = -1;
   static const char* kernel() { return "seg_compress_plan_kernel"; }
   static const char* phase1() { return "count"; }
   static __device__ __forceinline__ bool load(const uint8_t* mask, int64_t row, int&) { return mask[row] != 0; }
@@ -57,16 +58,7 @@ struct cp_scan {
 static_assert(sizeof(cp_scan::sum_t) == CP_WS_ELEM_BYTES, "the workspace the host plan sizes holds the kernel's counts");
 
 // ---------------------------------------------------------------- the move
-// the row of `small` that the token of big's row `row` (sequence b) goes to, or -1: dropped, or a rank that names no
-// token of the new sequence (a rank table that does not belong to these layouts must not index out of range)
-__device__ __forceinline__ int64_t cm_small_row(const rua_layout& S, const int32_t* rank, int64_t b, int64_t row,
-                                                int64_t slen) {
-  const int64_t r = rank[row];
-  if (r < 0 || r >= slen) return -1;
-  const int64_t sr = token_to_row(S, b, r, slen);
-  return sr >= 0 && sr < S.n_rows ? sr : -1;
-}
-
+// (the row of `small` a token of `big` goes to: cm_small_row, rua_seg_scan.h)
 // Rows wider than one vector: a workgroup per unit of `big` and 128-byte column chunk; a unit is a sequence, or
 // (maxblk > 0: few but long sequences) a block of SEG_BLOCK_TOK tokens of one.  Thread (q, l) = (tid / 8, tid % 8) takes
 // the tokens q, q + 32, ... of the unit, CM_UNR of them in flight, and owns the l-th 16-byte piece of the chunk.

@@ -38,6 +38,7 @@ struct rp_scan {
   using sum_t = int64_t;
   using val_t = int64_t;
   static constexpr bool COUNTS_INVALID = true;
+  static constexpr int64_t PAD = -1;
   static const char* kernel() { return "seg_repeat_plan_kernel"; }
   static const char* phase1() { return "sum"; }
   static __device__ __forceinline__ int64_t load(const int64_t* counts, int64_t row, int& bad) {

@@ -1,7 +1,7 @@
 // rua_seg_scan.h — the offsets scan of the operators whose result has another raggedness than their input
-// (rua_compress.hip, rua_repeat.hip; included by these two alone): ONE value per token of the input's storage layout,
+// (rua_compress.hip, rua_repeat.hip, rua_runs.hip; included by these alone): ONE value per token of the input's storage layout,
 // scanned exclusively per sequence.  out[row] = what the operator makes of the token's value and of the sum in front of
-// it in its sequence, -1 for a padding row; new_lens[b] = the sum over the sequence.  Integer work: every form gives
+// it in its sequence, Op::PAD for a padding row; new_lens[b] = the sum over the sequence.  Integer work: every form gives
 // the same bits.  Its host plan is seg_make_scan_plan (rua_seg_plan.h).
 //
 // An operator is a struct `Op` that holds what differs and nothing else:
@@ -11,6 +11,7 @@
 //   wave_prefix<G>(v, lane, q, before, total)   over the min(G, 64) lanes that scan together: the sum in front of the
 //                                   lane and the sum of all
 //   store(v, position)              what out[row] gets
+//   PAD                             what a padding row of a LEFT / RIGHT storage gets
 //   COUNTS_INVALID                  whether `bad` is added to new_lens[B] (a word the entry point zeroed)
 //   kernel(), phase1()              the names of the trace records
 #pragma once
@@ -29,8 +30,19 @@ void trace_add(const char* rec);
 // sum of the steps before is carried in a register.
 // phase 0: `out` and new_lens in one launch.  The cut form takes two: phase 1 leaves every block's sum in
 // ws[b * maxblk + blk] (and counts the invalid values); phase 2 adds the sums of the blocks before its own in block
-// order and writes `out`, the last block also new_lens.  Padding rows of a LEFT / RIGHT storage get -1 (block 0 writes
-// them).
+// order and writes `out`, the last block also new_lens.  Padding rows of a LEFT / RIGHT storage get Op::PAD (block 0
+// writes them).
+// the row of `small` that the token of big's row `row` (sequence b) goes to by the rank table of a compress plan, or
+// -1: dropped, or a rank that names no token of the new sequence (a rank table that does not belong to these layouts
+// must not index out of range)
+__device__ __forceinline__ int64_t cm_small_row(const rua_layout& S, const int32_t* rank, int64_t b, int64_t row,
+                                                int64_t slen) {
+  const int64_t r = rank[row];
+  if (r < 0 || r >= slen) return -1;
+  const int64_t sr = token_to_row(S, b, r, slen);
+  return sr >= 0 && sr < S.n_rows ? sr : -1;
+}
+
 template <int G, typename Op>
 __global__ __launch_bounds__(RUA_BLOCK) void seg_offsets_kernel(rua_layout L, const typename Op::in_t* __restrict__ in,
                                                                 typename Op::out_t* __restrict__ out,
@@ -97,7 +109,7 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_offsets_kernel(rua_layout L, co
     if (phase == 1) ws[b * maxblk + blk] = carried;
     else if (phase == 0 || blk == maxblk - 1) new_lens[b] = carried;
   }
-  if (phase != 1 && blk == 0) seg_fill_padding(L, b, len, q, G, [&](int64_t row) { out[row] = -1; });
+  if (phase != 1 && blk == 0) seg_fill_padding(L, b, len, q, G, [&](int64_t row) { out[row] = Op::PAD; });
 }
 
 static const char* seg_scan_form_name(int form) {
