@@ -713,6 +713,68 @@ int rua_segment_runs_inverse(const rua_layout* lay, const void* head, int64_t* i
 int rua_segment_runs_counts(const rua_layout* small, const rua_layout* big, const int32_t* rank, int32_t* starts,
                             int64_t* counts, void* stream);
 
+/* Per-sequence sliding-window pooling — max / mean / sum over windows of K tokens every S tokens along time (an
+ * EXTENSION, added to ABI 6 — the version number did not move: the reference's users pad with left(), transpose, call
+ * F.max_pool1d / F.avg_pool1d, compute the new lengths by hand and cast back; windows at a sequence's end then read the
+ * padding).  The first operator whose new raggedness is a CLOSED FORM of the old one.  For a sequence of n tokens
+ * (clamped to its storage), 1 <= K <= RUA_WINDOW_MAX_K, 1 <= S <= 2^31 - 1:
+ *   n <= 0:            n_out = 0
+ *   ceil_mode == 0:    n_out = (n - K) / S + 1 if n >= K, else 0
+ *   ceil_mode != 0:    m = ceil(max(n - K, 0) / S) + 1;  n_out = m - 1 if (m - 1) * S >= n, else m
+ * (ceil mode: a sequence shorter than K gives ONE clipped window).  Window u covers the tokens [u S, min(u S + K, n)):
+ * never empty, clipped at the end of the sequence, never reaching into padding or the next sequence.  S > K skips
+ * tokens; K == 1 is the strided subsample.  Where torch accepts the input, n_out and the values are those of
+ * F.max_pool1d(ceil_mode) / F.avg_pool1d(ceil_mode, count_include_pad=False).
+ * rua_window_lens: out_lens[b] = n_out of sequence b ([B] int64, one thread per sequence, one launch); own_lens, if
+ *   given ([B]), receives the length as `lay` GIVES it (lens[b] + len_add, unclamped) — what a caller that has to read
+ *   the new lengths back reads back with them.  A RIGHT `lay` whose T_log the caller does not know yet may be described
+ *   with T_log = T_phys here: only the clamp reads it.
+ * rua_segment_window_pool: `src_lay` describes `data`, `dst_lay` `out` (any two kinds, the same B; dst's lengths are
+ *   rua_window_lens's, or any others: a window past its sequence's end is written as zeros).  DESTINATION-driven: window
+ *   (b, u) reads its at most K rows through src's own row formula and writes ONE row; padding rows of src are never
+ *   read, padding rows of a LEFT / RIGHT dst are zeros written in the same launch.  Per column, `mode`:
+ *     RUA_SUM   the accumulator (fp32; fp64 for RUA_F64; int64, wrapping, for RUA_I64) starts at the window's first
+ *               token and adds the others in ascending position; one rounding.
+ *     RUA_MEAN  that sum, divided ONCE in the accumulator type by the number of tokens IN the window (never by K where
+ *               the window is clipped); one rounding.  RUA_I64: RUA_EINVAL.
+ *     RUA_MAX   argmax's total order on (value, position): a NaN beats every number, the first NaN or the first maximal
+ *               position wins, -0.0 == +0.0.  out holds the winner's BITS.  `arg` (may be NULL; uint8, shaped like out)
+ *               receives the winner's offset inside its window, 0 .. K - 1.
+ *     RUA_WINDOW_TAKE  reads `arg`: out[u] = data[u S + arg[u]] per column (zeros where that offset is outside the
+ *               window) — RUA_MAX as the linear map it is once arg is known.
+ *   ONE evaluation order per (window, column) whatever the layouts, the kernel form, the alignment or a block border: the
+ *   operator commutes with the casts bit for bit.
+ * rua_segment_window_spread: the adjoint.  `pooled_lay` describes grad_out (and arg), `big_lay` grad_in.  SOURCE-driven,
+ *   no atomics: token (b, t) of big adds, in ascending u, the windows u in [ceil((t - K + 1) / S), floor(t / S)] that
+ *   exist — g[u] (RUA_SUM), g[u] / cnt[u] with cnt the tokens in window u, divided first and then added (RUA_MEAN), g[u]
+ *   where arg[u] == t - u S (RUA_MAX and RUA_WINDOW_TAKE alike) — into an accumulator of the types above that starts at
+ *   +0; one rounding.  Tokens in no window (the gaps of S > K, a dropped tail) and the padding rows of a LEFT / RIGHT big
+ *   get exact zeros whatever grad_out holds; every row of grad_in is written.  Bit-identical across layouts too.
+ * Forms (those of rua_segment_causal_conv): rows of at most 16 bytes put consecutive windows (the spread: tokens) of a
+ * sequence on consecutive lanes, 32 per sequence, two sequences per wave (`form=lanes`); wider rows give a workgroup per
+ * (sequence x 128-byte column chunk), 16 bytes per thread (`form=rows`; `form=unaligned`: rows or bases off 16 bytes,
+ * elementwise accesses).  Few but long sequences (the family's cut rule over the BIG layout: fewer than 1 024
+ * sequence x chunk units with a bound of at least 8 192 tokens) are cut across workgroups, no workspace and no second
+ * launch: block i of the spread takes the tokens [2 048 i, 2 048 (i + 1)), block i of the pool the windows that BEGIN
+ * there.  A CAT big layout's T_log, where given (> 0), must be a TRUE bound, as for rua_segment_softmax.  Any H, any
+ * alignment of an element; lengths are clamped to the storages and every row is range-checked.
+ * Checks, before any HIP call: a null or inconsistent layout, H < 0, a dtype other than the four float types and
+ * RUA_I64, layouts of different B, a mode other than the four, RUA_I64 with RUA_MEAN, K < 1 or S < 1: RUA_EINVAL;
+ * K > RUA_WINDOW_MAX_K: RUA_ERANGE; then B == 0, a written side without rows or H == 0 returns 0 without a launch; then
+ * a null output, a null input where its layout has rows, a null arg where the mode reads it, out == data (grad_in ==
+ * grad_out), arg equal to either: RUA_EINVAL; a pointer that is not aligned to its element: RUA_EALIGN.  Trace:
+ * `seg_window_lens_kernel K= S= ceil= kind= B=` and `seg_window_pool_kernel` / `seg_window_spread_kernel form=lanes|rows|
+ * unaligned T= K= S= mode=sum|mean|max|take kind=<written> from=<read> cut= blocks=` (+ `W= H=` / `AL= chunks=`). */
+#define RUA_WINDOW_MAX_K 64
+#define RUA_WINDOW_TAKE 6   /* the fourth `mode`, next to RUA_SUM, RUA_MEAN and RUA_MAX of enum rua_op */
+int rua_window_lens(const rua_layout* lay, int32_t K, int32_t S, int32_t ceil_mode, int64_t* out_lens, int64_t* own_lens,
+                    void* stream);
+int rua_segment_window_pool(const rua_layout* src_lay, const rua_layout* dst_lay, const void* data, void* out,
+                            uint8_t* arg, int64_t H, int32_t K, int32_t S, int32_t mode, int32_t dtype, void* stream);
+int rua_segment_window_spread(const rua_layout* pooled_lay, const rua_layout* big_lay, const void* grad_out,
+                              const uint8_t* arg, void* grad_in, int64_t H, int32_t K, int32_t S, int32_t mode,
+                              int32_t dtype, void* stream);
+
 /* Per-sequence join and unjoin — concatenate ragged batches along time, and cut one at per-sequence boundaries (an
  * EXTENSION, added to ABI 6 — the version number did not move: the reference's users loop over B pairs with torch.cat,
  * or gather through an index built with repeat_interleave, and call a constructor again; for a CattedSequence only).

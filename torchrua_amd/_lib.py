@@ -33,6 +33,8 @@ OP_SHORT_SEQS = 0x400      # rua.h: a CattedSequence of short sequences, none fa
 CONV_MAX_TAPS = 8          # rua.h: RUA_CONV_MAX_TAPS, the longest filter of rua_segment_causal_conv
 JOIN_MAX_PARTS = 8         # rua.h: RUA_JOIN_MAX_PARTS, the most parts of one rua_segment_join
 RUNS_BITS = 0x100          # rua.h: RUA_RUNS_BITS, the `eq` of rua_segment_runs_heads that compares bits
+WINDOW_MAX_K = 64          # rua.h: RUA_WINDOW_MAX_K, the longest window of rua_segment_window_pool
+WINDOW_TAKE = 6            # rua.h: RUA_WINDOW_TAKE, the fourth mode of rua_segment_window_pool / _spread (next to SUM, MEAN, MAX)
 # enum rua_dtype / rua_op
 F32, BF16, F16, F64 = 0, 1, 2, 3
 SUM, MEAN, MAX, MIN, PROD, LOGSUMEXP = 0, 1, 2, 3, 4, 5
@@ -125,6 +127,11 @@ SYMBOLS = {
     'rua_segment_runs_heads': (c_int, [POINTER(RuaLayout), c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
     'rua_segment_runs_inverse': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'rua_segment_runs_counts': (c_int, [POINTER(RuaLayout), POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_void_p]),
+    'rua_window_lens': (c_int, [POINTER(RuaLayout), c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    'rua_segment_window_pool': (c_int, [POINTER(RuaLayout), POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_int64,
+                                        c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    'rua_segment_window_spread': (c_int, [POINTER(RuaLayout), POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_int64,
+                                          c_int32, c_int32, c_int32, c_int32, c_void_p]),
     'rua_segment_join_lens': (c_int, [POINTER(RuaLayout), c_int32, c_void_p, c_void_p, c_void_p]),
     'rua_segment_unjoin_lens': (c_int, [POINTER(RuaLayout), POINTER(c_void_p), POINTER(c_int64), c_int32, c_void_p,
                                         c_void_p, c_void_p]),

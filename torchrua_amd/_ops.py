@@ -1458,6 +1458,138 @@ def unjoin(data: Tensor, plan: JoinPlan) -> Tuple[Tensor, ...]:
     return launch_join(plan, _plain(data), True)
 
 
+# ------------------------------------------------------------------ per-sequence sliding-window pooling (an extension)
+_WINDOW_SUPPORT = 'window_pool supports'
+WINDOW_MODES = {'sum': L.SUM, 'mean': L.MEAN, 'max': L.MAX}
+_WINDOW_NAMES = {L.SUM: 'sum', L.MEAN: 'mean', L.MAX: 'max', L.WINDOW_TAKE: 'take'}
+
+
+class WindowPlan:
+    """Everything a rua_segment_window_pool / _spread launch needs except the payloads: the layout and storage shape of
+    the POOLED side and of the BIG side (the layouts keep their length vectors alive), the window and the step.  This
+    is all the sum and mean Functions hold."""
+    __slots__ = ('small', 'big', 'hidden', 'small_shape', 'big_shape', 'K', 'S')
+
+    def __init__(self, small: M.Lay, big: M.Lay, hidden, small_shape, big_shape, K: int, S: int):
+        self.small, self.big, self.hidden = small, big, tuple(hidden)
+        self.small_shape, self.big_shape, self.K, self.S = tuple(small_shape), tuple(big_shape), int(K), int(S)
+
+
+def launch_window_lens(lay: M.Lay, K: int, S: int, ceil_mode: bool, dev, want_own: bool = False) -> Tensor:
+    """rua_window_lens: row 0 of the result is the number of windows of every sequence; with want_own a row 1 follows,
+    the container's own lengths — one buffer, one copy for a caller who reads back.  One small launch, no ATen kernel."""
+    B = lay.B
+    out = torch.empty((2 if want_own else 1, B), dtype=torch.long, device=dev)
+    if B:
+        _call('window_lens', 'rua_window_lens', dev, lay.ref(), int(K), int(S), int(bool(ceil_mode)), L.ptr(out),
+              out.data_ptr() + 8 * B if want_own else None)
+    return out
+
+
+def _window_payload(src: Tensor, shape, what: str) -> int:
+    code = _require_dtype(src, L.SCAN_DTYPES, _WINDOW_SUPPORT)
+    if src.numel() != _prod(shape):
+        raise L.RuaError(f'window_pool: the {what} does not fit the plan (storage shape {tuple(shape)}; got '
+                         f'{tuple(src.shape)})')
+    return code
+
+
+def _window_arg(arg: Optional[Tensor], plan: WindowPlan, dev) -> Tensor:
+    if arg is None or arg.dtype != torch.uint8 or arg.numel() != _prod(plan.small_shape) or not arg.is_contiguous():
+        raise L.RuaError('window_pool: the arg table is a contiguous uint8 tensor shaped like the pooled payload')
+    L.require_device(arg)
+    return arg
+
+
+def launch_window_pool(plan: WindowPlan, data: Tensor, mode: int, arg: Optional[Tensor] = None,
+                       want_arg: bool = False) -> Tuple[Tensor, Optional[Tensor]]:
+    """rua_segment_window_pool: payload of `plan.big` -> (payload of `plan.small`, arg).  mode MAX with want_arg also
+    returns the uint8 table of the winners' offsets; mode WINDOW_TAKE reads `arg`.  ONE launch; padding rows of a
+    padded result are zeros."""
+    code = _window_payload(data, plan.big_shape, 'payload')
+    dev = data.device
+    data = data.contiguous()
+    if mode == L.WINDOW_TAKE:
+        arg = _window_arg(arg, plan, dev)
+    else:
+        arg = torch.empty(plan.small_shape, dtype=torch.uint8, device=dev) if want_arg and mode == L.MAX else None
+    out = torch.empty(plan.small_shape, dtype=data.dtype, device=dev)
+    if out.numel():
+        _call('window_' + _WINDOW_NAMES[mode], 'rua_segment_window_pool', dev, plan.big.ref(), plan.small.ref(),
+              L.ptr(data) if data.numel() else None, L.ptr(out), L.ptr(arg), _prod(plan.hidden), plan.K, plan.S, mode,
+              code)
+    return out, arg
+
+
+def launch_window_spread(plan: WindowPlan, grad: Tensor, mode: int, arg: Optional[Tensor] = None) -> Tensor:
+    """rua_segment_window_spread, the adjoint: payload of `plan.small` -> payload of `plan.big`; tokens in no window and
+    padding rows get exact zeros.  ONE launch (also where nothing was pooled: the zeros are the kernel's)."""
+    code = _window_payload(grad, plan.small_shape, 'pooled payload')
+    dev = grad.device
+    grad = grad.contiguous()
+    by_arg = mode in (L.MAX, L.WINDOW_TAKE)
+    if by_arg:
+        arg = _window_arg(arg, plan, dev)
+    out = torch.empty(plan.big_shape, dtype=grad.dtype, device=dev)
+    if out.numel():
+        _call('window_spread_' + _WINDOW_NAMES[mode], 'rua_segment_window_spread', dev, plan.small.ref(), plan.big.ref(),
+              L.ptr(grad) if grad.numel() else None, L.ptr(arg) if by_arg and arg.numel() else None, L.ptr(out),
+              _prod(plan.hidden), plan.K, plan.S, mode, code)
+    return out
+
+
+class _WindowPool(torch.autograd.Function):
+    """payload of the big side -> payload of the pooled side.  sum and mean are linear and hold ONLY the plan (length
+    vectors and layout metadata); max keeps the uint8 table of the winners' offsets — one byte per output element, no
+    payload, no int64 index — and, given that table, is the linear map `take`.  The adjoint is _WindowSpread."""
+
+    @staticmethod
+    def forward(ctx, data: Tensor, arg: Optional[Tensor], plan: WindowPlan, mode: int):
+        out, arg = launch_window_pool(plan, data, mode, arg, want_arg=True)
+        ctx.plan, ctx.mode = plan, mode
+        if arg is not None:
+            ctx.save_for_backward(arg)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad: Tensor):
+        arg = ctx.saved_tensors[0] if ctx.saved_tensors else None
+        return window_spread(grad, arg, ctx.plan, ctx.mode), None, None, None
+
+
+class _WindowSpread(torch.autograd.Function):
+    """payload of the pooled side -> payload of the big side: the adjoint of _WindowPool, and _WindowPool (max: as
+    `take`) is its adjoint — derivatives of every order from the two kernels."""
+
+    @staticmethod
+    def forward(ctx, grad: Tensor, arg: Optional[Tensor], plan: WindowPlan, mode: int):
+        ctx.plan, ctx.mode = plan, mode
+        if arg is not None:
+            ctx.save_for_backward(arg)
+        return launch_window_spread(plan, grad, mode, arg)
+
+    @staticmethod
+    def backward(ctx, grad: Tensor):
+        arg = ctx.saved_tensors[0] if ctx.saved_tensors else None
+        mode = L.WINDOW_TAKE if ctx.mode in (L.MAX, L.WINDOW_TAKE) else ctx.mode
+        return window_pool(grad, ctx.plan, mode, arg), None, None, None
+
+
+def window_pool(data: Tensor, plan: WindowPlan, mode: int, arg: Optional[Tensor] = None) -> Tensor:
+    L.require_device(data)
+    if data.is_floating_point() and data.requires_grad and torch.is_grad_enabled():
+        # contiguous HERE, before the Function (as in reduce()): a copy made inside forward() would carry no history
+        return _WindowPool.apply(data.contiguous(), arg, plan, mode)
+    return launch_window_pool(plan, _plain(data), mode, arg)[0]
+
+
+def window_spread(grad: Tensor, arg: Optional[Tensor], plan: WindowPlan, mode: int) -> Tensor:
+    L.require_device(grad)
+    if grad.is_floating_point() and grad.requires_grad and torch.is_grad_enabled():
+        return _WindowSpread.apply(grad.contiguous(), arg, plan, mode)
+    return launch_window_spread(plan, _plain(grad), mode, arg)
+
+
 # ------------------------------------------------------------------ per-sequence argmax / argmin (an extension)
 _ARG_SUPPORT = 'argmax / argmin support'
 
