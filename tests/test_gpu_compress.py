@@ -311,3 +311,37 @@ def test_integer_and_bool_payloads_carry_no_graph():
             out = build('P', x, lens).compress(mask_like('P', mask, lens))
         assert not out.data.requires_grad and out.data.grad_fn is None and out.data.dtype == dtype
         assert same_bits(out.cat().data, compress_cat(x, mask, lens)[0])
+
+
+def test_one_read_back_of_the_new_lengths(monkeypatch):
+    """Device-only lengths [2, 0, 3], hidden (2,): compress on a C, an L and a P, and segment_compress, each read back
+    exactly once — the [3] new lengths — and leave the host copy, the kept counts, on the result's lengths."""
+    from torchrua_amd import _meta
+    lens, mask = LT([2, 0, 3]), torch.tensor([True, False, True, True, False])
+    x = draw((5, 2), F32, 27)
+    packed = build('P', x, lens)
+    cases = {                                                    # containers from their fields: no cast has read the lengths
+        'C': (ta.C(x.to(DEV), lens.to(DEV)), mask.to(DEV)),
+        'L': (ta.L(build('L', x, lens).data, lens.to(DEV)), mask_like('L', mask, lens)),
+        'P': (ta.P(packed.data, packed.batch_sizes.clone(), packed.sorted_indices, packed.unsorted_indices),
+              mask_like('P', mask, lens)),
+    }
+    torch.cuda.synchronize()
+    calls = []
+    real = _meta._read_back
+    monkeypatch.setattr(_meta, '_read_back', lambda t: (calls.append(tuple(t.shape)), real(t))[1])
+    for kind, (z, m) in cases.items():
+        del calls[:]
+        out = z.compress(m)
+        assert calls == [(3,)], (kind, calls)
+        new = _meta.pack_lens(out) if kind == 'P' else out.token_sizes
+        host = _meta._memo_get(new, 'host')
+        assert host is not None and not host.is_cuda and host.tolist() == [1, 0, 2], (kind, host)
+        assert calls == [(3,)], (kind, calls)
+        assert same_bits(out.cat().data, x[mask]), kind
+    del calls[:]
+    data, new = ta.segment_compress(x.to(DEV), mask.to(DEV), lens.to(DEV))
+    assert calls == [(3,)], calls
+    host = _meta._memo_get(new, 'host')
+    assert host is not None and not host.is_cuda and host.tolist() == [1, 0, 2]
+    assert same_bits(data, x[mask])

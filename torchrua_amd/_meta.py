@@ -120,6 +120,39 @@ def attach_host(token_sizes: Tensor, host: Tensor) -> None:
     _memo_put(token_sizes, 'host', host)
 
 
+# ---- the read-back policy of the operators that change raggedness (compress, unique, repeat, join, unjoin, window):
+#      lengths with a host copy get the operator's formula applied on the host; otherwise ONE read_back_rows
+def host_known(lens: Optional[Tensor]) -> bool:
+    """The host can tell the lengths without a read-back (None: a tensor part of a join, every length 1)."""
+    return lens is None or not lens.is_cuda or _memo_get(lens, 'host') is not None
+
+
+def host_array(lens: Optional[Tensor], B: int) -> np.ndarray:
+    if lens is None:
+        return np.ones(B, dtype=np.int64)
+    return host_lens(lens).detach().numpy().astype(np.int64, copy=False)
+
+
+def own_host(values: np.ndarray) -> Tensor:
+    """A host length vector the library owns (what attach_host wants), over an array the library made itself: no copy.
+    (The lengths a CALLER hands over go through private_host_copy.)"""
+    return torch.from_numpy(np.ascontiguousarray(values, dtype=np.int64))
+
+
+def attach_rows(host: Tensor, targets) -> Tensor:
+    """Row k of `host` (a vector: the one row) becomes the host copy of targets[k], in that tensor's dtype; None skips."""
+    for k, t in enumerate(targets):
+        if t is not None:
+            row = host if host.dim() == 1 else host[k]
+            attach_host(t, row if row.dtype == t.dtype else row.to(t.dtype))
+    return host
+
+
+def read_back_rows(buf: Tensor, targets) -> Tensor:
+    """The call's ONE blocking read-back: `buf` comes over once and its rows are attached to `targets`."""
+    return attach_rows(_read_back(buf), targets)
+
+
 def private_host_copy(host: Tensor) -> Tensor:
     """A copy of the caller's host lengths that the library owns (a loader that refills its buffer through
     numpy / data_ptr does not bump `_version`, so a borrowed mirror can go stale silently).  It comes from torch's

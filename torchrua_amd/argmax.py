@@ -26,7 +26,7 @@ from typing import NamedTuple
 
 from torchrua_amd import _lib as K
 from torchrua_amd import _ops as O
-from torchrua_amd.layout import C, L, P, R, T, Z, cat_lay, lay_hidden
+from torchrua_amd.layout import T, Z, cat_lay, install, lay_hidden
 
 __all__ = ['segment_argmax', 'segment_argmin', 'argmax', 'argmin', 'seq_max', 'seq_min']
 
@@ -76,8 +76,4 @@ def seq_min(sequence: Z) -> SeqExtreme:
     return SeqExtreme(*O.argreduce(sequence.data, lay, K.MIN, hidden))
 
 
-for _cls in (C, L, P, R):
-    _cls.argmax = argmax
-    _cls.argmin = argmin
-    _cls.max = seq_max
-    _cls.min = seq_min
+install(argmax=argmax, argmin=argmin, max=seq_max, min=seq_min)

@@ -49,48 +49,27 @@ and goes through this plan and move.
 from typing import Tuple
 
 import torch
-from torch import Tensor
 
 from torchrua_amd import _lib as K
 from torchrua_amd import _meta as M
 from torchrua_amd import _ops as O
 from torchrua_amd.core import result_like
-from torchrua_amd.layout import C, L, P, R, T, Z, cat_lay, lay_hidden
+from torchrua_amd.layout import T, Z, cat_lay, check_per_token, install, lay_hidden, lead_shape, side_payload
 
 __all__ = ['segment_compress', 'compress']
 
 
-def _check_mask(mask, lead_shape: Tuple[int, ...], data: Tensor, what: str) -> Tensor:
-    """The mask as a tensor, after the checks that need no device: bool, one value per token in the storage layout of
-    the token dimensions, on the payload's device."""
-    if not isinstance(mask, Tensor):
-        raise K.RuaError(f'{what}: the mask is a torch.bool tensor (or a container of the same type holding one); got '
-                         f'{type(mask).__name__}')
-    if mask.dtype != torch.bool:
-        raise K.RuaError(f'{what}: the mask has dtype {mask.dtype}; it must be torch.bool')
-    lead_shape = tuple(lead_shape)
-    if mask.dim() > len(lead_shape) and tuple(mask.shape[:len(lead_shape)]) == lead_shape:
-        raise K.RuaError(f'{what}: the mask has shape {tuple(mask.shape)}: hidden dimensions — it holds ONE value per '
-                         f'token, shape {lead_shape}')
-    if tuple(mask.shape) != lead_shape:
-        raise K.RuaError(f'{what}: the mask has shape {tuple(mask.shape)}; the token dimensions of the storage are '
-                         f'{lead_shape}')
-    if mask.device != data.device:
-        raise K.RuaError(f'{what}: the mask lives on {mask.device}, the payload on {data.device}')
-    return mask
-
-
-def _new_lengths(big: M.Lay, mask: Tensor) -> Tuple[Tensor, Tensor]:
+def _new_lengths(big: M.Lay, mask: T) -> Tuple[T, T]:
     """(rank, new lengths) of the plan, the lengths with their host copy attached: the call's ONE read-back."""
     rank, new_sizes = O.launch_compress_plan(big, mask)
-    M.attach_host(new_sizes, M._read_back(new_sizes))
+    M.read_back_rows(new_sizes, [new_sizes])
     return rank, new_sizes
 
 
 def segment_compress(tensor: T, mask: T, segment_sizes: T) -> Tuple[T, T]:
     """The rows of `tensor` [N, *hidden] where `mask` [N] is true, and how many every run of `segment_sizes` rows keeps
     (the argument order of segment_cumsum, plus the mask): (tensor [N', *hidden], new_sizes [S] int64)."""
-    mask = _check_mask(mask, tuple(tensor.shape[:1]), tensor, 'segment_compress')
+    mask = check_per_token('segment_compress', 'the mask', mask, torch.bool, tensor.shape[:1], tensor)
     K.require_device(tensor, mask, segment_sizes)
     big, hidden = cat_lay(tensor, segment_sizes), tuple(tensor.shape[1:])
     rank, new_sizes = _new_lengths(big, mask)
@@ -103,18 +82,12 @@ def compress(sequence: Z, mask) -> Z:
     """Keep the tokens where `mask` is true; the same container type and number of sequences.  See the module
     docstring."""
     data = sequence.data
-    if isinstance(mask, (C, L, P, R)):
-        if type(mask) is not type(sequence):
-            raise K.RuaError(f'compress: a mask given as a container must be a {type(sequence).__name__}; got '
-                             f'{type(mask).__name__}')
-        mask = mask.data
-    lead = 1 if isinstance(sequence, (C, P)) else 2
-    mask = _check_mask(mask, tuple(data.shape[:lead]), data, 'compress')
+    mask = side_payload(sequence, mask, 'compress: a mask given as a container must be a {want}; got {got}')
+    mask = check_per_token('compress', 'the mask', mask, torch.bool, lead_shape(sequence), data)
     big, hidden = lay_hidden(sequence)
     rank, new_sizes = _new_lengths(big, mask)
     small, shape, wrap = result_like(type(sequence), new_sizes, big.B, hidden, data)
     return wrap(O.compress(data, rank, small, big, hidden, shape, tuple(data.shape)))
 
 
-for _cls in (C, L, P, R):
-    _cls.compress = compress
+install(compress=compress)

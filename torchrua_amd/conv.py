@@ -38,20 +38,14 @@ Derivatives of any order exist (composed from the convolution and its weight gra
 Out of scope: a fused activation (SiLU), an initial state or a streaming decode cache, dilation and stride, K > 8,
 non-depthwise (channel-mixing) convolutions, weights that differ per sequence, integer payloads.
 """
-from typing import Optional, Tuple
+from typing import Optional
 
 from torch import Tensor
 
 from torchrua_amd import _ops as O
-from torchrua_amd.layout import C, L, P, R, T, Z, cat_lay, lay_hidden, rewrap
+from torchrua_amd.layout import T, Z, cat_lay, hidden_of, install, lay_hidden, rewrap
 
 __all__ = ['segment_causal_conv', 'causal_conv']
-
-
-def _hidden_of(sequence: Z) -> Tuple[int, ...]:
-    """The hidden dimensions of a container's payload (no device needed: the argument checks come first)."""
-    data = sequence.data
-    return tuple(data.shape[1:]) if isinstance(sequence, (C, P)) else tuple(data.shape[2:])
 
 
 def segment_causal_conv(tensor: T, weight: T, segment_sizes: T, bias: Optional[Tensor] = None,
@@ -66,10 +60,9 @@ def segment_causal_conv(tensor: T, weight: T, segment_sizes: T, bias: Optional[T
 def causal_conv(sequence: Z, weight: T, bias: Optional[Tensor] = None, reverse: bool = False) -> Z:
     """y_t = bias + sum_k weight[k] * x_(t-(K-1)+k) over the tokens of every sequence (the taps look ahead with
     `reverse`); the same container type.  See the module docstring."""
-    O._conv_args(sequence.data, weight, bias, _hidden_of(sequence))
+    O._conv_args(sequence.data, weight, bias, hidden_of(sequence))       # (no device needed: the argument checks come first)
     lay, hidden = lay_hidden(sequence)
     return rewrap(sequence, O.causal_conv(sequence.data, weight, bias, lay, reverse, hidden))
 
 
-for _cls in (C, L, P, R):
-    _cls.causal_conv = causal_conv
+install(causal_conv=causal_conv)

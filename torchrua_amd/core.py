@@ -16,7 +16,7 @@ from torch import Tensor
 from torchrua_amd import _lib as K
 from torchrua_amd import _meta as M
 from torchrua_amd import _ops as O
-from torchrua_amd.layout import C, L, P, R, T, Z, describe, lens_of
+from torchrua_amd.layout import C, L, P, R, T, Z, describe, hidden_of, lens_of
 
 __all__ = ['get_mask']
 # NOTE: _namespace.py gives this module the attributes `cast`, `get`, `set`, `view` (the reference's submodules of
@@ -228,17 +228,13 @@ R.right_view = _to_self
 
 
 # ------------------------------------------------------------------ core/cast.py
-def _hidden(z: Z) -> Tuple[int, ...]:
-    return tuple(z.data.shape[1:]) if isinstance(z, (C, P)) else tuple(z.data.shape[2:])
-
-
 def _to_cat(self: Union[L, P, R]) -> C:
     """core/cast.py:8-16: L/P/R -> C."""
     lens = lens_of(self)
     B = lens.numel()
     n = int(self.data.size(0)) if isinstance(self, P) else M.total_len(lens)
     dst = M.lay_cat(lens, B, n)
-    data = O.move(self.data, O.MovePlan(dst, describe(self), (n,) + _hidden(self), name='to_cat'))
+    data = O.move(self.data, O.MovePlan(dst, describe(self), (n,) + hidden_of(self), name='to_cat'))
     return C(data=data, token_sizes=lens)
 
 
@@ -252,7 +248,7 @@ def _to_padded(cls, kind):
         if isinstance(self, P) and 0 < M.row_bytes(self.data, 1) <= M.NARROW_ROW_BYTES:
             # narrow rows out of a PackedSequence: (rank x time) tiles over the destination's whole grid (tokens + fill)
             src = M.lay_pack(self, row_bytes=M.row_bytes(self.data, 1), full_grid_T=t)
-        plan = O.MovePlan(dst, src, (b, t) + _hidden(self), fill=fill_value,
+        plan = O.MovePlan(dst, src, (b, t) + hidden_of(self), fill=fill_value,
                           name='to_left' if kind == K.LEFT else 'to_right')
         return cls(data=O.move(self.data, plan), token_sizes=lens)
     return cast
@@ -267,7 +263,7 @@ def _to_pack(self: Union[C, L, R]) -> P:
     M.adopt_pack(shell, lens, boff, bsz_dev)
     dst = M.lay_pack(shell, lens=lens, boff=boff, T=batch_sizes.numel(), n_rows=n,
                      row_bytes=M.row_bytes(self.data, 1 if isinstance(self, C) else 2))
-    data = O.move(self.data, O.MovePlan(dst, describe(self), (n,) + _hidden(self), name='to_pack'))
+    data = O.move(self.data, O.MovePlan(dst, describe(self), (n,) + hidden_of(self), name='to_pack'))
     return shell._replace(data=data)
 
 
@@ -415,11 +411,11 @@ def _getitem(cls):
             return key._replace(data=_gather_flat(self.raw(), key.data))
         if _is_ptr_pair(key):                       # (batch_ptr, token_ptr)
             bp, tp = key
-            shape = tuple(bp.shape) + _hidden(self)
+            shape = tuple(bp.shape) + hidden_of(self)
             plan = O.MovePlan(M.lay_list(bp.reshape(-1), tp.reshape(-1)), describe(self), shape, name='getitem')
             if self.data.requires_grad and torch.is_grad_enabled():
                 k = (bp.reshape(-1), tp.reshape(-1))
-                return O._ListGather.apply(self.data, plan, lambda: _flat_rows(self, k), len(self.data.shape) - len(_hidden(self)))
+                return O._ListGather.apply(self.data, plan, lambda: _flat_rows(self, k), len(self.data.shape) - len(hidden_of(self)))
             return O.launch_move(plan, self.data)
         if isinstance(key, Tensor):
             return _gather_flat(self.raw(), key)
@@ -436,7 +432,7 @@ def _setitem(cls):
             bp, tp = key[0].reshape(-1), key[1].reshape(-1)
             if not self.data.is_contiguous():
                 raise K.RuaError('__setitem__ needs contiguous storage')
-            hidden = _hidden(self)
+            hidden = hidden_of(self)
             if _needs_autograd(self.data, value):
                 # autograd has to see the write: the same scatter, recorded (_ops._ScatterRows)
                 if _is_leaf_write(self.data):

@@ -19,7 +19,7 @@ z.cat().cumsum()) and `reverse` is the same association order on the mirrored to
 z.cumsum(reverse=True)).  Autograd saves nothing: the backward is the scan in the other direction.
 """
 from torchrua_amd import _ops as O
-from torchrua_amd.layout import C, L, P, R, T, Z, cat_lay, lay_hidden, rewrap
+from torchrua_amd.layout import T, Z, cat_lay, install, lay_hidden, rewrap
 
 __all__ = ['segment_cumsum', 'cumsum']
 
@@ -35,5 +35,4 @@ def cumsum(sequence: Z, reverse: bool = False) -> Z:
     return rewrap(sequence, O.cumsum(sequence.data, lay, reverse, hidden))
 
 
-for _cls in (C, L, P, R):
-    _cls.cumsum = cumsum
+install(cumsum=cumsum)

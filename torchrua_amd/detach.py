@@ -8,7 +8,7 @@ from typing import List
 import torch
 
 from torchrua_amd import _meta as M
-from torchrua_amd.layout import C, L, P, R, T, Z
+from torchrua_amd.layout import C, L, P, R, T, Z, install
 
 __all__ = []  # methods are attached to the layout classes
 
@@ -35,5 +35,4 @@ def _tolist(self: Z):
 C.split = P.split = _split_dense
 L.split = _split_left
 R.split = _split_right
-for _cls in (C, L, P, R):
-    _cls.tolist = _tolist
+install(tolist=_tolist)

@@ -55,7 +55,7 @@ without a graph.
 `.split` exists on the containers with another meaning (the list of sequences); hence `unjoin`.
 """
 from numbers import Integral
-from typing import List, Optional, Sequence, Tuple, Union
+from typing import List, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -65,37 +65,12 @@ from torchrua_amd import _lib as K
 from torchrua_amd import _meta as M
 from torchrua_amd import _ops as O
 from torchrua_amd.core import result_like
-from torchrua_amd.layout import C, L, P, R, T, Z, lay_hidden, lens_of
+from torchrua_amd.layout import (NAMES, C, T, Z, cls_of, device_tensors, hidden_of, install, is_container, lay_hidden, lens_lay,
+                                 lens_of, n_seq, require_container)
 
 __all__ = ['join', 'unjoin', 'segment_join', 'segment_unjoin']
 
 MAX_PARTS = K.JOIN_MAX_PARTS
-_NAMES = {C: 'CattedSequence', L: 'LeftAlignedSequence', P: 'PackedSequence', R: 'RightAlignedSequence'}
-
-
-def _is_container(x) -> bool:
-    return isinstance(x, (C, L, P, R))
-
-
-def _cls(z):
-    return next(c for c in (C, L, P, R) if isinstance(z, c))
-
-
-def _n_seq(z) -> int:
-    return M.pack_nseq(z) if isinstance(z, P) else int(z.token_sizes.size(0))
-
-
-def _hidden(z) -> Tuple[int, ...]:
-    return tuple(z.data.shape[1:]) if isinstance(z, (C, P)) else tuple(z.data.shape[2:])
-
-
-def _tensors(z) -> List[Tensor]:
-    """Every tensor of a part that has to live on the device."""
-    if isinstance(z, Tensor):
-        return [z]
-    if isinstance(z, P):
-        return [t for t in (z.data, z.sorted_indices, z.unsorted_indices) if t is not None]
-    return [z.data, z.token_sizes]
 
 
 def _same_device(tensors: Sequence[Tensor], what: str) -> None:
@@ -106,25 +81,25 @@ def _same_device(tensors: Sequence[Tensor], what: str) -> None:
 
 def _check_parts(sequences) -> Tuple[list, type, int, Tuple[int, ...]]:
     """The parts as a list, the result type, B and the hidden shape — after every check that needs no device."""
-    if _is_container(sequences) or isinstance(sequences, Tensor) or not isinstance(sequences, (list, tuple)):
+    if is_container(sequences) or isinstance(sequences, Tensor) or not isinstance(sequences, (list, tuple)):
         raise K.RuaError(f'join takes a list of parts; got {type(sequences).__name__} (one part is join([z]), or z.join())')
     parts = list(sequences)
     if not 1 <= len(parts) <= MAX_PARTS:
         raise K.RuaError(f'join takes 1 to {MAX_PARTS} parts; got {len(parts)}')
     for k, x in enumerate(parts):
-        if not _is_container(x) and not isinstance(x, Tensor):
+        if not is_container(x) and not isinstance(x, Tensor):
             raise K.RuaError(f'join: part {k} is a {type(x).__name__}; a part is a container or a tensor [B, *hidden]')
-    containers = [x for x in parts if _is_container(x)]
+    containers = [x for x in parts if is_container(x)]
     if not containers:
         raise K.RuaError('join: no container among the parts — at least one part must be a C / L / P / R; it fixes the '
                          'result type')
-    cls = _cls(containers[0])
+    cls = cls_of(containers[0])
     for x in containers:
-        if _cls(x) is not cls:
-            raise K.RuaError(f'join: mixed container types in one call ({_NAMES[cls]} and {_NAMES[_cls(x)]}); cast the '
+        if cls_of(x) is not cls:
+            raise K.RuaError(f'join: mixed container types in one call ({NAMES[cls]} and {NAMES[cls_of(x)]}); cast the '
                              f'parts to one type first')
     first = containers[0]
-    B, hidden, dtype = _n_seq(first), _hidden(first), first.data.dtype
+    B, hidden, dtype = n_seq(first), hidden_of(first), first.data.dtype
     for k, x in enumerate(parts):
         if isinstance(x, Tensor):
             if x.dim() < 1 or tuple(x.shape) != (B,) + hidden:
@@ -132,16 +107,16 @@ def _check_parts(sequences) -> Tuple[list, type, int, Tuple[int, ...]]:
                                  f'per sequence, shape [B, *hidden] = {(B,) + hidden}')
             data = x
         else:
-            if _n_seq(x) != B:
-                raise K.RuaError(f'join: part {k} has {_n_seq(x)} sequences, the first container has {B}: the number of '
+            if n_seq(x) != B:
+                raise K.RuaError(f'join: part {k} has {n_seq(x)} sequences, the first container has {B}: the number of '
                                  f'sequences B differs')
-            if _hidden(x) != hidden:
-                raise K.RuaError(f'join: part {k} has hidden shape {_hidden(x)}, the first container has {hidden}: the '
+            if hidden_of(x) != hidden:
+                raise K.RuaError(f'join: part {k} has hidden shape {hidden_of(x)}, the first container has {hidden}: the '
                                  f'hidden shape differs')
             data = x.data
         if data.dtype != dtype:
             raise K.RuaError(f'join: part {k} has dtype {data.dtype}, the first container has {dtype}: the dtype differs')
-    _same_device([t for x in parts for t in _tensors(x)], 'join')
+    _same_device([t for x in parts for t in device_tensors(x)], 'join')
     return parts, cls, B, hidden
 
 
@@ -161,38 +136,12 @@ def _check_sizes(sizes, B: int) -> list:
     return sizes
 
 
-def _host_known(lens: Optional[Tensor]) -> bool:
-    """The host can tell the lengths without a read-back (None: a tensor part, every length 1)."""
-    return lens is None or not lens.is_cuda or M._memo_get(lens, 'host') is not None
-
-
-def _host_array(lens: Optional[Tensor], B: int) -> np.ndarray:
-    if lens is None:
-        return np.ones(B, dtype=np.int64)
-    return M.host_lens(lens).detach().numpy().astype(np.int64, copy=False)
-
-
-def _own_host(values: np.ndarray) -> Tensor:
-    """A host length vector the library owns (what attach_host wants)."""
-    return torch.from_numpy(np.ascontiguousarray(values, dtype=np.int64))
-
-
-def _tensor_lay(B: int) -> M.Lay:
-    """A tensor part [B, *hidden]: LEFT with T_phys = 1, no length vector, every length 1."""
-    return M.lay_padded(K.LEFT, None, B, 1, 1, len_add=1)
-
-
-def _part_lay(x, B: int) -> M.Lay:
-    return _tensor_lay(B) if isinstance(x, Tensor) else lay_hidden(x)[0]
-
-
-def _lens_lay(x, B: int) -> M.Lay:
-    """The part's layout for the LENGTH launch alone, built without a read-back: a right-aligned part whose longest
-    sequence the host does not know yet is described with T_log = T_phys (only the clamp reads it there)."""
-    if isinstance(x, R) and not _host_known(x.token_sizes):
-        t = int(x.data.size(1))
-        return M.lay_padded(K.RIGHT, x.token_sizes, B, t, t)
-    return _part_lay(x, B)
+def _part_lay(x, B: int, lens_only: bool = False) -> M.Lay:
+    """A part's layout (lens_only: for the length launch alone, layout.lens_lay).  A tensor part [B, *hidden] is LEFT
+    with T_phys = 1, no length vector, every length 1."""
+    if isinstance(x, Tensor):
+        return M.lay_padded(K.LEFT, None, B, 1, 1, len_add=1)
+    return lens_lay(x) if lens_only else lay_hidden(x)[0]
 
 
 def join(sequences: Sequence[Union[Z, T]]) -> Z:
@@ -200,16 +149,16 @@ def join(sequences: Sequence[Union[Z, T]]) -> Z:
     docstring."""
     parts, cls, B, hidden = _check_parts(sequences)
     datas = [x if isinstance(x, Tensor) else x.data for x in parts]
-    dev = K.require_device(*[t for x in parts for t in _tensors(x)])
+    dev = K.require_device(*[t for x in parts for t in device_tensors(x)])
     lens = [None if isinstance(x, Tensor) else lens_of(x) for x in parts]
     n = None
-    if all(_host_known(v) for v in lens):
+    if all(M.host_known(v) for v in lens):
         # every part's lengths have a host copy: added on the host — no read-back for any result type
         lays = [_part_lay(x, B) for x in parts]
         sizes = O.launch_join_lens(lays, dev)[0]
         # (the device adds the lengths CLAMPED to their storages, the host the lengths as given: the same numbers for
         # well-formed containers — lengths within their storages — which is what every host mirror here assumes)
-        M.attach_host(sizes, _own_host(sum(_host_array(v, B) for v in lens)))
+        M.attach_host(sizes, M.own_host(sum(M.host_array(v, B) for v in lens)))
     elif cls is C:
         # a C never synchronises: the storage is the sum of the parts' storages, the offsets come from the device scan
         # (a part whose storage holds more rows than its lengths add up to leaves spare rows at the end: zeros)
@@ -218,13 +167,9 @@ def join(sequences: Sequence[Union[Z, T]]) -> Z:
         n = sum(int(d.size(0)) for d in datas)
     else:
         # ONE read-back: the new lengths and the parts' own, all attached — the casts that follow read nothing
-        buf = O.launch_join_lens([_lens_lay(x, B) for x in parts], dev, want_parts=True)
-        host = M._read_back(buf)
+        buf = O.launch_join_lens([_part_lay(x, B, lens_only=True) for x in parts], dev, want_parts=True)
         sizes = buf[0]
-        M.attach_host(sizes, host[0])
-        for k, v in enumerate(lens):
-            if not _host_known(v):
-                M.attach_host(v, host[k + 1].to(v.dtype))
+        M.read_back_rows(buf, [sizes] + [None if M.host_known(v) else v for v in lens])
         lays = [_part_lay(x, B) for x in parts]
     joined, shape, wrap = result_like(cls, sizes, B, hidden, datas[0], n)
     plan = O.JoinPlan(joined, lays, hidden, shape, [tuple(d.shape) for d in datas])
@@ -233,38 +178,32 @@ def join(sequences: Sequence[Union[Z, T]]) -> Z:
 
 def unjoin(sequence: Z, sizes: Sequence[Union[T, int]]) -> List[Z]:
     """Cut every sequence at the given sizes; one container of the same type per size.  See the module docstring."""
-    if not _is_container(sequence):
-        raise K.RuaError(f'unjoin takes a container (C / L / P / R); got {type(sequence).__name__}')
-    cls, B, hidden = _cls(sequence), _n_seq(sequence), _hidden(sequence)
+    cls, B, hidden = require_container(sequence, 'unjoin'), n_seq(sequence), hidden_of(sequence)
     sizes = _check_sizes(sizes, B)
+    n = len(sizes)
     given = [s for s in sizes if isinstance(s, Tensor)]
-    _same_device(_tensors(sequence) + given, 'unjoin')
-    dev = K.require_device(*(_tensors(sequence) + given))
+    _same_device(device_tensors(sequence) + given, 'unjoin')
+    dev = K.require_device(*(device_tensors(sequence) + given))
     own = lens_of(sequence)
-    if _host_known(own) and all(not isinstance(s, Tensor) or _host_known(s) for s in sizes):
+    if M.host_known(own) and all(not isinstance(s, Tensor) or M.host_known(s) for s in sizes):
         joined, _ = lay_hidden(sequence)
         buf = O.launch_unjoin_lens(joined, sizes, dev)
-        rest = np.maximum(_host_array(own, B), 0)
+        rest = np.maximum(M.host_array(own, B), 0)
         rows = []
         for s in sizes:
-            want = _host_array(s, B) if isinstance(s, Tensor) else np.full(B, int(s), dtype=np.int64)
+            want = M.host_array(s, B) if isinstance(s, Tensor) else np.full(B, int(s), dtype=np.int64)
             rows.append(np.minimum(np.maximum(want, 0), rest))
             rest = rest - rows[-1]
-        host = _own_host(np.stack(rows))
+        part_sizes = [buf[k] for k in range(n)]   # (ONE tensor object per part: the memo lives on the object)
+        M.attach_rows(M.own_host(np.stack(rows)), part_sizes)
     else:
         # the call's ONE read-back: the parts' lengths size their storages; the container's own lengths come over
         # with them and are attached, so a right-aligned batch is described (its longest sequence) without another
-        n = len(sizes)
-        buf = O.launch_unjoin_lens(_lens_lay(sequence, B), sizes, dev, want_own=not _host_known(own))
-        host = M._read_back(buf)
-        if not _host_known(own):
-            M.attach_host(own, host[n].to(own.dtype))
+        buf = O.launch_unjoin_lens(lens_lay(sequence), sizes, dev, want_own=not M.host_known(own))
+        part_sizes = [buf[k] for k in range(n)]
+        M.read_back_rows(buf, part_sizes + [None if M.host_known(own) else own])
         joined, _ = lay_hidden(sequence)
-    plans = []
-    for k in range(len(sizes)):
-        part_sizes = buf[k]                       # (ONE tensor object per part: the memo lives on the object)
-        M.attach_host(part_sizes, host[k])
-        plans.append(result_like(cls, part_sizes, B, hidden, sequence.data))
+    plans = [result_like(cls, s, B, hidden, sequence.data) for s in part_sizes]
     plan = O.JoinPlan(joined, [p[0] for p in plans], hidden, tuple(sequence.data.shape), [p[1] for p in plans])
     outs = O.unjoin(sequence.data, plan)
     return [p[2](out) for p, out in zip(plans, outs)]
@@ -294,6 +233,4 @@ def _unjoin_method(self: Z, *sizes) -> List[Z]:
     return unjoin(self, list(sizes))
 
 
-for _c in (C, L, P, R):
-    _c.join = _join_method
-    _c.unjoin = _unjoin_method
+install(join=_join_method, unjoin=_unjoin_method)

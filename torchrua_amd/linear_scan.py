@@ -41,7 +41,7 @@ from torch import Tensor
 
 from torchrua_amd import _lib as K
 from torchrua_amd import _ops as O
-from torchrua_amd.layout import C, L, P, R, T, Z, cat_lay, lay_hidden, rewrap
+from torchrua_amd.layout import T, Z, cat_lay, install, lay_hidden, rewrap, side_payload
 
 __all__ = ['segment_linear_scan', 'linear_scan']
 
@@ -52,26 +52,16 @@ def segment_linear_scan(tensor: T, gate, segment_sizes: T, reverse: bool = False
     return O.linear_scan(tensor, gate, cat_lay(tensor, segment_sizes), reverse, tuple(tensor.shape[1:]))
 
 
-def _gate_data(sequence: Z, gate):
-    """The gate as a tensor (of a container: its payload; the container types must agree) or a Python number."""
-    if isinstance(gate, (C, L, P, R)):
-        if type(gate) is not type(sequence):
-            raise K.RuaError(f'linear_scan: the gate is a {type(gate).__name__}, the sequence a '
-                             f'{type(sequence).__name__}; cast one of them first')
-        return gate.data
-    return gate
-
-
 def linear_scan(sequence: Z, gate, reverse: bool = False) -> Z:
     """h_t = gate_t * h_(t-1) + x_t over the tokens of every sequence (h_t = gate_t * h_(t+1) + x_t with `reverse`);
     the same container type.  See the module docstring for the gate forms and the documented limit."""
     K.require_device(sequence.data)
-    gate = _gate_data(sequence, gate)
+    # the gate as a tensor (of a container: its payload; the container types must agree) or a Python number
+    gate = side_payload(sequence, gate, 'linear_scan: the gate is a {got}, the sequence a {want}; cast one of them first')
     if isinstance(gate, Tensor):
         K.require_device(sequence.data, gate)
     lay, hidden = lay_hidden(sequence)
     return rewrap(sequence, O.linear_scan(sequence.data, gate, lay, reverse, hidden))
 
 
-for _cls in (C, L, P, R):
-    _cls.linear_scan = linear_scan
+install(linear_scan=linear_scan)

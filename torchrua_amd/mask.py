@@ -4,7 +4,7 @@ rua_mask) — an attention-mask producer usually sits right behind a pad, on gri
 import torch
 
 from torchrua_amd.core import _mask_grid
-from torchrua_amd.layout import C, L, P, R, T, Z, lens_of
+from torchrua_amd.layout import T, Z, install, lens_of
 
 __all__ = []  # methods are attached to the layout classes
 
@@ -29,7 +29,4 @@ def _flavoured(name: str):
     return method
 
 
-for _cls in (C, L, P, R):
-    _cls.mask = _mask
-    for _name in _FLAVOURS:
-        setattr(_cls, _name, _flavoured(_name))
+install(mask=_mask, **{_name: _flavoured(_name) for _name in _FLAVOURS})

@@ -29,7 +29,7 @@ Out of scope: std (`var(z).sqrt()` on [B, H] is cheap), an affine weight and bia
 from typing import Tuple
 
 from torchrua_amd import _ops as O
-from torchrua_amd.layout import C, L, P, R, T, Z, cat_lay, lay_hidden, rewrap
+from torchrua_amd.layout import T, Z, cat_lay, install, lay_hidden, rewrap
 
 __all__ = ['segment_var_mean', 'segment_var', 'segment_standardize', 'var_mean', 'var', 'standardize']
 
@@ -68,7 +68,4 @@ def standardize(sequence: Z, eps: float = 1e-5, correction: int = 0) -> Z:
     return rewrap(sequence, O.standardize(sequence.data, lay, hidden, eps, correction))
 
 
-for _cls in (C, L, P, R):
-    _cls.var_mean = var_mean
-    _cls.var = var
-    _cls.standardize = standardize
+install(var_mean=var_mean, var=var, standardize=standardize)

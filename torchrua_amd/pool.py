@@ -32,7 +32,7 @@ from torch import Tensor
 
 from torchrua_amd import _lib as K
 from torchrua_amd import _ops as O
-from torchrua_amd.layout import C, L, P, R, T, Z, cat_lay, lay_hidden
+from torchrua_amd.layout import P, T, Z, cat_lay, install, lay_hidden, n_lead, side_payload
 
 __all__ = ['segment_softmax_pool', 'softmax_pool']
 
@@ -62,14 +62,10 @@ def segment_softmax_pool(tensor: T, scores: T, segment_sizes: T) -> T:
 
 def _scores_data(sequence: Z, scores) -> Tensor:
     """The scores as a tensor (of a container: its payload; the container types must agree)."""
-    if isinstance(scores, (C, L, P, R)):
-        if type(scores) is not type(sequence):
-            raise K.RuaError(f'softmax_pool: the scores are a {type(scores).__name__}, the sequence a '
-                             f'{type(sequence).__name__}; cast one of them first')
-        if isinstance(sequence, P) and not torch.equal(scores.batch_sizes, sequence.batch_sizes):
-            raise K.RuaError('softmax_pool: the scores and the sequence are PackedSequences with different batch_sizes')
-        return scores.data
-    return scores
+    data = side_payload(sequence, scores, 'softmax_pool: the scores are a {got}, the sequence a {want}; cast one of them first')
+    if data is not scores and isinstance(sequence, P) and not torch.equal(scores.batch_sizes, sequence.batch_sizes):
+        raise K.RuaError('softmax_pool: the scores and the sequence are PackedSequences with different batch_sizes')
+    return data
 
 
 def softmax_pool(sequence: Z, scores) -> T:
@@ -78,10 +74,9 @@ def softmax_pool(sequence: Z, scores) -> T:
     data = sequence.data
     K.require_device(data)
     scores = _scores_data(sequence, scores)
-    G = _score_columns(data, scores, 1 if isinstance(sequence, (C, P)) else 2)
+    G = _score_columns(data, scores, n_lead(sequence))
     lay, hidden = lay_hidden(sequence)
     return O.softmax_pool(data, scores, lay, hidden, G)
 
 
-for _cls in (C, L, P, R):
-    _cls.softmax_pool = softmax_pool
+install(softmax_pool=softmax_pool)

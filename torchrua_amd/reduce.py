@@ -18,7 +18,7 @@ from torch.autograd.function import once_differentiable
 from torchrua_amd import _lib as K
 from torchrua_amd import _meta as M
 from torchrua_amd import _ops as O
-from torchrua_amd.layout import C, P, T, Z, describe, lens_of
+from torchrua_amd.layout import C, P, T, Z, describe, hidden_of, lens_of
 
 __all__ = [
     'segment_max', 'segment_min', 'segment_sum', 'segment_mean', 'segment_prod', 'segment_logsumexp',
@@ -78,8 +78,7 @@ def segment_last(tensor: T, segment_sizes: T) -> T:
 
 # ------------------------------------------------------------------ reduce over sequences of any layout
 def _reduce_seq(sequence: Z, op: int) -> T:
-    hidden = tuple(sequence.data.shape[1:]) if isinstance(sequence, (C, P)) else tuple(sequence.data.shape[2:])
-    return O.reduce(sequence.data, describe(sequence), op, hidden, lens_of(sequence))
+    return O.reduce(sequence.data, describe(sequence), op, hidden_of(sequence), lens_of(sequence))
 
 
 def reduce_sum(sequence: Z) -> T:
@@ -336,10 +335,10 @@ def pack_reduce(sequence: Z, op: str = 'sum', fused: bool = None):
     payload once instead of twice (2*N*H*e + B*H*e bytes instead of 3*N*H*e + B*H*e).  Falls back to the
     two-kernel form when autograd is recording, for a PackedSequence input, or for rows that are not a
     multiple of 16 bytes."""
-    from torchrua_amd.core import _hidden, _pack_meta
+    from torchrua_amd.core import _pack_meta
     code = _OPS[op]
     data = sequence.data
-    hidden = _hidden(sequence)
+    hidden = hidden_of(sequence)
     H = 1
     for d in hidden:
         H *= d

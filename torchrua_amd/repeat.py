@@ -68,14 +68,14 @@ from torchrua_amd import _lib as K
 from torchrua_amd import _meta as M
 from torchrua_amd import _ops as O
 from torchrua_amd.core import result_like
-from torchrua_amd.layout import C, L, P, R, T, Z, cat_lay, lay_hidden, lens_of
+from torchrua_amd.layout import C, T, Z, cat_lay, check_per_token, install, lay_hidden, lead_shape, lens_of, side_payload
 
 __all__ = ['segment_repeat_interleave', 'repeat_interleave']
 
 MAX_COUNT = 2 ** 31 - 1
 
 
-def _check_repeats(repeats, lead_shape: Tuple[int, ...], data: Tensor, what: str) -> Union[int, Tensor]:
+def _check_repeats(repeats, shape: Tuple[int, ...], data: Tensor, what: str) -> Union[int, Tensor]:
     """The counts as an int or a tensor, after the checks that need no device: int64, one value per token in the
     storage layout of the token dimensions, on the payload's device; an int is not negative."""
     if isinstance(repeats, int) and not isinstance(repeats, bool):
@@ -84,23 +84,9 @@ def _check_repeats(repeats, lead_shape: Tuple[int, ...], data: Tensor, what: str
         if repeats > MAX_COUNT:
             raise K.RuaError(f'{what}: repeats is {repeats}; a count above 2^31 - 1 is invalid')
         return repeats
-    if not isinstance(repeats, Tensor):
-        raise K.RuaError(f'{what}: repeats is a torch.int64 tensor (or a container of the same type holding one) or an '
-                         f'int; got {type(repeats).__name__}')
-    if repeats.dtype == torch.bool:
+    if isinstance(repeats, Tensor) and repeats.dtype == torch.bool:
         raise K.RuaError(f'{what}: repeats has dtype torch.bool; keeping tokens by a mask is compress(mask)')
-    if repeats.dtype != torch.int64:
-        raise K.RuaError(f'{what}: repeats has dtype {repeats.dtype}; it must be torch.int64')
-    lead_shape = tuple(lead_shape)
-    if repeats.dim() > len(lead_shape) and tuple(repeats.shape[:len(lead_shape)]) == lead_shape:
-        raise K.RuaError(f'{what}: repeats has shape {tuple(repeats.shape)}: hidden dimensions — it holds ONE count per '
-                         f'token, shape {lead_shape}')
-    if tuple(repeats.shape) != lead_shape:
-        raise K.RuaError(f'{what}: repeats has shape {tuple(repeats.shape)}; the token dimensions of the storage are '
-                         f'{lead_shape}')
-    if repeats.device != data.device:
-        raise K.RuaError(f'{what}: repeats lives on {repeats.device}, the payload on {data.device}')
-    return repeats
+    return check_per_token(what, 'repeats', repeats, torch.int64, shape, data, or_form=', or an int')
 
 
 def _too_long(new_sizes: Tensor, what: str) -> None:
@@ -115,9 +101,8 @@ def _new_lengths(src: M.Lay, lens: Tensor, repeats: Union[int, Tensor], what: st
     when `lens` carries one; nothing is launched for the table and nothing is read back."""
     if isinstance(repeats, int):
         new_sizes = M._as_lens(lens) * repeats
-        host = lens if not lens.is_cuda else M._memo_get(lens, 'host')
-        if host is not None:
-            M.attach_host(new_sizes, M.private_host_copy(host * repeats))
+        if M.host_known(lens):
+            M.attach_host(new_sizes, M.private_host_copy(M.host_lens(lens) * repeats))
         _too_long(new_sizes, what)
         return None, None, repeats, new_sizes
     counts = O._plain(repeats).contiguous()
@@ -152,13 +137,8 @@ def repeat_interleave(sequence: Z, repeats) -> Z:
     """Every token `repeats[b, t]` (or `repeats`, an int) times in its own sequence; the same container type and number
     of sequences.  See the module docstring."""
     data = sequence.data
-    if isinstance(repeats, (C, L, P, R)):
-        if type(repeats) is not type(sequence):
-            raise K.RuaError(f'repeat_interleave: repeats given as a container must be a {type(sequence).__name__}; got '
-                             f'{type(repeats).__name__}')
-        repeats = repeats.data
-    lead = 1 if isinstance(sequence, (C, P)) else 2
-    repeats = _check_repeats(repeats, tuple(data.shape[:lead]), data, 'repeat_interleave')
+    repeats = side_payload(sequence, repeats, 'repeat_interleave: repeats given as a container must be a {want}; got {got}')
+    repeats = _check_repeats(repeats, lead_shape(sequence), data, 'repeat_interleave')
     src, hidden = lay_hidden(sequence)
     first, counts, uniform, new_sizes = _new_lengths(src, lens_of(sequence), repeats, 'repeat_interleave')
     # (a C and an int count: N * r rows, known without a look at the lengths — a C result never synchronises)
@@ -172,5 +152,4 @@ def repeat_interleave(sequence: Z, repeats) -> Z:
     return wrap(O.repeat(data, first, counts, uniform, dst, src, hidden, shape, tuple(data.shape)))
 
 
-for _cls in (C, L, P, R):
-    _cls.repeat_interleave = repeat_interleave
+install(repeat_interleave=repeat_interleave)

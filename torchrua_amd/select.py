@@ -11,8 +11,8 @@ from torch import Tensor
 from torchrua_amd import _lib as K
 from torchrua_amd import _meta as M
 from torchrua_amd import _ops as O
-from torchrua_amd.core import _hidden, pack_reference_order
-from torchrua_amd.layout import C, L, P, R, Z, describe, lens_of
+from torchrua_amd.core import pack_reference_order
+from torchrua_amd.layout import C, L, P, R, Z, describe, hidden_of, install, lens_of
 
 
 __all__ = []  # methods are attached to the layout classes
@@ -23,7 +23,7 @@ def _cat_head(self: C, n: int) -> C:
     """select/head.py:6-16 (.tolist() + 2B split views + cat in the reference)."""
     B = self.token_sizes.size(0)
     dst = M.lay_cat(None, B, B * n, len_add=n)
-    data = O.move(self.data, O.MovePlan(dst, describe(self), (B * n,) + _hidden(self), name='head'))
+    data = O.move(self.data, O.MovePlan(dst, describe(self), (B * n,) + hidden_of(self), name='head'))
     return C(data=data, token_sizes=torch.full_like(self.token_sizes, fill_value=n))
 
 
@@ -45,7 +45,7 @@ def _right_head(self: R, n: int) -> R:
     B, t_phys = self.data.shape[:2]
     src = M.lay_padded(K.RIGHT, self.token_sizes, B, t_phys, t_phys)
     dst = M.lay_padded(K.RIGHT, None, B, n, n, len_add=n)
-    data = O.move(self.data, O.MovePlan(dst, src, (B, n) + _hidden(self), name='head'))
+    data = O.move(self.data, O.MovePlan(dst, src, (B, n) + hidden_of(self), name='head'))
     return R(data=data, token_sizes=torch.full_like(self.token_sizes, fill_value=n))
 
 
@@ -61,11 +61,10 @@ def _last(self: Z) -> Tensor:
     lens = lens_of(self)
     B = lens.numel()
     dst = M.lay_padded(K.LEFT, None, B, 1, 1, len_add=1)
-    return O.move(self.data, O.MovePlan(dst, describe(self), (B,) + _hidden(self), tmap=K.T_REV_S, name='last'))
+    return O.move(self.data, O.MovePlan(dst, describe(self), (B,) + hidden_of(self), tmap=K.T_REV_S, name='last'))
 
 
-for _cls in (C, L, P, R):
-    _cls.last = _last
+install(last=_last)
 
 
 # ------------------------------------------------------------------ roll / rev
@@ -81,7 +80,7 @@ def _same_layout_move(self: Z, tmap: int, arg: int, name: str, pad_row: int = -1
         # (layout/left.py:73-77); rev reads data[b, ...] with the physical stride (select/rev.py:25-41)
         stride = t if logical_stride else int(self.data.size(1))
         src = M.lay_padded(kind, self.token_sizes, b, stride, t)
-        plan = O.MovePlan(dst, src, (b, t) + _hidden(self), tmap, arg, fill=0, pad_row=pad_row, name=name)
+        plan = O.MovePlan(dst, src, (b, t) + hidden_of(self), tmap, arg, fill=0, pad_row=pad_row, name=name)
     else:
         lay = describe(self)
         order = pack_reference_order(self) if isinstance(self, P) else None
@@ -130,8 +129,7 @@ def _rev(self: Z):
     return _same_layout_move(self, K.T_REV_S, 0, 'rev')
 
 
-for _cls in (C, L, P, R):
-    _cls.rev = _rev
+install(rev=_rev)
 
 
 # ------------------------------------------------------------------ trunc (select/trunc.py)
@@ -141,7 +139,7 @@ def _cat_trunc(self: C, trunc: Tuple[int, int]) -> C:
     B = self.token_sizes.size(0)
     n = int(self.data.size(0)) - B * (a + b)
     dst = M.lay_cat(self.token_sizes, B, n, len_add=-(a + b))
-    data = O.move(self.data, O.MovePlan(dst, describe(self), (n,) + _hidden(self), K.T_SHIFT, a, name='trunc'))
+    data = O.move(self.data, O.MovePlan(dst, describe(self), (n,) + hidden_of(self), K.T_SHIFT, a, name='trunc'))
     return C(data=data, token_sizes=self.token_sizes - a - b)
 
 
@@ -152,7 +150,7 @@ def _pack_trunc(self: P, trunc: Tuple[int, int]) -> P:
     n = int(batch_sizes.sum())
     shell = self._replace(batch_sizes=batch_sizes)
     dst = M.lay_pack(shell, lens=M.pack_lens(self), len_add=-(a + b), n_rows=n)
-    data = O.move(self.data, O.MovePlan(dst, describe(self), (n,) + _hidden(self), K.T_SHIFT, a, name='trunc'))
+    data = O.move(self.data, O.MovePlan(dst, describe(self), (n,) + hidden_of(self), K.T_SHIFT, a, name='trunc'))
     return shell._replace(data=data)
 
 

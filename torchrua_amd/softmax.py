@@ -16,7 +16,7 @@ storage shape and dtype of the input; padding rows of an L / R result are zeros.
 bit for bit: z.softmax().cat() == z.cat().softmax().  Autograd saves only y.
 """
 from torchrua_amd import _ops as O
-from torchrua_amd.layout import C, L, P, R, T, Z, cat_lay, lay_hidden, rewrap
+from torchrua_amd.layout import T, Z, cat_lay, install, lay_hidden, rewrap
 
 __all__ = ['segment_softmax', 'segment_log_softmax', 'softmax', 'log_softmax']
 
@@ -50,6 +50,4 @@ def log_softmax(sequence: Z) -> Z:
     return _seq(sequence, True)
 
 
-for _cls in (C, L, P, R):
-    _cls.softmax = softmax
-    _cls.log_softmax = log_softmax
+install(softmax=softmax, log_softmax=log_softmax)

@@ -66,11 +66,10 @@ from torch import Tensor
 
 from torchrua_amd import _lib as K
 from torchrua_amd import _ops as O
-from torchrua_amd.layout import C, L, P, R, T, Z, cat_lay, lay_hidden, rewrap
+from torchrua_amd.layout import (T, Z, cat_lay, check_per_token, install, lay_hidden, lead_shape, require_container, rewrap,
+                                 side_payload)
 
 __all__ = ['SeqSort', 'sort', 'argsort', 'segment_sort', 'segment_argsort', 'reorder', 'topk']
-
-_NAMES = {C: 'CattedSequence', L: 'LeftAlignedSequence', P: 'PackedSequence', R: 'RightAlignedSequence'}
 
 
 class SeqSort(NamedTuple):
@@ -82,17 +81,6 @@ class SeqSort(NamedTuple):
 def _check_dtype(data: Tensor, what: str) -> None:
     if data.dtype not in K.SCAN_DTYPES:
         raise K.RuaError(f'{what} supports {[str(d) for d in K.SCAN_DTYPES]}; got {data.dtype}')
-
-
-def _container(sequence, what: str):
-    for cls in (C, L, P, R):
-        if isinstance(sequence, cls):
-            return cls
-    raise K.RuaError(f'{what} takes a container (C / L / P / R); got {type(sequence).__name__}')
-
-
-def _lead(sequence: Z) -> int:
-    return 1 if isinstance(sequence, (C, P)) else 2
 
 
 def segment_sort(tensor: T, segment_sizes: T, descending: bool = False) -> Tuple[T, T]:
@@ -111,7 +99,7 @@ def segment_argsort(tensor: T, segment_sizes: T, descending: bool = False) -> T:
 
 def sort(sequence: Z, descending: bool = False) -> SeqSort:
     """SeqSort(values, indices): every sequence sorted stably on its own, per column.  See the module docstring."""
-    _container(sequence, 'sort')
+    require_container(sequence, 'sort')
     _check_dtype(sequence.data, 'sort')
     lay, hidden = lay_hidden(sequence)
     values, indices = O.sort(sequence.data, lay, descending, hidden)
@@ -120,36 +108,20 @@ def sort(sequence: Z, descending: bool = False) -> SeqSort:
 
 def argsort(sequence: Z, descending: bool = False) -> Z:
     """The token positions that sort every sequence, as a container of the same type (int64)."""
-    _container(sequence, 'argsort')
+    require_container(sequence, 'argsort')
     _check_dtype(sequence.data, 'argsort')
     lay, hidden = lay_hidden(sequence)
     return rewrap(sequence, O.sort(sequence.data, lay, descending, hidden, want_values=False)[1])
 
 
 def _check_indices(sequence: Z, indices, what: str) -> Tuple[Tensor, bool]:
-    """(index tensor, per_row) after the checks that need no device."""
-    cls = _container(sequence, what)
-    if isinstance(indices, (C, L, P, R)):
-        if not isinstance(indices, cls):
-            raise K.RuaError(f'{what}: indices given as a container must be a {_NAMES[cls]}; got '
-                             f'{type(indices).__name__}')
-        indices = indices.data
-    if not isinstance(indices, Tensor):
-        raise K.RuaError(f'{what}: indices is a torch.int64 tensor or a container of the same type holding one; got '
-                         f'{type(indices).__name__}')
-    if indices.dtype != torch.int64:
-        raise K.RuaError(f'{what}: indices has dtype {indices.dtype}; it must be torch.int64')
-    data = sequence.data
-    lead = tuple(data.shape[:_lead(sequence)])
-    if tuple(indices.shape) == lead:
-        per_row = True
-    elif tuple(indices.shape) == tuple(data.shape):
-        per_row = False
-    else:
-        raise K.RuaError(f'{what}: indices has shape {tuple(indices.shape)}; it is the token dimensions of the storage '
-                         f'{lead} (whole rows) or the storage shape {tuple(data.shape)} (per element)')
-    if indices.device != data.device:
-        raise K.RuaError(f'{what}: indices lives on {indices.device}, the payload on {data.device}')
+    """(index tensor, per_row) after the checks that need no device: one index per token (whole rows), or — this
+    operator's second form — one per element, in the full storage shape."""
+    require_container(sequence, what)
+    indices = side_payload(sequence, indices, what + ': indices given as a container must be a {want}; got {got}')
+    lead, full = lead_shape(sequence), tuple(sequence.data.shape)
+    per_row = not (isinstance(indices, Tensor) and tuple(indices.shape) == full != lead)
+    check_per_token(what, 'indices', indices, torch.int64, lead if per_row else full, sequence.data, per_element=full)
     return indices, per_row
 
 
@@ -166,15 +138,11 @@ def topk(sequence: Z, k: int, largest: bool = True) -> SeqSort:
     """SeqSort of the min(k, len) largest (smallest) tokens of every sequence, in sorted order, per column: the full
     stable sort followed by `unjoin` with the int size k — no kernel of its own; it synchronises exactly when `unjoin`
     does."""
-    _container(sequence, 'topk')
+    require_container(sequence, 'topk')
     if isinstance(k, bool) or not isinstance(k, Integral) or k < 0:
         raise K.RuaError(f'topk: k is {k!r}; it must be a non-negative int')
     out = sort(sequence, descending=bool(largest))
     return SeqSort(out.values.unjoin(int(k))[0], out.indices.unjoin(int(k))[0])
 
 
-for _cls in (C, L, P, R):
-    _cls.sort = sort
-    _cls.argsort = argsort
-    _cls.reorder = reorder
-    _cls.topk = topk
+install(sort=sort, argsort=argsort, reorder=reorder, topk=topk)

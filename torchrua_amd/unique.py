@@ -61,7 +61,7 @@ from torchrua_amd import _lib as K
 from torchrua_amd import _meta as M
 from torchrua_amd import _ops as O
 from torchrua_amd.core import result_like
-from torchrua_amd.layout import C, L, P, R, T, Z, cat_lay, lay_hidden, rewrap
+from torchrua_amd.layout import T, Z, cat_lay, install, lay_hidden, n_lead, require_container, rewrap
 
 __all__ = ['SeqRuns', 'segment_unique_consecutive', 'unique_consecutive']
 
@@ -92,7 +92,7 @@ def _plan(big: M.Lay, data: Tensor, hidden: Tuple[int, ...], lead: Tuple[int, ..
         head = O.launch_runs_heads(big, data, hidden)
         rank, new_sizes = O.launch_compress_plan(big, head)
         inverse = O.launch_runs_inverse(big, head, lead) if want_inverse else None
-    M.attach_host(new_sizes, M._read_back(new_sizes))
+    M.read_back_rows(new_sizes, [new_sizes])
     return rank, new_sizes, inverse
 
 
@@ -114,12 +114,11 @@ def segment_unique_consecutive(tensor: T, segment_sizes: T, return_inverse: bool
 
 def unique_consecutive(sequence: Z, return_inverse: bool = False, return_counts: bool = False) -> SeqRuns:
     """SeqRuns(values, inverse, counts): every sequence run-length encoded on its own.  See the module docstring."""
-    if not isinstance(sequence, (C, L, P, R)):
-        raise K.RuaError(f'unique_consecutive takes a container (C / L / P / R); got {type(sequence).__name__}')
+    require_container(sequence, 'unique_consecutive')
     _check_dtype(sequence.data, 'unique_consecutive')
     big, hidden = lay_hidden(sequence)
     data = sequence.data.contiguous()
-    lead = 1 if isinstance(sequence, (C, P)) else 2
+    lead = n_lead(sequence)
     rank, new_sizes, inverse = _plan(big, data, hidden, tuple(data.shape[:lead]), return_inverse)
     small, shape, wrap = result_like(type(sequence), new_sizes, big.B, hidden, data)
     values = wrap(O.compress(data, rank, small, big, hidden, shape, tuple(data.shape)))
@@ -127,5 +126,4 @@ def unique_consecutive(sequence: Z, return_inverse: bool = False, return_counts:
     return SeqRuns(values, None if inverse is None else rewrap(sequence, inverse), counts)
 
 
-for _cls in (C, L, P, R):
-    _cls.unique_consecutive = unique_consecutive
+install(unique_consecutive=unique_consecutive)

@@ -72,8 +72,8 @@ from torchrua_amd import _lib as K
 from torchrua_amd import _meta as M
 from torchrua_amd import _ops as O
 from torchrua_amd.core import result_like
-from torchrua_amd.join import _cls, _hidden, _host_array, _host_known, _is_container, _lens_lay, _n_seq, _own_host, _tensors
-from torchrua_amd.layout import C, L, P, R, T, Z, lay_hidden, lens_of
+from torchrua_amd.layout import (C, T, Z, cls_of, device_tensors, hidden_of, install, lay_hidden, lens_lay, lens_of, n_seq,
+                                 require_container)
 
 __all__ = ['window_pool', 'max_pool', 'avg_pool', 'segment_window_pool', 'window_out_lens']
 
@@ -102,8 +102,7 @@ def _window_int(value, name: str, most: int) -> int:
 
 def _check_args(sequence, kernel_size, stride, mode) -> Tuple[int, int, int]:
     """(K, S, mode code) after every check that needs no device — each refusal names the offending value."""
-    if not _is_container(sequence):
-        raise K.RuaError(f'window_pool takes a container (C / L / P / R); got {type(sequence).__name__}')
+    require_container(sequence, 'window_pool')
     if not isinstance(mode, str) or mode not in O.WINDOW_MODES:
         raise K.RuaError(f'window_pool: mode is {mode!r}; it is one of {sorted(O.WINDOW_MODES)}')
     k = _window_int(kernel_size, 'kernel_size', MAX_K)
@@ -121,21 +120,19 @@ def window_pool(sequence: Z, kernel_size: int, stride: Optional[int] = None, mod
     """Every sequence pooled over windows of `kernel_size` tokens every `stride` tokens; a container of the same type
     with the new lengths.  See the module docstring."""
     k, s, code = _check_args(sequence, kernel_size, stride, mode)
-    dev = K.require_device(*_tensors(sequence))
-    cls, B, hidden = _cls(sequence), _n_seq(sequence), _hidden(sequence)
+    dev = K.require_device(*device_tensors(sequence))
+    cls, B, hidden = cls_of(sequence), n_seq(sequence), hidden_of(sequence)
     own = lens_of(sequence)
-    if _host_known(own):
+    if M.host_known(own):
         # the lengths have a host copy: the formula is applied to it as well — no read-back for any container type
         big, _ = lay_hidden(sequence)
         sizes = O.launch_window_lens(big, k, s, ceil_mode, dev)[0]
-        M.attach_host(sizes, _own_host(window_out_lens(_host_array(own, B), k, s, ceil_mode)))
+        M.attach_host(sizes, M.own_host(window_out_lens(M.host_array(own, B), k, s, ceil_mode)))
     else:
         # ONE read-back: the new lengths and the container's own, both attached — the casts that follow read nothing
-        buf = O.launch_window_lens(_lens_lay(sequence, B), k, s, ceil_mode, dev, want_own=True)
-        host = M._read_back(buf)
+        buf = O.launch_window_lens(lens_lay(sequence), k, s, ceil_mode, dev, want_own=True)
         sizes = buf[0]
-        M.attach_host(sizes, host[0])
-        M.attach_host(own, host[1].to(own.dtype))
+        M.read_back_rows(buf, [sizes, own])
         big, _ = lay_hidden(sequence)
     small, shape, wrap = result_like(cls, sizes, B, hidden, sequence.data)
     plan = O.WindowPlan(small, big, hidden, shape, tuple(sequence.data.shape), k, s)
@@ -163,7 +160,4 @@ def segment_window_pool(tensor: T, segment_sizes: T, kernel_size: int, stride: O
     return out.data, out.token_sizes
 
 
-for _c in (C, L, P, R):
-    _c.window_pool = window_pool
-    _c.max_pool = max_pool
-    _c.avg_pool = avg_pool
+install(window_pool=window_pool, max_pool=max_pool, avg_pool=avg_pool)
