@@ -60,17 +60,28 @@ def _expect(kind, data, lens, roll=0):
     return out
 
 
-def _traced(monkeypatch, fn):
-    """fn() with the trace on and a spy on rua_move_rows: (result, the mover's trace records, the dry records)."""
+def _traced(monkeypatch, fn, extra_flags=0, pick=None, plain=None):
+    """fn() with the trace on and a spy on rua_move_rows: (result, the mover's trace records, the dry records).
+    extra_flags: developer flags (include/rua.h) ORed into the calls `pick(row_bytes, flags)` accepts, before the dry
+    call and the real one alike; every other mover call passes through unchanged.  `plain` (a list) receives, per call
+    that was picked, the dry record of the call as the library made it."""
     lib = K.load()
     real, dry = lib.rua_move_rows, []
 
-    def spy(dst, src, tmap, arg, out_ptr, src_ptr, rb, fill, pad_row, flags, stream):
+    def plan(dst, src, tmap, arg, out_ptr, src_ptr, rb, pad_row, flags):
         buf = ctypes.create_string_buffer(512)
         n = lib.rua_debug_move_plan(dst, src, tmap, arg, out_ptr or 0, src_ptr or 0, rb, pad_row, flags, buf, 512)
         assert n >= 0, n
-        if n:
-            dry.append(buf.raw[:n].decode())
+        return buf.raw[:n].decode()
+
+    def spy(dst, src, tmap, arg, out_ptr, src_ptr, rb, fill, pad_row, flags, stream):
+        if extra_flags and pick(rb, flags):
+            if plain is not None:
+                plain.append(plan(dst, src, tmap, arg, out_ptr, src_ptr, rb, pad_row, flags))
+            flags |= extra_flags
+        rec = plan(dst, src, tmap, arg, out_ptr, src_ptr, rb, pad_row, flags)
+        if rec:
+            dry.append(rec)
         return real(dst, src, tmap, arg, out_ptr, src_ptr, rb, fill, pad_row, flags, stream)
 
     monkeypatch.setattr(lib, 'rua_move_rows', spy)
