@@ -502,6 +502,66 @@ int64_t rua_cumsum_ws_bytes(const rua_layout* lay, int64_t H, int32_t dtype);
 int rua_segment_cumsum(const rua_layout* lay, const void* data, void* out, int64_t H, int32_t dtype, int32_t reverse,
                        void* ws, void* stream);
 
+/* Per-sequence running max / min with indices and logcumsumexp (EXTENSIONS, added to ABI 6 — the version number did not
+ * move): the rest of torch's cum* family on rua_segment_cumsum's skeleton (csrc/rua_cumext.hip).  The positions along
+ * the scan (u = t, reverse: u = len - 1 - t), the groups of 8, tiles of 32 and blocks of 2 048, the three kernel forms
+ * (lanes for rows of one vector, rows, and the cut form when `ws` is given), the cut rule, the clamped lengths, the
+ * zeroed padding rows of a LEFT / RIGHT result (in EVERY output; padding rows of the inputs are never read), the empty
+ * returns (B == 0, H == 0, n_rows == 0: 0 without a launch) and the accepted alignments are those of
+ * rua_segment_cumsum; what changes is the state that is combined.  Every combine absorbs its identity EXACTLY (it
+ * returns the other operand), so a form that meets a carry that does not exist gives the bits of one that skips it.
+ *
+ * rua_segment_cumextreme: torch.cummax(seq, dim=0) (op == RUA_MAX) / torch.cummin (RUA_MIN; any other op RUA_EINVAL) of
+ * every sequence on its own, per column, bit for bit in both outputs.  The state is (value, position) under ONE total
+ * order: NaN above every number, -0.0 == +0.0, and among equals the LATER position along the scan wins (the opposite of
+ * rua_segment_argreduce's "first wins"); once a NaN is met the value stays NaN and the index moves on to every later
+ * NaN.  The combine picks one of its operands, so it is associative and idempotent: every association order, layout and
+ * kernel form gives the same bits.  The identity is "no element" (position -1), not a -inf.  `values` (payload dtype)
+ * holds the winner's bits, `indices` (int64, the storage shape of the payload) its token POSITION inside the sequence in
+ * un-mirrored coordinates (so with `reverse` the EARLIER token wins among equals).  Either output may be NULL and is
+ * then not written; both NULL, a null `data`, or values == indices: RUA_EINVAL.  RUA_F32 / RUA_F64 / RUA_BF16 / RUA_F16
+ * / RUA_I64.  The cut form keeps a (value, position) pair per block and padded column:
+ *   rua_cumextreme_ws_bytes = B * ceil(bound / 2 048) * ceil(H * esize / 128) * (128 / esize) * 16, or 0.
+ *
+ * rua_segment_cumextreme_backward: the adjoint of "gather by `indices`" for the `indices` of the forward whose direction
+ * was `reverse`.  Along the scan `indices` is constant on a run and the head s of a run has indices[s] == s, so
+ *   grad_in[s] = [indices[s] == s] * sum of grad[t] over the run of s.
+ * A segmented scan, state (sum, run id), run AGAINST the forward's direction on the same skeleton: no atomics, fp32
+ * accumulation (fp64 for RUA_F64), one rounding, one order per (sequence, column).  Tokens that never win and padding
+ * rows get exact zeros whatever `grad` holds in the padding.  `indices` is compared, never dereferenced: any content is
+ * memory-safe.  Float dtypes only; workspace: rua_cumextreme_ws_bytes.
+ *
+ * rua_segment_logcumsumexp: torch.logcumsumexp(seq, dim=0) of every sequence on its own.  The state is (m, s) with value
+ * m + log s, combined as s = s_a * exp(m_a - M) + s_b * exp(m_b - M), M = max(m_a, m_b) — the softmax kernels'
+ * convention — where the factor of the operand that holds M is exactly 1.  A token is (x, 1), -inf is the identity
+ * (-inf, 0), a NaN is (-inf, NaN).  A prefix of only -inf gives -inf, +inf gives +inf from there on, a NaN poisons only
+ * the later tokens of its own sequence and column.  One association order (the cumsum's) per (sequence, column,
+ * direction): the operator commutes with the casts and `reverse` equals rev / scan / rev, bit for bit.  The float
+ * dtypes; fp32 accumulation (fp64 for RUA_F64), one rounding.  The cut form keeps (m, s) per block and padded column:
+ *   rua_logcumsumexp_ws_bytes = B * ceil(bound / 2 048) * ceil(H * esize / 128) * (128 / esize) * (8, or 16 for RUA_F64).
+ *
+ * rua_segment_logcumsumexp_backward: grad_in[s] = sum over t >= s (scan order) of grad[t] * exp(data[s] - out[t]) — the
+ * SAME fold with exponents -out[t] and signed weights grad[t], run against the forward's direction and finished as
+ * s_state * exp(m_state + data[s]).  A token with data[s] == -inf gets exactly 0 (torch gives NaN there: a documented
+ * deviation).  Workspace: rua_logcumsumexp_ws_bytes.
+ *
+ * Checks of the four, before any HIP call: the layout, H < 0 and the dtype (RUA_EINVAL), the empty returns, null
+ * pointers (RUA_EINVAL), a payload too large for 64-bit offsets (RUA_ERANGE), a pointer not aligned to its element
+ * (RUA_EALIGN).  Trace: `seg_cumextreme_{lanes,rows}_kernel`, `seg_cumextreme_bwd_*`, `seg_logcumsumexp_*`,
+ * `seg_logcumsumexp_bwd_*` with T=, W= / H= (lanes), AL=, rev= (the direction of THAT scan), kind=, op=, and cut= /
+ * phase=partial|finish / blocks= / chunks= (rows). */
+int64_t rua_cumextreme_ws_bytes(const rua_layout* lay, int64_t H, int32_t dtype);
+int rua_segment_cumextreme(const rua_layout* lay, const void* data, void* values /* NULL: not written */,
+                           void* indices /* NULL: not written */, int64_t H, int32_t dtype, int32_t op, int32_t reverse,
+                           void* ws, void* stream);
+int rua_segment_cumextreme_backward(const rua_layout* lay, const void* grad, const void* indices, void* grad_in,
+                                    int64_t H, int32_t dtype, int32_t reverse, void* ws, void* stream);
+int64_t rua_logcumsumexp_ws_bytes(const rua_layout* lay, int64_t H, int32_t dtype);
+int rua_segment_logcumsumexp(const rua_layout* lay, const void* data, void* out, int64_t H, int32_t dtype,
+                             int32_t reverse, void* ws, void* stream);
+int rua_segment_logcumsumexp_backward(const rua_layout* lay, const void* grad, const void* data, const void* out,
+                                      void* grad_in, int64_t H, int32_t dtype, int32_t reverse, void* ws, void* stream);
+
 /* Per-sequence gated linear recurrence (an EXTENSION, added to ABI 6 — the version number did not move: the reference's
  * users pad, loop over the time steps with elementwise kernels and cast back).  For every sequence b of `lay` (ANY
  * layout) and column h, with u the position along the scan (u = t; reverse != 0: u = len - 1 - t):

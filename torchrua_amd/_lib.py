@@ -111,6 +111,16 @@ SYMBOLS = {
                                                  c_int32, c_int64, c_void_p, c_void_p]),
     'rua_cumsum_ws_bytes': (c_int64, [POINTER(RuaLayout), c_int64, c_int32]),
     'rua_segment_cumsum': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
+    'rua_cumextreme_ws_bytes': (c_int64, [POINTER(RuaLayout), c_int64, c_int32]),
+    'rua_segment_cumextreme': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32,
+                                       c_int32, c_void_p, c_void_p]),
+    'rua_segment_cumextreme_backward': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_int64, c_int32,
+                                                c_int32, c_void_p, c_void_p]),
+    'rua_logcumsumexp_ws_bytes': (c_int64, [POINTER(RuaLayout), c_int64, c_int32]),
+    'rua_segment_logcumsumexp': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p,
+                                         c_void_p]),
+    'rua_segment_logcumsumexp_backward': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                                  c_int32, c_int32, c_void_p, c_void_p]),
     'rua_linear_scan_ws_bytes': (c_int64, [POINTER(RuaLayout), c_int64, c_int32]),
     'rua_segment_linear_scan': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_double, c_void_p, c_int64, c_int32,
                                         c_int32, c_void_p, c_void_p]),

@@ -795,6 +795,182 @@ def cumsum(data: Tensor, lay: M.Lay, reverse: bool, hidden) -> Tensor:
     return launch_cumsum(lay, _plain(data), bool(reverse), tuple(hidden))
 
 
+# ------------------------------------------------------------------ per-sequence cummax / cummin / logcumsumexp (extensions)
+_CUMEXT_SUPPORT = 'cummax / cummin support'
+_LCSE_SUPPORT = 'logcumsumexp supports'
+
+
+def launch_cumextreme(lay: M.Lay, data: Tensor, op: int, reverse: bool, hidden: Tuple[int, ...],
+                      want_values: bool = True, want_indices: bool = True,
+                      cut: bool = True) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+    """rua_segment_cumextreme: (values or None, indices or None), both of the payload's storage shape — one launch (two
+    for cut sequences), one read of the payload.  cut=False withholds the workspace (the same bits: a developer A/B)."""
+    code = _require_dtype(data, L.SCAN_DTYPES, _CUMEXT_SUPPORT)
+    if op not in (L.MAX, L.MIN):
+        raise L.RuaError('cumextreme: the operator is MAX or MIN')
+    dev, H = data.device, _prod(hidden)
+    ws = _workspace('rua_cumextreme_ws_bytes', lay, H, code, dev, cut)
+    data = data.contiguous()
+    values = torch.empty(data.shape, dtype=data.dtype, device=dev) if want_values else None      # padding rows: zeroed
+    indices = torch.empty(data.shape, dtype=torch.int64, device=dev) if want_indices else None   # by the call
+    name = ('cummax' if op == L.MAX else 'cummin') + ('_rev' if reverse else '')
+    _call(name, 'rua_segment_cumextreme', dev, lay.ref(), L.ptr(data), L.ptr(values), L.ptr(indices), H, code, op,
+          int(bool(reverse)), L.ptr(ws))
+    return values, indices
+
+
+def _cum_indices(grad: Tensor, indices: Tensor, what: str) -> Tensor:
+    L.require_device(grad, indices)
+    if indices.dtype != torch.int64 or indices.shape != grad.shape:
+        raise L.RuaError(f'{what}: the indices are an int64 tensor of the storage shape of the cotangent')
+    return _plain(indices).contiguous()
+
+
+def launch_cumextreme_backward(lay: M.Lay, grad: Tensor, indices: Tensor, reverse: bool, hidden: Tuple[int, ...],
+                               cut: bool = True) -> Tensor:
+    """rua_segment_cumextreme_backward: the run sums of `grad` at the run heads of `indices` — the adjoint of the
+    gather by `indices`; zeros elsewhere and in padding rows."""
+    code = _require_dtype(grad, L.DTYPES, _CUMEXT_SUPPORT + ' (gradients)')
+    indices = _cum_indices(grad, indices, 'cummax / cummin backward')
+    dev, H = grad.device, _prod(hidden)
+    ws = _workspace('rua_cumextreme_ws_bytes', lay, H, code, dev, cut)
+    grad = grad.contiguous()
+    out = torch.empty(grad.shape, dtype=grad.dtype, device=dev)
+    _call('cumextreme_rev_bwd' if reverse else 'cumextreme_bwd', 'rua_segment_cumextreme_backward', dev, lay.ref(),
+          L.ptr(grad), L.ptr(indices), L.ptr(out), H, code, int(bool(reverse)), L.ptr(ws))
+    return out
+
+
+class _CumRunSum(torch.autograd.Function):
+    """grad -> its run sums at the run heads of `indices` (rua_segment_cumextreme_backward).  Linear; its adjoint is
+    the gather by the same indices (_CumGather), whose adjoint is this again: derivatives of every order exist.  Saves
+    ONLY the indices."""
+
+    @staticmethod
+    def forward(ctx, grad: Tensor, indices: Tensor, lay: M.Lay, reverse: bool, hidden):
+        ctx.args = (lay, bool(reverse), tuple(hidden))
+        ctx.save_for_backward(indices)
+        return launch_cumextreme_backward(lay, grad, indices, reverse, hidden)
+
+    @staticmethod
+    def backward(ctx, grad: Tensor):
+        indices, = ctx.saved_tensors
+        lay, reverse, hidden = ctx.args
+        return cum_gather(grad, indices, lay, reverse, hidden), None, None, None, None
+
+
+class _CumGather(torch.autograd.Function):
+    """payload -> out[b, t, h] = payload[b, indices[b, t, h], h]: the per-element gather of rua_segment_reorder, which
+    takes repeated positions (its scatter does not: this never routes through _Reorder).  Saves ONLY the indices."""
+
+    @staticmethod
+    def forward(ctx, data: Tensor, indices: Tensor, lay: M.Lay, reverse: bool, hidden):
+        ctx.args = (lay, bool(reverse), tuple(hidden))
+        ctx.save_for_backward(indices)
+        return launch_reorder(lay, data, indices, hidden, per_row=False, inverse=False)
+
+    @staticmethod
+    def backward(ctx, grad: Tensor):
+        indices, = ctx.saved_tensors
+        lay, reverse, hidden = ctx.args
+        return cum_run_sum(grad, indices, lay, reverse, hidden), None, None, None, None
+
+
+def cum_run_sum(grad: Tensor, indices: Tensor, lay: M.Lay, reverse: bool, hidden) -> Tensor:
+    if _wants_grad(grad):
+        return _CumRunSum.apply(grad.contiguous(), indices, lay, bool(reverse), tuple(hidden))
+    return launch_cumextreme_backward(lay, _plain(grad), indices, bool(reverse), tuple(hidden))
+
+
+def cum_gather(data: Tensor, indices: Tensor, lay: M.Lay, reverse: bool, hidden) -> Tensor:
+    if _wants_grad(data):
+        return _CumGather.apply(data.contiguous(), indices, lay, bool(reverse), tuple(hidden))
+    return launch_reorder(lay, _plain(data), indices, tuple(hidden), per_row=False, inverse=False)
+
+
+class _CumExtreme(torch.autograd.Function):
+    """(values, indices) = the running max / min of every sequence.  Saves ONLY the indices; the backward is the run
+    sum of the cotangent (cum_run_sum), itself differentiable."""
+
+    @staticmethod
+    def forward(ctx, data: Tensor, lay: M.Lay, op: int, reverse: bool, hidden):
+        values, indices = launch_cumextreme(lay, data, op, reverse, hidden)
+        ctx.args = (lay, bool(reverse), tuple(hidden))
+        ctx.save_for_backward(indices)
+        ctx.mark_non_differentiable(indices)
+        return values, indices
+
+    @staticmethod
+    def backward(ctx, grad: Tensor, _grad_indices):
+        indices, = ctx.saved_tensors
+        lay, reverse, hidden = ctx.args
+        return cum_run_sum(grad, indices, lay, reverse, hidden), None, None, None, None
+
+
+def cumextreme(data: Tensor, lay: M.Lay, op: int, reverse: bool, hidden) -> Tuple[Tensor, Tensor]:
+    _require_dtype(data, L.SCAN_DTYPES, _CUMEXT_SUPPORT)
+    if _wants_grad(data):
+        # contiguous HERE, before the Function (as in cumsum()): a copy made inside forward() would carry no history
+        return _CumExtreme.apply(data.contiguous(), lay, op, bool(reverse), tuple(hidden))
+    return launch_cumextreme(lay, _plain(data), op, bool(reverse), tuple(hidden))
+
+
+def launch_logcumsumexp(lay: M.Lay, data: Tensor, reverse: bool, hidden: Tuple[int, ...], cut: bool = True) -> Tensor:
+    """rua_segment_logcumsumexp: one launch (two for cut sequences), one read and one write of the payload."""
+    code = _require_dtype(data, L.DTYPES, _LCSE_SUPPORT)
+    dev, H = data.device, _prod(hidden)
+    ws = _workspace('rua_logcumsumexp_ws_bytes', lay, H, code, dev, cut)
+    data = data.contiguous()
+    out = torch.empty(data.shape, dtype=data.dtype, device=dev)      # padding rows: zeroed by the call
+    _call('logcumsumexp_rev' if reverse else 'logcumsumexp', 'rua_segment_logcumsumexp', dev, lay.ref(), L.ptr(data),
+          L.ptr(out), H, code, int(bool(reverse)), L.ptr(ws))
+    return out
+
+
+def launch_logcumsumexp_backward(lay: M.Lay, grad: Tensor, data: Tensor, out: Tensor, reverse: bool,
+                                 hidden: Tuple[int, ...], cut: bool = True) -> Tensor:
+    """rua_segment_logcumsumexp_backward: grad_in[s] = sum over t >= s (scan order) of grad[t] * exp(x[s] - y[t])."""
+    code = _require_dtype(grad, L.DTYPES, _LCSE_SUPPORT)
+    L.require_device(grad, data, out)
+    if not (grad.dtype == data.dtype == out.dtype) or not (grad.shape == data.shape == out.shape):
+        raise L.RuaError('logcumsumexp backward: cotangent, input and output share one dtype and one storage shape')
+    dev, H = grad.device, _prod(hidden)
+    ws = _workspace('rua_logcumsumexp_ws_bytes', lay, H, code, dev, cut)
+    grad, data, out = grad.contiguous(), data.contiguous(), out.contiguous()
+    gx = torch.empty(grad.shape, dtype=grad.dtype, device=dev)
+    _call('logcumsumexp_rev_bwd' if reverse else 'logcumsumexp_bwd', 'rua_segment_logcumsumexp_backward', dev, lay.ref(),
+          L.ptr(grad), L.ptr(data), L.ptr(out), L.ptr(gx), H, code, int(bool(reverse)), L.ptr(ws))
+    return gx
+
+
+class _LogCumSumExp(torch.autograd.Function):
+    """y = logcumsumexp of every sequence.  Saves the input and the output; the backward is one fused kernel (the same
+    weighted log-space scan run the other way).  Second derivatives are out of scope."""
+
+    @staticmethod
+    def forward(ctx, data: Tensor, lay: M.Lay, reverse: bool, hidden):
+        out = launch_logcumsumexp(lay, data, reverse, hidden)
+        ctx.args = (lay, bool(reverse), tuple(hidden))
+        ctx.save_for_backward(data, out)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad: Tensor):
+        if torch.is_grad_enabled():
+            raise L.RuaError('logcumsumexp: second derivatives (create_graph=True) are out of scope')
+        data, out = ctx.saved_tensors
+        lay, reverse, hidden = ctx.args
+        return launch_logcumsumexp_backward(lay, grad, data, out, reverse, hidden), None, None, None
+
+
+def logcumsumexp(data: Tensor, lay: M.Lay, reverse: bool, hidden) -> Tensor:
+    _require_dtype(data, L.DTYPES, _LCSE_SUPPORT)
+    if data.requires_grad and torch.is_grad_enabled():
+        # contiguous HERE, before the Function (as in cumsum()): a copy made inside forward() would carry no history
+        return _LogCumSumExp.apply(data.contiguous(), lay, bool(reverse), tuple(hidden))
+    return launch_logcumsumexp(lay, _plain(data), bool(reverse), tuple(hidden))
+
+
 # ------------------------------------------------------------------ per-sequence gated linear recurrence (an extension)
 def _gate_arg(data: Tensor, gate) -> Tuple[Optional[Tensor], float]:
     """(the gate tensor or None, the scalar gate): a tensor of the payload's storage shape, dtype and device, or ONE
