@@ -562,6 +562,62 @@ int rua_segment_logcumsumexp(const rua_layout* lay, const void* data, void* out,
 int rua_segment_logcumsumexp_backward(const rua_layout* lay, const void* grad, const void* data, const void* out,
                                       void* grad_in, int64_t H, int32_t dtype, int32_t reverse, void* ws, void* stream);
 
+/* Per-sequence linear-chain CRF (an EXTENSION, added to ABI 6 — the version number did not move): the log partition
+ * function, its gradients (the marginals) and Viterbi over the emissions [rows, K] of ANY layout (csrc/rua_crf.hip).
+ * `emissions` is the storage of `lay` with rows of K elements, `transitions` [K, K] row-major (transitions[i, j]: tag i
+ * at t-1, then tag j at t), `start` / `end` [K] or NULL (NULL adds 0 and gives the bits of a zeros tensor); all four in
+ * the element type `dtype` (RUA_F32 / RUA_F64 / RUA_BF16 / RUA_F16).  The per-sequence results and the table `alpha` are
+ * in the ACCUMULATOR type (float; double for RUA_F64) and are never rounded to a 16-bit type.  1 <= K <= RUA_CRF_MAX_TAGS.
+ *
+ * Geometry: one wave per sequence, lane j owns tag j; wave w of the launch walks sequences w, w + waves, ... (the
+ * forward launches at most 1 024 workgroups, the backward at most 1 024 WAVES).  A kernel per element type, semiring
+ * and tag bucket (K <= 8 / 16 / 32 / 64).  One very long sequence is walked by ONE wave: correct and slow (cutting it
+ * needs K x K matrix products per block; out of scope).
+ *
+ * ONE evaluation order per (sequence, tag, step), whatever the layout (no contraction):
+ *   alpha_0[j] = start[j] + x_0[j];   v_i = alpha_{t-1}[i] + transitions[i, j] for i = 0 .. K-1;
+ *   RUA_CRF_LOG: m = max_i v_i, s = sum_i exp(v_i - m) in ascending i, alpha_t[j] = x_t[j] + (m + log s), or
+ *                x_t[j] + (-inf) when m == -inf (an unreachable tag is -inf, never NaN; a NaN v_i makes alpha_t[j] NaN);
+ *   RUA_CRF_MAX: the maximum under rua_segment_argreduce's order (a NaN beats every number, the first of equals wins),
+ *                its i is the backpointer of (t, j), alpha_t[j] = x_t[j] + max;
+ *   out[b] = the same fold of alpha_{n-1}[j] + end[j] over j (RUA_CRF_MAX: last[b] = its j).  An empty sequence gives
+ *   out[b] = 0 (last[b] = -1).  -inf is a forbidden move; +inf is out of scope.  Padding rows are never read.
+ *
+ * rua_segment_crf_forward: `out` [B] always; RUA_CRF_LOG writes `alpha` [rows, K] (the storage layout of the
+ * emissions; padding rows are not written) when it is not NULL; RUA_CRF_MAX writes `backptr` (one uint8 per (row, tag);
+ * the rows of token 0 are not written) and `last` [B] int64, both required.
+ * rua_segment_crf_backtrace: a launch of its own on the same stream; a thread per sequence walks `backptr` from
+ * `last` and writes `tags` (int64, one per row of the storage; zeros in the padding rows of LEFT / RIGHT).
+ * rua_segment_crf_backward (of RUA_CRF_LOG, with `grad` [B] the cotangent of `out`, `alpha` and `logz` what the forward
+ * wrote): beta_{n-1} = end, beta_{t-1}[i] = logsumexp_j(transitions[i, j] + (x_t[j] + beta_t[j])) in ascending j,
+ *   grad_emissions[t, j] = grad[b] * exp((alpha_t[j] + beta_t[j]) - logz[b])      (rounded once; padding rows: zeros)
+ * and the sums over tokens and sequences grad_transitions [K, K], grad_start [K], grad_end [K] (element type; each may
+ * be NULL).  A sequence with logz == -inf gets exact zeros and adds nothing.  No float atomics: every wave leaves one
+ * part [K * K + 2 K] in `ws` and a finish launch adds the parts in part order — bitwise reproducible for the same
+ * container.  `ws` is required when one of the three sums is wanted:
+ *   rua_crf_ws_bytes(lay, K, dtype) = 4 * min(ceil(B / 4), 256) * (K * K + 2 * K) * sizeof(acc), 0 for B == 0.
+ *
+ * Checks, before any HIP call: a null layout, a dtype outside the four, K outside [1, 64], an unknown semiring
+ * (RUA_EINVAL); B == 0 returns 0 without a launch; a missing required pointer (RUA_EINVAL); a table too large for
+ * 64-bit offsets (RUA_ERANGE); a pointer not aligned to its element (RUA_EALIGN).  Trace: `seg_crf_forward_kernel`
+ * (T=, K=, bucket=, semiring=, alpha=, kind=, grid=), `seg_crf_backtrace_kernel`, `seg_crf_backward_kernel` (parts=),
+ * `seg_crf_finish_kernel`. */
+#define RUA_CRF_MAX_TAGS 64
+#define RUA_CRF_LOG 0
+#define RUA_CRF_MAX 1
+int64_t rua_crf_ws_bytes(const rua_layout* lay, int32_t K, int32_t dtype);   /* backward only */
+int rua_segment_crf_forward(const rua_layout* lay, const void* emissions, const void* transitions,
+                            const void* start /* NULL */, const void* end /* NULL */, void* alpha /* NULL */,
+                            void* backptr, void* out, void* last, int32_t K, int32_t dtype, int32_t semiring,
+                            void* stream);
+int rua_segment_crf_backtrace(const rua_layout* lay, const void* backptr, const void* last, void* tags, int32_t K,
+                              void* stream);
+int rua_segment_crf_backward(const rua_layout* lay, const void* grad, const void* emissions, const void* transitions,
+                             const void* end /* NULL */, const void* alpha, const void* logz,
+                             void* grad_emissions /* NULL */, void* grad_transitions /* NULL */,
+                             void* grad_start /* NULL */, void* grad_end /* NULL */, int32_t K, int32_t dtype, void* ws,
+                             void* stream);
+
 /* Per-sequence gated linear recurrence (an EXTENSION, added to ABI 6 — the version number did not move: the reference's
  * users pad, loop over the time steps with elementwise kernels and cast back).  For every sequence b of `lay` (ANY
  * layout) and column h, with u the position along the scan (u = t; reverse != 0: u = len - 1 - t):

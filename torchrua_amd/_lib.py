@@ -35,6 +35,8 @@ CONV_MAX_TAPS = 8          # rua.h: RUA_CONV_MAX_TAPS, the longest filter of rua
 JOIN_MAX_PARTS = 8         # rua.h: RUA_JOIN_MAX_PARTS, the most parts of one rua_segment_join
 RUNS_BITS = 0x100          # rua.h: RUA_RUNS_BITS, the `eq` of rua_segment_runs_heads that compares bits
 WINDOW_MAX_K = 64          # rua.h: RUA_WINDOW_MAX_K, the longest window of rua_segment_window_pool
+CRF_MAX_TAGS = 64          # rua.h: RUA_CRF_MAX_TAGS, the most tags of the linear-chain CRF (a lane per tag)
+CRF_LOG, CRF_MAX = 0, 1    # rua.h: RUA_CRF_LOG / RUA_CRF_MAX, the semiring of rua_segment_crf_forward
 WINDOW_TAKE = 6            # rua.h: RUA_WINDOW_TAKE, the fourth mode of rua_segment_window_pool / _spread (next to SUM, MEAN, MAX)
 # enum rua_dtype / rua_op
 F32, BF16, F16, F64 = 0, 1, 2, 3
@@ -121,6 +123,12 @@ SYMBOLS = {
                                          c_void_p]),
     'rua_segment_logcumsumexp_backward': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                                   c_int32, c_int32, c_void_p, c_void_p]),
+    'rua_crf_ws_bytes': (c_int64, [POINTER(RuaLayout), c_int32, c_int32]),
+    'rua_segment_crf_forward': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    'rua_segment_crf_backtrace': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
+    'rua_segment_crf_backward': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     'rua_linear_scan_ws_bytes': (c_int64, [POINTER(RuaLayout), c_int64, c_int32]),
     'rua_segment_linear_scan': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_double, c_void_p, c_int64, c_int32,
                                         c_int32, c_void_p, c_void_p]),

@@ -971,6 +971,135 @@ def logcumsumexp(data: Tensor, lay: M.Lay, reverse: bool, hidden) -> Tensor:
     return launch_logcumsumexp(lay, _plain(data), bool(reverse), tuple(hidden))
 
 
+# ------------------------------------------------------------------ per-sequence linear-chain CRF (an extension)
+_CRF_SUPPORT = 'crf: the emissions are one of'
+
+
+def crf_args(what: str, data: Tensor, hidden: Tuple[int, ...], transitions, start, end,
+             before_device: Optional[Callable[[], None]] = None) -> int:
+    """K, after the checks that come before any launch, each naming its argument: a float payload with exactly one hidden
+    dimension of 1 <= K <= CRF_MAX_TAGS; `transitions` [K, K], `start` / `end` [K] or None, all of the payload's dtype
+    and device; and last (so that every other refusal can be met without a GPU) the payload on a HIP device."""
+    if data.dtype not in L.DTYPES:
+        raise L.RuaError(f'{what}: the emissions are one of {list(L.DTYPES)}; got {data.dtype}')
+    if len(hidden) != 1:
+        raise L.RuaError(f'{what}: the emissions have exactly ONE hidden dimension (the K tags); got hidden dimensions '
+                         f'{tuple(hidden)}')
+    K = int(hidden[0])
+    if not 1 <= K <= L.CRF_MAX_TAGS:
+        raise L.RuaError(f'{what}: the emissions have K = {K} tags; 1 <= K <= {L.CRF_MAX_TAGS}')
+    for name, t, shape in (('transitions', transitions, (K, K)), ('start', start, (K,)), ('end', end, (K,))):
+        if t is None and name != 'transitions':
+            continue
+        if not isinstance(t, Tensor):
+            raise L.RuaError(f'{what}: `{name}` is a tensor of shape {shape}; got {type(t).__name__}')
+        if tuple(t.shape) != shape:
+            raise L.RuaError(f'{what}: `{name}` has shape {tuple(t.shape)}; with K = {K} tags it must be {shape}')
+        if t.dtype != data.dtype:
+            raise L.RuaError(f'{what}: `{name}` has dtype {t.dtype}, the emissions {data.dtype}')
+        if t.device != data.device:
+            raise L.RuaError(f'{what}: `{name}` lives on {t.device}, the emissions on {data.device}')
+    if before_device is not None:
+        before_device()
+    if not data.is_cuda:
+        raise L.RuaError(f'{what}: the emissions live on {data.device}; move them to a HIP device (there is no CPU '
+                         f'fallback by design)')
+    return K
+
+
+def _crf_small(t: Optional[Tensor]) -> Optional[Tensor]:
+    return None if t is None else _plain(t).contiguous()
+
+
+def launch_crf_forward(lay: M.Lay, data: Tensor, transitions: Tensor, start: Optional[Tensor], end: Optional[Tensor],
+                       K: int, viterbi: bool = False, want_alpha: bool = False):
+    """rua_segment_crf_forward: ONE launch.  (out [B], alpha [*storage, K] or None, backptr or None, last or None), the
+    per-sequence results and alpha in the accumulator type.  B == 0: empty results without a launch."""
+    code = _require_dtype(data, L.DTYPES, _CRF_SUPPORT)
+    dev, acc = data.device, _acc_dtype(data.dtype)
+    data, transitions, start, end = data.contiguous(), _crf_small(transitions), _crf_small(start), _crf_small(end)
+    out = torch.empty(lay.B, dtype=acc, device=dev)
+    alpha = torch.empty(data.shape, dtype=acc, device=dev) if want_alpha and not viterbi else None
+    backptr = torch.empty(data.shape, dtype=torch.uint8, device=dev) if viterbi else None
+    last = torch.empty(lay.B, dtype=torch.int64, device=dev) if viterbi else None
+    if lay.B:
+        _call('crf_viterbi' if viterbi else 'crf_partition', 'rua_segment_crf_forward', dev, lay.ref(), L.ptr(data),
+              L.ptr(transitions), L.ptr(start), L.ptr(end), L.ptr(alpha), L.ptr(backptr), L.ptr(out), L.ptr(last), K, code,
+              L.CRF_MAX if viterbi else L.CRF_LOG)
+    return out, alpha, backptr, last
+
+
+def launch_crf_backtrace(lay: M.Lay, backptr: Tensor, last: Tensor, lead_shape: Sequence[int], K: int) -> Tensor:
+    """rua_segment_crf_backtrace: a launch of its own on the same stream; the int64 tags, one per row of the storage."""
+    dev = backptr.device
+    tags = torch.empty(tuple(lead_shape), dtype=torch.int64, device=dev)       # padding rows: zeroed by the call
+    if lay.B and tags.numel():
+        _call('crf_backtrace', 'rua_segment_crf_backtrace', dev, lay.ref(), L.ptr(backptr), L.ptr(last), L.ptr(tags), K)
+    return tags
+
+
+def launch_crf_backward(lay: M.Lay, grad: Tensor, data: Tensor, transitions: Tensor, end: Optional[Tensor], alpha: Tensor,
+                        logz: Tensor, K: int, want_emissions: bool = True, want_transitions: bool = True,
+                        want_start: bool = True, want_end: bool = True):
+    """rua_segment_crf_backward: (grad_emissions, grad_transitions, grad_start, grad_end), None where not wanted — one
+    walk, plus the finish launch when one of the parameter sums is wanted."""
+    code = _require_dtype(data, L.DTYPES, _CRF_SUPPORT)
+    dev, acc = data.device, _acc_dtype(data.dtype)
+    L.require_device(grad, data, transitions, end, alpha, logz)
+    if grad.dtype != acc or tuple(grad.shape) != (lay.B,):
+        raise L.RuaError(f'crf backward: the cotangent of logZ is a {acc} tensor of shape ({lay.B},)')
+    params = want_transitions or want_start or want_end
+    # (no sequence: the entry point returns without a launch, and an empty sum is 0)
+    small = torch.zeros if lay.B == 0 else torch.empty
+    gx = torch.empty(data.shape, dtype=data.dtype, device=dev) if want_emissions else None
+    gt = small((K, K), dtype=data.dtype, device=dev) if want_transitions else None
+    gs = small((K,), dtype=data.dtype, device=dev) if want_start else None
+    ge = small((K,), dtype=data.dtype, device=dev) if want_end else None
+    if lay.B and (want_emissions or params):
+        nbytes = L.load().rua_crf_ws_bytes(lay.ref(), K, code) if params else 0
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+        # bound to names until the launch is queued: a copy whose only owner is an argument expression goes back to the
+        # allocator before the next copy is made, which then lands on it (the cotangent of .sum() is a stride-0 view)
+        grad, data, alpha, logz = grad.contiguous(), data.contiguous(), alpha.contiguous(), logz.contiguous()
+        transitions, end = _crf_small(transitions), _crf_small(end)
+        _call('crf_partition_bwd', 'rua_segment_crf_backward', dev, lay.ref(), L.ptr(grad), L.ptr(data),
+              L.ptr(transitions), L.ptr(end), L.ptr(alpha), L.ptr(logz), L.ptr(gx), L.ptr(gt), L.ptr(gs), L.ptr(ge), K, code,
+              L.ptr(ws))
+    return gx, gt, gs, ge
+
+
+class _CrfPartition(torch.autograd.Function):
+    """logZ [B] of every sequence.  Saves the forward table alpha ([rows, K], accumulator type, the emissions' storage
+    layout), logZ and the inputs; the backward is one fused walk plus the finish launch of the parameter sums.  Second
+    derivatives are out of scope."""
+
+    @staticmethod
+    def forward(ctx, data: Tensor, transitions: Tensor, start: Optional[Tensor], end: Optional[Tensor], lay: M.Lay, K: int):
+        logz, alpha, _, _ = launch_crf_forward(lay, data, transitions, start, end, K, want_alpha=True)
+        ctx.lay, ctx.K, ctx.has_end = lay, K, end is not None
+        ctx.save_for_backward(*((data, transitions, alpha, logz) + ((end,) if end is not None else ())))
+        return logz
+
+    @staticmethod
+    def backward(ctx, grad: Tensor):
+        if torch.is_grad_enabled():
+            raise L.RuaError('crf_partition: second derivatives (create_graph=True) are out of scope')
+        data, transitions, alpha, logz = ctx.saved_tensors[:4]
+        end = ctx.saved_tensors[4] if ctx.has_end else None
+        want = ctx.needs_input_grad
+        gx, gt, gs, ge = launch_crf_backward(ctx.lay, grad, data, transitions, end, alpha, logz, ctx.K, want[0], want[1],
+                                             want[2], want[3])
+        return gx, gt, gs, ge, None, None
+
+
+def crf_partition(data: Tensor, transitions: Tensor, start: Optional[Tensor], end: Optional[Tensor], lay: M.Lay,
+                  K: int) -> Tensor:
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (data, transitions, start, end)):
+        # contiguous HERE, before the Function (as in cumsum()): a copy made inside forward() would carry no history
+        return _CrfPartition.apply(data.contiguous(), transitions, start, end, lay, K)
+    return launch_crf_forward(lay, _plain(data), transitions, start, end, K)[0]
+
+
 # ------------------------------------------------------------------ per-sequence gated linear recurrence (an extension)
 def _gate_arg(data: Tensor, gate) -> Tuple[Optional[Tensor], float]:
     """(the gate tensor or None, the scalar gate): a tensor of the payload's storage shape, dtype and device, or ONE
