@@ -278,6 +278,33 @@ int rua_pack_reduce(const rua_layout* src, const rua_layout* pack, const void* d
                     int64_t H, int32_t dtype, int32_t op, uint64_t empty_bits, void* extreme, int64_t split_rows,
                     void* ws, void* stream);
 
+/* pack() that keeps the per-sequence sums of its one pass (what `pack(keep_sums=...)` calls).  rua_pack_reduce with
+ * op = RUA_SUM, except that the sums are stored as the fp32 ACCUMULATORS, not rounded: sums[b, :] (fp32 [B, H], batch
+ * order) is what rua_segment_reduce(pack, RUA_SUM) rounds to the payload dtype, so one side buffer serves any later
+ * output dtype (rua_sums_cast).  dtype: RUA_F32 / RUA_BF16 / RUA_F16 (anything else RUA_EINVAL).  Sequences longer than
+ * split_rows go through the work list of rua_segment_reduce (ws: rua_reduce_ws_bytes), folded in part order: deterministic.
+ * Nothing is launched and the code says why when the call cannot be served: a null layout or pointer, a source that is
+ * not CAT / LEFT / RIGHT, a `pack` of another batch size: RUA_EINVAL; rows that are not a multiple of 16 bytes or a
+ * pointer (data, pack_data, sums) off a 16-byte boundary: RUA_EALIGN — the caller then packs with rua_move_rows and
+ * keeps no sums; it never gets wrong ones.  Trace: the records of rua_pack_reduce (COPY=1). */
+int rua_pack_sums(const rua_layout* src, const rua_layout* pack, const void* data, void* pack_data, float* sums,
+                  int64_t H, int32_t dtype, int64_t split_rows, void* ws, void* stream);
+
+/* The adjoint of rua_pack_sums when both outputs carry a cotangent, in one pass (N*H*e read, N*H*e written):
+ *   grad_src[row(b, t)] = grad_pack[boff[t] + rank(b)] + grad_sums[b, :]       (added in fp32, rounded once)
+ * grad_src has the storage of `src`; padding rows of a LEFT / RIGHT source are zeroed.  With one cotangent only the
+ * existing calls are the adjoint: rua_segment_reduce_backward(src, RUA_SUM) for the sums, rua_move_rows(src <- pack) for
+ * the payload.  One wave walks a whole sequence (no long-sequence split).  Codes as rua_pack_sums (RUA_EALIGN: rows or
+ * pointers off 16 bytes).  Trace: `pack_sums_backward_kernel T= EPL= NT= chunks=`. */
+int rua_pack_sums_backward(const rua_layout* src, const rua_layout* pack, const void* grad_pack, const float* grad_sums,
+                           void* grad_src, int64_t H, int32_t dtype, void* stream);
+
+/* n elements between the fp32 side buffer of rua_pack_sums and the payload dtype: to_f32 == 0 rounds in[fp32] to
+ * out[dtype] (the rounding rua_segment_reduce applies to its accumulators), to_f32 != 0 widens in[dtype] to out[fp32].
+ * dtype as in rua_pack_sums; a null pointer, in == out or n < 0: RUA_EINVAL; a pointer that is not aligned to its
+ * element: RUA_EALIGN. */
+int rua_sums_cast(const void* in, void* out, int64_t n, int32_t dtype, int32_t to_f32, void* stream);
+
 /* Backward of rua_segment_reduce in one kernel (semantics of torch's
  * segment_reduce backward, which the reference inherits through autograd: reduce.py:34-61):
  *   SUM g | MEAN g/len | PROD g*prod(others) (zero factors handled like torch) | LOGSUMEXP g*exp(x-out) |

@@ -87,6 +87,11 @@ SYMBOLS = {
                                    c_int32, c_uint64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     'rua_pack_reduce': (c_int, [POINTER(RuaLayout), POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_int64, c_int32,
                                 c_int32, c_uint64, c_void_p, c_int64, c_void_p, c_void_p]),
+    'rua_pack_sums': (c_int, [POINTER(RuaLayout), POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_int64, c_int32,
+                              c_int64, c_void_p, c_void_p]),
+    'rua_pack_sums_backward': (c_int, [POINTER(RuaLayout), POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_int64,
+                                       c_int32, c_void_p]),
+    'rua_sums_cast': (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p]),
     'rua_segment_reduce_backward': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                             c_int64, c_int32, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_void_p,
                                             c_void_p]),

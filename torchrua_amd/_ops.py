@@ -391,6 +391,143 @@ def reduce(data: Tensor, lay: M.Lay, op: int, hidden, lens: Optional[Tensor]) ->
     return launch_reduce(lay, _plain(data), op, hidden=tuple(hidden))
 
 
+# ------------------------------------------------------------------ pack() that keeps the sums of its one pass
+# pack(keep_sums=...) runs the fused pack + sum (rua_pack_sums): the PackedSequence AND the fp32 per-sequence sums in one
+# pass over the payload.  The sums ride on the returned payload tensor (the per-tensor memo, keyed by its version), and
+# reduce_sum(p) rounds them to the payload dtype (rua_sums_cast) instead of reading the payload a third time.
+SUMS_DTYPES = (torch.float32, torch.bfloat16, torch.float16)      # payloads the fused kernel accumulates in fp32
+_SUMS_KEY = 'pack_sums'
+
+
+def pack_sums_can(data: Tensor, hidden: Tuple[int, ...]) -> bool:
+    """Can rua_pack_sums take this payload?  (Its own conditions: anything else is packed by the mover, without sums.)"""
+    return (data.dtype in SUMS_DTYPES and data.is_contiguous() and data.data_ptr() % 16 == 0 and data.numel() > 0
+            and (_prod(hidden) * data.element_size()) % 16 == 0)
+
+
+def launch_pack_sums(data: Tensor, src: M.Lay, dst: M.Lay, hidden: Tuple[int, ...]) -> Tuple[Tensor, Tensor]:
+    dev = data.device
+    H = _prod(hidden)
+    pdata = torch.empty((dst.n_rows,) + tuple(hidden), dtype=data.dtype, device=dev)
+    sums = torch.empty((src.B,) + tuple(hidden), dtype=torch.float32, device=dev)
+    split, ws = split_workspace(src, H, data.dtype, dev, team_ok=False)      # (the fused kernel has no wave teams)
+    _call('to_pack', 'rua_pack_sums', dev, src.ref(), dst.ref(), L.ptr(data), L.ptr(pdata), L.ptr(sums), H,
+          L.DTYPES[data.dtype], split, L.ptr(ws))
+    return pdata, sums
+
+
+def launch_sums_cast(x: Tensor, dtype: torch.dtype, to_f32: bool, name: Optional[str] = None) -> Tensor:
+    """fp32 [B, *H] -> `dtype` (rounded as the reducer rounds its accumulators), or `dtype` -> fp32: a fresh tensor."""
+    dev = L.require_device(x)
+    x = x.contiguous()
+    out = torch.empty(x.shape, dtype=torch.float32 if to_f32 else dtype, device=dev)
+    args = (L.ptr(x), L.ptr(out), x.numel(), L.DTYPES[dtype], 1 if to_f32 else 0)
+    if name is None:
+        L.check(L.load().rua_sums_cast(*args, L.stream_ptr(dev)), 'rua_sums_cast')
+    else:
+        _call(name, 'rua_sums_cast', dev, *args)
+    return out
+
+
+class _SumsCast(torch.autograd.Function):
+    """The kept fp32 sums as reduce_sum's output; its adjoint widens the cotangent back (exact)."""
+
+    @staticmethod
+    def forward(ctx, sums: Tensor, dtype: torch.dtype):
+        ctx.dtype = dtype
+        return launch_sums_cast(sums, dtype, False, name='reduce')
+
+    @staticmethod
+    def backward(ctx, grad: Tensor):
+        if torch.is_grad_enabled():          # create_graph: torch's own cast carries the graph on
+            return grad.to(torch.float32), None
+        return launch_sums_cast(grad, ctx.dtype, True), None
+
+
+class _PackSums(torch.autograd.Function):
+    """(payload of the PackedSequence, fp32 sums) = rua_pack_sums(source).  The adjoint takes whichever cotangents
+    arrive: the payload's alone is the adjoint move P -> source; the sums' alone is the reduce's backward over the SOURCE
+    layout (a broadcast of every sequence's row over its rows: one write of the payload); both at once are ONE kernel
+    (rua_pack_sums_backward: one read, one write).  Under create_graph the same is spelled with the differentiable
+    two-op pieces (_Move, _ReduceBwd): the fused kernels differentiate once."""
+
+    @staticmethod
+    def forward(ctx, data: Tensor, src: M.Lay, dst: M.Lay, hidden: Tuple[int, ...]):
+        ctx.src, ctx.dst, ctx.hidden, ctx.shape, ctx.dtype = src, dst, tuple(hidden), tuple(data.shape), data.dtype
+        ctx.set_materialize_grads(False)
+        return launch_pack_sums(data, src, dst, hidden)
+
+    @staticmethod
+    def backward(ctx, g_pack: Optional[Tensor], g_sums: Optional[Tensor]):
+        if g_pack is None and g_sums is None:
+            return None, None, None, None
+        src, dst, hidden = ctx.src, ctx.dst, ctx.hidden
+        to_src = MovePlan(src, dst, ctx.shape, name='to_pack_bwd')
+        if torch.is_grad_enabled():
+            g = None
+            if g_pack is not None:
+                g = _Move.apply(g_pack.contiguous(), to_src)
+            if g_sums is not None:
+                gs = g_sums.to(ctx.dtype).contiguous()
+                # (sum reads neither x nor out: `ref` only carries the source's shape and dtype — one element, expanded)
+                ref = torch.empty((1,) * len(ctx.shape), dtype=ctx.dtype, device=gs.device).expand(ctx.shape)
+                spread = _ReduceBwd.apply(gs, ref, gs.detach(), src, L.SUM, None)
+                g = spread if g is None else g + spread
+            return g, None, None, None
+        if g_sums is None:
+            return launch_move(to_src, g_pack), None, None, None
+        dev = g_sums.device
+        g_sums = g_sums.contiguous()
+        H = _prod(hidden)
+        if g_pack is not None:
+            g_pack = g_pack.contiguous()
+            if (H * g_pack.element_size()) % 16 == 0 and (g_pack.data_ptr() | g_sums.data_ptr()) % 16 == 0:
+                g = torch.empty(ctx.shape, dtype=ctx.dtype, device=dev)
+                L.check(L.load().rua_pack_sums_backward(src.ref(), dst.ref(), L.ptr(g_pack), L.ptr(g_sums), L.ptr(g), H,
+                                                        L.DTYPES[ctx.dtype], L.stream_ptr(dev)), 'rua_pack_sums_backward')
+                return g, None, None, None
+        # the sums' cotangent alone: its rows in the payload dtype, spread over the source rows by the reduce's backward
+        gs = g_sums if ctx.dtype == torch.float32 else launch_sums_cast(g_sums, ctx.dtype, False)
+        g = torch.empty(ctx.shape, dtype=ctx.dtype, device=dev)
+        split, ws = split_workspace(src, H, ctx.dtype, dev, team_ok=False)
+        # (sum reads neither x nor out: both stand-ins are the read-only cotangent, never the buffer being written)
+        L.check(L.load().rua_segment_reduce_backward(src.ref(), None, L.ptr(gs), L.ptr(gs), L.ptr(gs), L.ptr(g), H,
+                                                     L.DTYPES[ctx.dtype], L.SUM, L.BWD_FILL_PADDING, split, L.ptr(ws),
+                                                     None, None, L.stream_ptr(dev)), 'rua_segment_reduce_backward')
+        if g_pack is not None:        # (rows off 16 bytes cannot get here: the forward would not have run)
+            g += launch_move(to_src, g_pack)
+        return g, None, None, None
+
+
+def pack_sums(data: Tensor, src: M.Lay, dst: M.Lay, hidden: Tuple[int, ...]) -> Tuple[Tensor, Tensor]:
+    """(payload of the PackedSequence `dst`, fp32 [B, *hidden] sums) of the source `src`, recorded by autograd."""
+    if data.requires_grad and torch.is_grad_enabled():
+        return _PackSums.apply(data, src, dst, tuple(hidden))
+    return launch_pack_sums(_plain(data), src, dst, tuple(hidden))
+
+
+def keep_sums(p, sums: Tensor) -> None:
+    """Record `sums` as the per-sequence sums of the PackedSequence `p` whose payload this pass just wrote: on the payload
+    tensor, under its version (an in-place write invalidates them), with the metadata objects they belong to."""
+    M._memo_put(p.data, _SUMS_KEY, (sums, p.batch_sizes, p.sorted_indices, p.unsorted_indices))
+
+
+def kept_sums(p) -> Optional[Tensor]:
+    """The fp32 sums pack() left on this very PackedSequence — same payload tensor at the same version, same
+    batch_sizes / index tensors — or None (a sliced, re-built or foreign PackedSequence; a payload written since)."""
+    hit = M._memo_get(p.data, _SUMS_KEY)
+    if hit is None or hit[1] is not p.batch_sizes or hit[2] is not p.sorted_indices or hit[3] is not p.unsorted_indices:
+        return None
+    return hit[0]
+
+
+def reduce_kept_sums(sums: Tensor, dtype: torch.dtype) -> Tensor:
+    """reduce_sum from the kept sums: ONE small launch (fp32 [B, H] -> dtype), a fresh tensor every call."""
+    if sums.requires_grad and torch.is_grad_enabled():
+        return _SumsCast.apply(sums, dtype)
+    return launch_sums_cast(_plain(sums), dtype, False, name='reduce')
+
+
 # ------------------------------------------------------------------ per-sequence softmax / log_softmax (an extension)
 _SOFTMAX_SUPPORT = 'softmax / log_softmax support'
 

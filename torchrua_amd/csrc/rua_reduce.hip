@@ -9,6 +9,7 @@
 #include <mutex>
 #include <string>
 #include "rua_reduce_impl.h"
+#include "rua_pack_sums_plan.h"
 
 namespace rua {
 // the dispatch trace (rua_debug_trace): process-global — autograd runs the backward on a thread of its own — and
@@ -85,16 +86,18 @@ static const ReduceEntry* entry_for(int dtype) {
 // plan, trace if on, launch.  `dry` (rua_debug_reduce_plan): the plan's records go there and nothing is launched.
 static int dispatch_reduce(int dtype, int op, hipStream_t s, const rua_layout& L, const int64_t* perm, const void* data,
                            void* out, int64_t H, int include_self, uint64_t empty_bits, void* extreme, int64_t split,
-                           void* ws, const rua_layout* CD, void* copy, void* ties, int hints, std::string* dry) {
+                           void* ws, const rua_layout* CD, void* copy, void* ties, int hints, std::string* dry,
+                           void* acc_out = nullptr) {
   const ReduceEntry* E = entry_for(dtype);
   if (!E) return RUA_EINVAL;
   const ReducePlan P = plan_reduce(L, E->esize, H, op, include_self, perm != nullptr, ws != nullptr, ties != nullptr,
-                                   copy != nullptr, (uintptr_t)data | (uintptr_t)out | (uintptr_t)copy | (uintptr_t)ties,
+                                   copy != nullptr,
+                                   (uintptr_t)data | (uintptr_t)out | (uintptr_t)copy | (uintptr_t)ties | (uintptr_t)acc_out,
                                    split, hints);
   if (P.err) return P.err;
   if (dry) trace_reduce(P, E->name, [&](const char* r) { dry->append(r).push_back('\n'); });
   else if (tracing()) trace_reduce(P, E->name, trace_add);
-  return dry ? 0 : E->reduce(P, s, L, perm, data, out, H, include_self, empty_bits, extreme, ws, CD, copy, ties);
+  return dry ? 0 : E->reduce(P, s, L, perm, data, out, H, include_self, empty_bits, extreme, ws, CD, copy, ties, acc_out);
 }
 
 constexpr int EXTREME_WORDS_ENTRY = RUA_EXTREME_WORDS;     // 1 024 slots, flags, the reset ticket, one spare
@@ -183,6 +186,7 @@ static int pack_reduce(const rua_layout* src, const rua_layout* pack, const void
   return dispatch_reduce(dtype, op, s, *src, nullptr, data, out, H, 0, empty_bits, extreme, split_rows, ws, pack, pack_data,
                          nullptr, hints, dry);
 }
+
 }  // namespace rua
 
 using namespace rua;
@@ -284,6 +288,44 @@ int rua_pack_reduce(const rua_layout* src, const rua_layout* pack, const void* d
                     int64_t H, int32_t dtype, int32_t op, uint64_t empty_bits, void* extreme, int64_t split_rows,
                     void* ws, void* stream) {
   return pack_reduce(src, pack, data, pack_data, out, H, dtype, op, empty_bits, extreme, split_rows, ws, stream, nullptr);
+}
+
+int rua_pack_sums(const rua_layout* src, const rua_layout* pack, const void* data, void* pack_data, float* sums,
+                  int64_t H, int32_t dtype, int64_t split_rows, void* ws, void* stream) {
+  const int rc = pack_sums_check(src, pack, H, dtype);
+  if (rc) return rc;
+  if (src->B == 0 || H == 0) return 0;
+  if (!sums || !pack_data || !data) return RUA_EINVAL;
+  // (the plan answers RUA_EALIGN for rows or pointers off 16 bytes, before anything is launched)
+  return dispatch_reduce(dtype, RUA_SUM, (hipStream_t)stream, *src, nullptr, data, nullptr, H, 0, 0, nullptr, split_rows, ws,
+                         pack, pack_data, nullptr, 0, nullptr, sums);
+}
+
+int rua_pack_sums_backward(const rua_layout* src, const rua_layout* pack, const void* grad_pack, const float* grad_sums,
+                           void* grad_src, int64_t H, int32_t dtype, void* stream) {
+  const int rc = pack_sums_check(src, pack, H, dtype);
+  if (rc) return rc;
+  if (src->B == 0 || H == 0 || src->n_rows == 0) return 0;
+  if (!grad_pack || !grad_sums || !grad_src) return RUA_EINVAL;
+  const ReduceEntry* E = entry_for(dtype);
+  const PackSumsBackwardPlan P = plan_pack_sums_backward(src->B, H, E->esize,
+                                                         (uintptr_t)grad_pack | (uintptr_t)grad_sums | (uintptr_t)grad_src);
+  if (P.err) return P.err;
+  const bool nt = reduce_nt(src->n_rows, H, E->esize);
+  if (tracing())
+    trace_add(fmt("pack_sums_backward_kernel T=%s EPL=%d NT=%d chunks=%lld", E->name, P.epl, nt ? 1 : 0,
+                  (long long)P.n_chunks).c_str());
+  return E->pack_sums_backward((hipStream_t)stream, *src, *pack, grad_pack, grad_sums, grad_src, H, P.lp_log2, P.n_chunks, nt);
+}
+
+int rua_sums_cast(const void* in, void* out, int64_t n, int32_t dtype, int32_t to_f32, void* stream) {
+  if (n < 0 || (dtype != RUA_F32 && dtype != RUA_BF16 && dtype != RUA_F16)) return RUA_EINVAL;
+  if (n == 0) return 0;
+  if (!in || !out || in == out) return RUA_EINVAL;
+  const ReduceEntry* E = entry_for(dtype);
+  const uintptr_t narrow = (uintptr_t)(to_f32 ? in : out), wide = (uintptr_t)(to_f32 ? out : in);
+  if (narrow % E->esize != 0 || wide % 4 != 0) return RUA_EALIGN;
+  return E->sums_cast((hipStream_t)stream, in, out, n, to_f32 ? 1 : 0);
 }
 
 int rua_fill_empty(const rua_layout* lay, void* out, int64_t H, int32_t dtype, int32_t op, void* extreme,

@@ -461,19 +461,34 @@ __device__ __forceinline__ void fold_merge(Fold<A, EPL>& f, const A* acc2, const
 template <typename T, int EPL, int OP, int CPW = 1, bool RANKS = false>
 __device__ __forceinline__ void fold_store(const Unit<T, EPL>& U, Fold<typename elem<T>::acc, EPL * CPW>& f,
                                            T* __restrict__ out, int64_t H, int include_self, T empty_val,
-                                           typename elem<T>::acc* __restrict__ ties = nullptr) {
+                                           typename elem<T>::acc* __restrict__ ties = nullptr,
+                                           typename elem<T>::acc* __restrict__ acc_out = nullptr) {
   using A = typename elem<T>::acc;
   constexpr int CW = RUA_WAVE * EPL;
   const bool keep = include_self == 2 && U.len <= 0;
   const bool inc = include_self == 1;
   if (U.colok && U.rsub == 0 && !keep) {       // (RANKS: rsub = the row slot inside the sequence's group)
     const int64_t cnt = U.len + (inc ? 1 : 0);
+    if (acc_out) {
+      // rua_pack_sums: the accumulators themselves, not rounded — one fp32 side buffer serves any later output dtype.
+      // A lane's EPL accumulators of a chunk go out as 16-byte vectors (the plan admits 16-byte lanes and bases only)
+      struct alignas((sizeof(A) * EPL) % 16 == 0 ? 16 : sizeof(A)) AccV { A v[EPL]; };
+#pragma unroll
+      for (int c = 0; c < CPW; ++c) {
+        if (CPW > 1 && U.col + c * CW >= H) continue;
+        AccV v;
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) v.v[e] = f.acc[c * EPL + e];
+        *reinterpret_cast<AccV*>(acc_out + U.b * H + U.col + c * CW) = v;
+      }
+      return;
+    }
 #pragma unroll
     for (int ce = 0; ce < EPL * CPW; ++ce) {
       const int c = ce / EPL, e = ce % EPL;
       if (CPW > 1 && U.col + c * CW >= H) continue;
-      T* o = out + U.b * H + U.col + c * CW;
       A r = f.acc[ce];
+      T* o = out + U.b * H + U.col + c * CW;
       if (OP == RUA_LOGSUMEXP) {
         if (inc) {  // fold exp(self) in
           const A x = elem<T>::up(o[e]);
@@ -577,6 +592,7 @@ struct SplitWs {
   int64_t max_u;      // bound on extra items and on long units
   int64_t split;      // rows per part (0 = splitting off)
   void* ties;         // [B, H] accumulators of the tie-counting max/min (RUA_MAX_T / RUA_MIN_T), else NULL
+  void* acc_out;      // [B, H] accumulators the fused pack + sum stores INSTEAD of the rounded `out` (rua_pack_sums), else NULL
 };
 
 template <typename A, int EPL, int OP>
@@ -638,7 +654,7 @@ __global__ __launch_bounds__(RUA_WAVE * WPB) void seg_reduce_kernel(rua_layout L
   } else {
     fold_rows<T, EPL, OP, NT, COPY, CPW>(U, 0, U.len, data, H, f, CD, copy, lane, 0, 1, track);
     fold_wave<A, NE, OP>(f, lp_log2);
-    fold_store<T, EPL, OP, CPW>(U, f, out, H, include_self, empty_val, (A*)W.ties);
+    fold_store<T, EPL, OP, CPW>(U, f, out, H, include_self, empty_val, (A*)W.ties, COPY ? (A*)W.acc_out : nullptr);
   }
   fold_flags<A, NE, OP>(f, extreme, lane, U.len <= 0, track);
 }
@@ -847,7 +863,7 @@ __global__ __launch_bounds__(RUA_WAVE * (COMBINE_WAVES_MAX / CPW)) void seg_redu
     combine_range<A, NE, OP>(f, P, pbase, 0, nparts, lane);
     const Unit<T, EPL> U = copy_mode ? make_unit<T, EPL, true, CPW>(L, CD, perm, e[0], e[1], H, lp_log2, lane)
                                      : make_unit<T, EPL, false, CPW>(L, CD, perm, e[0], e[1], H, lp_log2, lane);
-    fold_store<T, EPL, OP, CPW>(U, f, out, H, include_self, empty_val, (A*)W.ties);
+    fold_store<T, EPL, OP, CPW>(U, f, out, H, include_self, empty_val, (A*)W.ties, copy_mode ? (A*)W.acc_out : nullptr);
   }
 
   // pass B: the whole workgroup per unit with many parts (block-uniform loop and condition)
@@ -874,7 +890,7 @@ __global__ __launch_bounds__(RUA_WAVE * (COMBINE_WAVES_MAX / CPW)) void seg_redu
       }
       const Unit<T, EPL> U = copy_mode ? make_unit<T, EPL, true, CPW>(L, CD, perm, e[0], e[1], H, lp_log2, lane)
                                        : make_unit<T, EPL, false, CPW>(L, CD, perm, e[0], e[1], H, lp_log2, lane);
-      fold_store<T, EPL, OP, CPW>(U, f, out, H, include_self, empty_val, (A*)W.ties);
+      fold_store<T, EPL, OP, CPW>(U, f, out, H, include_self, empty_val, (A*)W.ties, copy_mode ? (A*)W.acc_out : nullptr);
     }
   }
 }
@@ -1612,6 +1628,8 @@ static SplitWs carve_ws(void* ws, int64_t max_u, int64_t split) {
   W.partials = (void*)p;
   W.max_u = max_u;
   W.split = split;
+  W.ties = nullptr;
+  W.acc_out = nullptr;
   return W;
 }
 
@@ -1649,7 +1667,7 @@ static void with_epl(int epl, F&& f) {
 template <typename T>
 static int launch_reduce(const ReducePlan& P, hipStream_t s, const rua_layout& L, const int64_t* perm, const void* data,
                          void* out, int64_t H, int include_self, uint64_t empty_bits, void* extreme, void* ws,
-                         const rua_layout* CD, void* copy, void* ties) {
+                         const rua_layout* CD, void* copy, void* ties, void* acc_out) {
   using A = typename elem<T>::acc;
   constexpr int FULL = 16 / sizeof(T), HALF = FULL >= 4 ? FULL / 2 : 1;
   T ev;
@@ -1665,6 +1683,7 @@ static int launch_reduce(const ReducePlan& P, hipStream_t s, const rua_layout& L
     if (e != hipSuccess) return (int)e;
   }
   W.ties = ties;
+  W.acc_out = copy ? acc_out : nullptr;
   const dim3 g(P.grid), b(RUA_WAVE);
   const int rc = with_op<true>(P.op, P.ties, [&](auto op_c) {
     constexpr int OP = decltype(op_c)::value;
@@ -1805,6 +1824,10 @@ static int launch_backward(const BackwardPlan& P, hipStream_t s, const rua_layou
   return rc ? rc : (int)hipGetLastError();
 }
 
+}  // namespace rua
+#include "rua_pack_sums.h"     // the kernels of pack(keep_sums=...): the adjoint of the fused pack + sum, the sums' cast
+namespace rua {
+
 // ---- per-dtype entry points: each element type is compiled in its own translation unit (rua_reduce_<dtype>.hip) so
 // the ~300 kernel instantiations build in parallel; rua_reduce.hip reaches them through entry_for(dtype)
 struct ReduceEntry {
@@ -1812,13 +1835,17 @@ struct ReduceEntry {
   int esize;
   int (*reduce)(const ReducePlan& P, hipStream_t s, const rua_layout& L, const int64_t* perm, const void* data, void* out,
                 int64_t H, int include_self, uint64_t empty_bits, void* extreme, void* ws, const rua_layout* CD,
-                void* copy, void* ties);
+                void* copy, void* ties, void* acc_out);
   int (*backward)(const BackwardPlan& P, hipStream_t s, const rua_layout& L, const int64_t* perm, const void* data,
                   const void* out, const void* gout, void* gin, int64_t H, int extra_count, void* ws, void* ties,
                   const void* self_in);
   int (*fill_empty)(hipStream_t s, const rua_layout& L, void* out, int64_t H, int want_max, void* ext, int reset);
   int (*self_grad)(hipStream_t s, const int64_t* counts, int64_t S, int64_t H, const void* self_in, const void* out,
                    const void* gout, const void* aux, void* gself, int op, int inc);
+  // rua_pack_sums_backward / rua_sums_cast (16-byte lanes; lp_log2 and n_chunks as plan_reduce counts them at CPW == 1)
+  int (*pack_sums_backward)(hipStream_t s, const rua_layout& L, const rua_layout& CD, const void* gpack, const void* gsums,
+                            void* gsrc, int64_t H, int lp_log2, int64_t n_chunks, bool nt);
+  int (*sums_cast)(hipStream_t s, const void* in, void* out, int64_t n, int to_acc);
 };
 const ReduceEntry &reduce_entry_f32(), &reduce_entry_bf16(), &reduce_entry_f16(), &reduce_entry_f64();
 
@@ -1840,7 +1867,7 @@ static int launch_self_grad(hipStream_t s, const int64_t* counts, int64_t S, int
 #define RUA_DEFINE_REDUCE_DTYPE(NAME, T)                                                                   \
   const rua::ReduceEntry& rua::reduce_entry_##NAME() {                                                     \
     static const ReduceEntry e = {#NAME, (int)sizeof(T), launch_reduce<T>, launch_backward<T>, launch_fill_empty<T>, \
-                                  launch_self_grad<T>};                                                    \
+                                  launch_self_grad<T>, launch_pack_sums_backward<T>, launch_sums_cast<T>};  \
     return e;                                                                                              \
   }
 

@@ -82,6 +82,15 @@ def _reduce_seq(sequence: Z, op: int) -> T:
 
 
 def reduce_sum(sequence: Z) -> T:
+    """Per-sequence sums, [B, *H] in batch order.  Over a PackedSequence that `pack()` returned with its sums kept
+    (core `pack(keep_sums=...)`) — the very payload tensor, unwritten since, with the batch_sizes and index tensors
+    pack() handed out — this is one small launch that rounds the kept fp32 sums to the payload dtype: the payload is not
+    read again.  Anything else (another op, a sliced or re-built PackedSequence, one from torch.nn.utils.rnn, a payload
+    written in place) walks the payload as before.  A fresh tensor every call."""
+    if isinstance(sequence, P):
+        kept = O.kept_sums(sequence)
+        if kept is not None:
+            return O.reduce_kept_sums(kept, sequence.data.dtype)
     return _reduce_seq(sequence, K.SUM)
 
 
@@ -325,6 +334,11 @@ _OPS = {'sum': K.SUM, 'mean': K.MEAN, 'max': K.MAX, 'min': K.MIN, 'prod': K.PROD
 FUSED_MIN_UNITS = 16384      # below this many (sequence, column chunk) units pack_reduce takes the two-kernel form
 
 
+def fused_units(n_seq: int, row_bytes: int) -> int:
+    """(sequence, column chunk) units of the fused pack + reduce kernel: one wave each."""
+    return n_seq * (1 if row_bytes <= 1024 else -(-row_bytes // 4096))
+
+
 def pack_reduce(sequence: Z, op: str = 'sum', fused: bool = None):
     """(sequence.pack(), reduce_<op>(that PackedSequence)) in ONE pass over the payload.
 
@@ -349,9 +363,7 @@ def pack_reduce(sequence: Z, op: str = 'sum', fused: bool = None):
     # the two-kernel form moves rows at tile granularity and reduces with teams of waves (B = 4 096, H = 256: 0.93 ms
     # fused against 0.29 ms for pack + reduce)
     n_seq = int(sequence.token_sizes.numel()) if not isinstance(sequence, P) else 0
-    row_bytes = H * data.element_size()
-    n_chunks = 1 if row_bytes <= 1024 else -(-row_bytes // 4096)
-    if fused is False or (fused is None and n_seq * n_chunks < FUSED_MIN_UNITS):     # fused=True: whenever it can
+    if fused is False or (fused is None and fused_units(n_seq, H * data.element_size()) < FUSED_MIN_UNITS):     # fused=True: whenever it can
         fusable = False
     if not fusable:
         p = sequence.pack()
