@@ -645,6 +645,64 @@ int rua_segment_crf_backward(const rua_layout* lay, const void* grad, const void
                              void* grad_start /* NULL */, void* grad_end /* NULL */, int32_t K, int32_t dtype, void* ws,
                              void* stream);
 
+/* Per-sequence CTC (an EXTENSION, added to ABI 6 — the version number did not move): the loss, its TRUE gradient and the
+ * forced alignment (csrc/rua_ctc.hip).  The first entry points that read two ragged containers at once: `frames`
+ * describes `log_probs` (rows of V elements of `dtype`, RUA_F32 / RUA_F64 / RUA_BF16 / RUA_F16, ANY layout), `targets`
+ * describes `labels` (int64, one per row, ANY layout, independently of `frames`); both have the same B and sequence b is
+ * the same sequence in both (a PACK layout: through `unsorted`).  0 <= S_max <= RUA_CTC_MAX_TARGET bounds the labels of
+ * a sequence (longer ones are cut to it: the caller sizes the launch by the longest target); 0 <= blank < V.  The
+ * per-sequence results and the table `alpha` are in the ACCUMULATOR type (float; double for RUA_F64).
+ *
+ * The extended target is l' = (blank, y_0, blank, ..., y_{S-1}, blank), S' = 2 S + 1 states.  Geometry: the lanes form
+ * (2 S_max + 1 <= 512) walks a sequence with ONE wave, lane i keeping the R = 1 / 2 / 4 / 8 consecutive states
+ * i R .. i R + R - 1 in registers (2 S_max + 1 <= 64 / 128 / 256 / 512), the boundary values coming from lane i - 1 by a
+ * cross-lane move; the workgroup form (up to 2 047 states) walks it with one workgroup, 8 states per thread, the
+ * boundary values through LDS with one barrier per frame.  At most 1 024 workgroups; the teams stride over b.  ONE long
+ * target sends the whole batch to the workgroup form; one wave / workgroup walks ALL the frames of a sequence.
+ *
+ * ONE evaluation order per (sequence, frame, state), whatever the layouts, the form or R (no contraction):
+ *   v0 = alpha[s], v1 = alpha[s-1] (s >= 1), v2 = alpha[s-2] (s >= 2, l'_s != blank, l'_s != l'_{s-2}); a term that does
+ *   not exist is absent.  RUA_CRF_LOG: m = max (a NaN stays one); m == -inf gives -inf; else
+ *   alpha_t[s] = lp_t[l'_s] + (m + log(exp(v0 - m) + exp(v1 - m) [+ exp(v2 - m)])).  RUA_CRF_MAX: the maximum in ascending
+ *   predecessor state (s-2, s-1, s) under rua_segment_argreduce's order (a NaN beats every number, the first of equals
+ *   wins); s minus the predecessor is the code of (row, state); -inf stays -inf.  alpha_0[0] = lp_0[blank],
+ *   alpha_0[1] = lp_0[y_0], -inf elsewhere.  The end folds alpha_{T-1}[S'-1], then alpha_{T-1}[S'-2], the same way.
+ *
+ * rua_segment_ctc_forward: RUA_CRF_LOG writes out[b] = -logZ (0 instead of +inf when zero_infinity != 0), `logz` [B]
+ *   (may be NULL) and `alpha` [rows of the frames' storage, 2 S_max + 1] (may be NULL; padding rows and the states
+ *   >= S' are not written).  RUA_CRF_MAX writes out[b] = the best path's log-probability, `last` [B] int64 (its final
+ *   state; -1: there is no alignment) and `codes` (one uint8 per (row, state); the rows of frame 0 are not written),
+ *   both required.  T = 0: 0 for S = 0, else no alignment (logZ = -inf).  A label outside [0, V) is never dereferenced:
+ *   out[b] = logz[b] = NaN, last[b] = -1.
+ * rua_segment_ctc_backtrace: a thread per sequence walks `codes` from `last` and writes `out_labels` (the class of
+ *   every frame) and `out_positions` (the index into the sequence's own target, -1 for a blank frame), int64, one per
+ *   row of the frames' storage, zeros in padding rows; a sequence without alignment gets `blank` and -1.
+ * rua_segment_ctc_backward (of RUA_CRF_LOG; `grad` [B] the cotangent of out): beta WITHOUT the emission at t,
+ *   beta_{T-1}[S'-1] = beta_{T-1}[S'-2] = 0, u_s = lp_{t+1}[l'_s] + beta_{t+1}[s], beta_t[s] = the same logsumexp of u_s,
+ *   u_{s+1}, u_{s+2}; grad_log_probs[t, c] = -grad[b] * sum_{s : l'_s = c} exp((alpha_t[s] + beta_t[s]) - logz[b]),
+ *   rounded once; every V-wide row is written exactly once, zeros included; padding rows, sequences with
+ *   logz == -inf and sequences with a label outside [0, V) get exact zeros.  NO FLOAT ATOMICS; the class sum is, for
+ *   c != blank, the states of c in ascending s added from 0; for blank, lane i of 64 adds post[2 k] and then
+ *   post[2 k + 1] when y_k == blank over k = i, i + 64, ... from 0 and the 64 parts are folded by the butterfly
+ *   xor 32 .. 1.  Bitwise reproducible and identical for every pair of layouts and for both forms.  No workspace.
+ *
+ * Checks, before any HIP call: a null layout, different B, a dtype outside the four, V < 1, S_max outside
+ * [0, RUA_CTC_MAX_TARGET], blank outside [0, V), an unknown semiring (RUA_EINVAL); B == 0 returns 0 without a launch; a
+ * missing required pointer (RUA_EINVAL); a table too large for 64-bit offsets (RUA_ERANGE); a pointer not aligned to
+ * its element (RUA_EALIGN).  Trace: `seg_ctc_forward_kernel` (T=, V=, S_max=, form=, R=, semiring=, alpha=, kind=,
+ * tkind=, grid=), `seg_ctc_backtrace_kernel`, `seg_ctc_backward_kernel`. */
+#define RUA_CTC_MAX_TARGET 1023
+int rua_segment_ctc_forward(const rua_layout* frames, const rua_layout* targets, const void* log_probs,
+                            const void* labels, void* alpha /* NULL */, void* codes, void* out, void* logz /* NULL */,
+                            void* last, int32_t V, int32_t S_max, int32_t blank, int32_t dtype, int32_t semiring,
+                            int32_t zero_infinity, void* stream);
+int rua_segment_ctc_backtrace(const rua_layout* frames, const rua_layout* targets, const void* labels, const void* codes,
+                              const void* last, void* out_labels, void* out_positions, int32_t V, int32_t S_max,
+                              int32_t blank, void* stream);
+int rua_segment_ctc_backward(const rua_layout* frames, const rua_layout* targets, const void* grad,
+                             const void* log_probs, const void* labels, const void* alpha, const void* logz,
+                             void* grad_log_probs, int32_t V, int32_t S_max, int32_t blank, int32_t dtype, void* stream);
+
 /* Per-sequence gated linear recurrence (an EXTENSION, added to ABI 6 — the version number did not move: the reference's
  * users pad, loop over the time steps with elementwise kernels and cast back).  For every sequence b of `lay` (ANY
  * layout) and column h, with u the position along the scan (u = t; reverse != 0: u = len - 1 - t):

@@ -6,7 +6,7 @@ nothing maps to) — the same kernel.  Backward of a segmented reduce is one fus
 """
 import ctypes
 import threading
-from typing import Callable, Optional, Sequence, Tuple
+from typing import Callable, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor
@@ -1235,6 +1235,136 @@ def crf_partition(data: Tensor, transitions: Tensor, start: Optional[Tensor], en
         # contiguous HERE, before the Function (as in cumsum()): a copy made inside forward() would carry no history
         return _CrfPartition.apply(data.contiguous(), transitions, start, end, lay, K)
     return launch_crf_forward(lay, _plain(data), transitions, start, end, K)[0]
+
+
+# ------------------------------------------------------------------ per-sequence CTC (an extension)
+_CTC_SUPPORT = 'ctc: the log-probabilities are one of'
+
+
+def ctc_args(what: str, data: Tensor, hidden: Tuple[int, ...], n_seq: int, labels, label_hidden, n_target_seq: int,
+             blank, before_device: Optional[Callable[[], None]] = None) -> int:
+    """V, after the checks that come before any launch and need no lengths, each naming its argument: float
+    `log_probs` with exactly one hidden dimension (the V classes); int64 `targets` without hidden dimensions, with the
+    same number of sequences, on the same device; `blank` in [0, V); and last (so that every other refusal can be met
+    without a GPU) the log-probabilities on a HIP device."""
+    if data.dtype not in L.DTYPES:
+        raise L.RuaError(f'{what}: `log_probs` is one of {list(L.DTYPES)}; got {data.dtype}')
+    if len(hidden) != 1:
+        raise L.RuaError(f'{what}: `log_probs` has exactly ONE hidden dimension (the V classes); got hidden dimensions '
+                         f'{tuple(hidden)}')
+    V = int(hidden[0])
+    if not isinstance(labels, Tensor) or labels.dtype != torch.int64:
+        raise L.RuaError(f'{what}: `targets` holds torch.int64 labels; got '
+                         f'{labels.dtype if isinstance(labels, Tensor) else type(labels).__name__}')
+    if len(label_hidden):
+        raise L.RuaError(f'{what}: `targets` holds ONE label per token; got hidden dimensions {tuple(label_hidden)}')
+    if n_target_seq != n_seq:
+        raise L.RuaError(f'{what}: `targets` holds {n_target_seq} sequences, `log_probs` {n_seq}')
+    if labels.device != data.device:
+        raise L.RuaError(f'{what}: `targets` lives on {labels.device}, `log_probs` on {data.device}')
+    if isinstance(blank, bool) or not isinstance(blank, int) or not 0 <= blank < V:
+        raise L.RuaError(f'{what}: `blank` = {blank!r} is not a class of [0, {V})')
+    if before_device is not None:
+        before_device()
+    if not data.is_cuda:
+        raise L.RuaError(f'{what}: `log_probs` lives on {data.device}; move it to a HIP device (there is no CPU fallback '
+                         f'by design)')
+    return V
+
+
+def ctc_target_bound(what: str, s_max: int) -> int:
+    """The longest target of the batch, which sizes the launch.  Longer than CTC_MAX_TARGET: refused, before any launch."""
+    if s_max > L.CTC_MAX_TARGET:
+        raise L.RuaError(f'{what}: the longest of `targets` has {s_max} labels; at most {L.CTC_MAX_TARGET} '
+                         f'(2 S + 1 <= {2 * L.CTC_MAX_TARGET + 1} states)')
+    return max(s_max, 0)
+
+
+class CtcPlan(NamedTuple):
+    """What every CTC launch of one call shares: both layouts, V, the state bound and blank."""
+    frames: M.Lay
+    targets: M.Lay
+    V: int
+    S_max: int
+    blank: int
+
+
+def launch_ctc_forward(plan: CtcPlan, data: Tensor, labels: Tensor, viterbi: bool = False, want_alpha: bool = False,
+                       zero_infinity: bool = False):
+    """rua_segment_ctc_forward: ONE launch.  (out [B], logZ [B] or None, alpha [*storage, 2 S_max + 1] or None, codes or
+    None, last or None), in the accumulator type.  B == 0: empty results without a launch."""
+    code = _require_dtype(data, L.DTYPES, _CTC_SUPPORT)
+    dev, acc = data.device, _acc_dtype(data.dtype)
+    lay = plan.frames
+    data, labels = data.contiguous(), labels.contiguous()
+    table = tuple(data.shape[:-1]) + (2 * plan.S_max + 1,)
+    out = torch.empty(lay.B, dtype=acc, device=dev)
+    logz = torch.empty(lay.B, dtype=acc, device=dev) if not viterbi else None
+    alpha = torch.empty(table, dtype=acc, device=dev) if want_alpha and not viterbi else None
+    codes = torch.empty(table, dtype=torch.uint8, device=dev) if viterbi else None
+    last = torch.empty(lay.B, dtype=torch.int64, device=dev) if viterbi else None
+    if lay.B:
+        _call('ctc_align' if viterbi else 'ctc_loss', 'rua_segment_ctc_forward', dev, lay.ref(), plan.targets.ref(),
+              L.ptr(data), L.ptr(labels), L.ptr(alpha), L.ptr(codes), L.ptr(out), L.ptr(logz), L.ptr(last), plan.V,
+              plan.S_max, plan.blank, code, L.CRF_MAX if viterbi else L.CRF_LOG, int(bool(zero_infinity)))
+    return out, logz, alpha, codes, last
+
+
+def launch_ctc_backtrace(plan: CtcPlan, labels: Tensor, codes: Tensor, last: Tensor, lead_shape: Sequence[int]):
+    """rua_segment_ctc_backtrace: a launch of its own on the same stream; (labels, positions), int64, one per row."""
+    dev = codes.device
+    out_labels = torch.empty(tuple(lead_shape), dtype=torch.int64, device=dev)     # padding rows: zeroed by the call
+    out_positions = torch.empty(tuple(lead_shape), dtype=torch.int64, device=dev)
+    if plan.frames.B and out_labels.numel():
+        labels = labels.contiguous()
+        _call('ctc_backtrace', 'rua_segment_ctc_backtrace', dev, plan.frames.ref(), plan.targets.ref(), L.ptr(labels),
+              L.ptr(codes), L.ptr(last), L.ptr(out_labels), L.ptr(out_positions), plan.V, plan.S_max, plan.blank)
+    return out_labels, out_positions
+
+
+def launch_ctc_backward(plan: CtcPlan, grad: Tensor, data: Tensor, labels: Tensor, alpha: Tensor, logz: Tensor) -> Tensor:
+    """rua_segment_ctc_backward: the gradient of the log-probabilities, every row written once by ONE launch."""
+    code = _require_dtype(data, L.DTYPES, _CTC_SUPPORT)
+    dev, acc = data.device, _acc_dtype(data.dtype)
+    lay = plan.frames
+    L.require_device(grad, data, labels, alpha, logz)
+    if grad.dtype != acc or tuple(grad.shape) != (lay.B,):
+        raise L.RuaError(f'ctc backward: the cotangent of the loss is a {acc} tensor of shape ({lay.B},)')
+    gx = torch.empty(data.shape, dtype=data.dtype, device=dev)
+    if lay.B and gx.numel():
+        # bound to names until the launch is queued (see launch_crf_backward)
+        grad, data, labels, alpha, logz = (grad.contiguous(), data.contiguous(), labels.contiguous(), alpha.contiguous(),
+                                           logz.contiguous())
+        _call('ctc_loss_bwd', 'rua_segment_ctc_backward', dev, lay.ref(), plan.targets.ref(), L.ptr(grad), L.ptr(data),
+              L.ptr(labels), L.ptr(alpha), L.ptr(logz), L.ptr(gx), plan.V, plan.S_max, plan.blank, code)
+    return gx
+
+
+class _CtcLoss(torch.autograd.Function):
+    """The negative log-likelihood [B] of every sequence.  Saves the forward table alpha ([rows, 2 S_max + 1],
+    accumulator type, the frames' storage layout), logZ, the log-probabilities and the labels; the backward is one
+    fused walk.  Second derivatives are out of scope."""
+
+    @staticmethod
+    def forward(ctx, data: Tensor, labels: Tensor, plan: CtcPlan, zero_infinity: bool):
+        loss, logz, alpha, _, _ = launch_ctc_forward(plan, data, labels, want_alpha=True, zero_infinity=zero_infinity)
+        ctx.plan = plan
+        ctx.save_for_backward(data, labels, alpha, logz)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad: Tensor):
+        if torch.is_grad_enabled():
+            raise L.RuaError('ctc_loss: second derivatives (create_graph=True) are out of scope')
+        data, labels, alpha, logz = ctx.saved_tensors
+        return launch_ctc_backward(ctx.plan, grad, data, labels, alpha, logz), None, None, None
+
+
+def ctc_loss(data: Tensor, labels: Tensor, plan: CtcPlan, zero_infinity: bool) -> Tensor:
+    if torch.is_grad_enabled() and data.requires_grad:
+        # contiguous HERE, before the Function (as in cumsum()): a copy made inside forward() would carry no history
+        return _CtcLoss.apply(data.contiguous(), labels, plan, bool(zero_infinity))
+    return launch_ctc_forward(plan, _plain(data), labels, zero_infinity=zero_infinity)[0]
 
 
 # ------------------------------------------------------------------ per-sequence gated linear recurrence (an extension)
