@@ -703,6 +703,45 @@ int rua_segment_ctc_backward(const rua_layout* frames, const rua_layout* targets
                              const void* log_probs, const void* labels, const void* alpha, const void* logz,
                              void* grad_log_probs, int32_t V, int32_t S_max, int32_t blank, int32_t dtype, void* stream);
 
+/* Per-sequence edit distance and alignment (an EXTENSION, added to ABI 6 — the version number did not move): the
+ * Levenshtein distance of every hypothesis against its reference, and its split into substitutions, insertions and
+ * deletions (csrc/rua_edit.hip).  `hyp` describes `hyp_tokens`, `ref` describes `ref_tokens` (both int64,
+ * one per row, ANY layout, independently of each other); both have the same B and sequence b is the same sequence in
+ * both (a PACK layout: through `unsorted`).  Tokens are compared as 64-bit values: there is no vocabulary.
+ * 0 <= S_max <= RUA_EDIT_MAX_REF bounds the tokens of a reference (longer ones are cut to it: the caller sizes the launch
+ * by the longest reference); a hypothesis is as long as its storage allows.  The arithmetic is pure integer (int32 in
+ * registers: rows of `hyp` + S_max < 2^31, else RUA_ERANGE), every output is int64.
+ *
+ *   D[0][j] = j, D[i][0] = i, D[i][j] = min(D[i-1][j-1] + (hyp[i-1] != ref[j-1]), D[i-1][j] + 1, D[i][j-1] + 1).
+ *
+ * Geometry: a TEAM walks one pair, hyp token by hyp token, thread i keeping the R consecutive columns i R + 1 ..
+ * i R + R and their ref tokens in registers.  The lanes form (S_max <= 512) is one wave, R = 1 / 2 / 4 / 8 for
+ * S_max <= 64 / 128 / 256 / 512, four teams per workgroup; the workgroup form (S_max <= 2 048) is 256 threads with R = 8.
+ * At most 1 024 workgroups; the teams stride over b.  The dependence on the left neighbour is a prefix minimum, not a
+ * walk: with t[j] = min(Dprev[j-1] + neq, Dprev[j] + 1) and t[0] = i, D[j] = j + min_{k <= j} (t[k] - k) — an R-long
+ * chain in registers and ONE prefix-min across the team per row (a shuffle scan; across the four waves of the workgroup
+ * form through LDS with one barrier).  The same bits in every bucket and both forms.
+ *
+ * rua_segment_edit_forward: writes distance[b] = D[T][S].  `codes` NULL: nothing else.  Otherwise one uint8 per cell,
+ *   codes[row of hyp token i-1][j-1] for 1 <= j <= S, rows of the hyp storage S_max apart: 0 the diagonal attains
+ *   D[i][j] and the tokens are equal, 1 the diagonal attains it and they differ, else 2 up (D[i-1][j] + 1) attains it,
+ *   else 3 (left).  Padding rows and the columns >= S are not written.
+ * rua_segment_edit_backtrace: a thread per sequence walks `codes` from (T, S) — the diagonal if it attains D[i][j], else
+ *   up, else left; at j == 0 only up, at i == 0 only left — and writes `positions` (int64, one per row of the hyp
+ *   storage: the index into the sequence's own ref of the token hyp token t is paired with, -1 for an inserted token,
+ *   0 in padding rows) and `substitutions`, `insertions`, `deletions` [B] int64.
+ *
+ * Checks, before any HIP call: a null or malformed layout, different B, S_max outside [0, RUA_EDIT_MAX_REF]
+ * (RUA_EINVAL); B == 0 returns 0 without a launch; a missing required pointer (RUA_EINVAL; `codes` and `positions` may
+ * be NULL where they have no element); more rows than int32 distances hold (RUA_ERANGE); a pointer not aligned to 8 bytes
+ * (RUA_EALIGN).  Trace: `seg_edit_forward_kernel` (S_max=, form=, R=, codes=, kind=, rkind=, grid=),
+ * `seg_edit_backtrace_kernel`. */
+#define RUA_EDIT_MAX_REF 2048
+int rua_segment_edit_forward(const rua_layout* hyp, const rua_layout* ref, const void* hyp_tokens, const void* ref_tokens,
+                             void* distance, void* codes /* NULL */, int32_t S_max, void* stream);
+int rua_segment_edit_backtrace(const rua_layout* hyp, const rua_layout* ref, const void* codes, void* positions,
+                               void* substitutions, void* insertions, void* deletions, int32_t S_max, void* stream);
+
 /* Per-sequence gated linear recurrence (an EXTENSION, added to ABI 6 — the version number did not move: the reference's
  * users pad, loop over the time steps with elementwise kernels and cast back).  For every sequence b of `lay` (ANY
  * layout) and column h, with u the position along the scan (u = t; reverse != 0: u = len - 1 - t):

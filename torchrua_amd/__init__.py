@@ -32,6 +32,7 @@ from torchrua_amd.window import *  # noqa: F401,F403
 from torchrua_amd.cumext import *  # noqa: F401,F403
 from torchrua_amd.crf import *  # noqa: F401,F403
 from torchrua_amd.ctc import *  # noqa: F401,F403
+from torchrua_amd.edit import *  # noqa: F401,F403
 from torchrua_amd._lib import RuaError, load as load_library  # noqa: F401
 
 # BASELINE.json's names for the constructors (README.md:13 of the reference speaks of them too)

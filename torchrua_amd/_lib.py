@@ -38,6 +38,7 @@ WINDOW_MAX_K = 64          # rua.h: RUA_WINDOW_MAX_K, the longest window of rua_
 CRF_MAX_TAGS = 64          # rua.h: RUA_CRF_MAX_TAGS, the most tags of the linear-chain CRF (a lane per tag)
 CRF_LOG, CRF_MAX = 0, 1    # rua.h: RUA_CRF_LOG / RUA_CRF_MAX, the semiring of rua_segment_crf_forward
 CTC_MAX_TARGET = 1023      # rua.h: RUA_CTC_MAX_TARGET, the longest target of the CTC operators (2 S + 1 <= 2 047 states)
+EDIT_MAX_REF = 2048       # rua.h: RUA_EDIT_MAX_REF, the longest reference of the edit-distance operators (hyp is unbounded)
 WINDOW_TAKE = 6            # rua.h: RUA_WINDOW_TAKE, the fourth mode of rua_segment_window_pool / _spread (next to SUM, MEAN, MAX)
 # enum rua_dtype / rua_op
 F32, BF16, F16, F64 = 0, 1, 2, 3
@@ -142,6 +143,10 @@ SYMBOLS = {
                                           c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     'rua_segment_ctc_backward': (c_int, [POINTER(RuaLayout), POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    'rua_segment_edit_forward': (c_int, [POINTER(RuaLayout), POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_int32, c_void_p]),
+    'rua_segment_edit_backtrace': (c_int, [POINTER(RuaLayout), POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_int32, c_void_p]),
     'rua_linear_scan_ws_bytes': (c_int64, [POINTER(RuaLayout), c_int64, c_int32]),
     'rua_segment_linear_scan': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_double, c_void_p, c_int64, c_int32,
                                         c_int32, c_void_p, c_void_p]),

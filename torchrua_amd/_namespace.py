@@ -20,10 +20,10 @@ from torch import Tensor
 from importlib import import_module as _im
 
 # (import_module, not `from torchrua_amd import x`: the package attribute `compose` is the FUNCTION, as in the reference)
-_compose_mod, _core, _detach, _layout, _mask_mod, _reduce, _segment, _select, _utils, _softmax_mod, _cumsum_mod, _argmax_mod, _linear_scan_mod, _pool_mod, _norm_mod, _conv_mod, _compress_mod, _join_mod, _repeat_mod, _sort_mod, _unique_mod, _window_mod, _cumext_mod, _crf_mod, _ctc_mod = (
+_compose_mod, _core, _detach, _layout, _mask_mod, _reduce, _segment, _select, _utils, _softmax_mod, _cumsum_mod, _argmax_mod, _linear_scan_mod, _pool_mod, _norm_mod, _conv_mod, _compress_mod, _join_mod, _repeat_mod, _sort_mod, _unique_mod, _window_mod, _cumext_mod, _crf_mod, _ctc_mod, _edit_mod = (
     _im(f'torchrua_amd.{m}') for m in ('compose', 'core', 'detach', 'layout', 'mask', 'reduce', 'segment', 'select', 'utils',
                                        'softmax', 'cumsum', 'argmax', 'linear_scan', 'pool', 'norm', 'conv', 'compress', 'join', 'repeat',
-                                       'sort', 'unique', 'window', 'cumext', 'crf', 'ctc'))
+                                       'sort', 'unique', 'window', 'cumext', 'crf', 'ctc', 'edit'))
 from torchrua_amd.layout import C, L, P, R, T, Z, CattedSequence, LeftAlignedSequence, RightAlignedSequence, PackedSequence
 
 _PKG = 'torchrua_amd'
@@ -114,11 +114,11 @@ def build(pkg) -> None:
     _fill(_detach, DETACH)
     _fill(_utils, UTILS)
     _fill(_compose_mod, dict(invert_permutation=_utils.invert_permutation, List=List))
-    # (softmax.py, cumsum.py, argmax.py, linear_scan.py, pool.py, norm.py, conv.py, compress.py, join.py, repeat.py, sort.py, unique.py, window.py, cumext.py, crf.py, ctc.py — like `compose`, the package attributes `softmax`, `cumsum`,
+    # (softmax.py, cumsum.py, argmax.py, linear_scan.py, pool.py, norm.py, conv.py, compress.py, join.py, repeat.py, sort.py, unique.py, window.py, cumext.py, crf.py, ctc.py, edit.py — like `compose`, the package attributes `softmax`, `cumsum`,
     # `argmax`, `linear_scan` and `sort` are the FUNCTIONS: extensions the reference lacks)
     for mod in (_compose_mod, _core, _detach, _layout, _mask_mod, _reduce, _segment, _select, _utils, _softmax_mod,
                 _cumsum_mod, _argmax_mod, _linear_scan_mod, _pool_mod, _norm_mod, _conv_mod, _compress_mod, _join_mod, _repeat_mod,
-                _sort_mod, _unique_mod, _window_mod, _cumext_mod, _crf_mod, _ctc_mod):
+                _sort_mod, _unique_mod, _window_mod, _cumext_mod, _crf_mod, _ctc_mod, _edit_mod):
         _fill(mod, _TYPES)
     # the package itself: every public name of every submodule (torchrua/__init__.py:1-8), then the submodules
     for table in (CAST, GET, SET, VIEW, NEW, HEAD, LAST, REV, ROLL, TRUNC, SEG, MASK, DETACH, PACK, LAY_CAT,

@@ -1367,6 +1367,72 @@ def ctc_loss(data: Tensor, labels: Tensor, plan: CtcPlan, zero_infinity: bool) -
     return launch_ctc_forward(plan, _plain(data), labels, zero_infinity=zero_infinity)[0]
 
 
+# ------------------------------------------------------------------ per-sequence edit distance (an extension)
+def edit_args(what: str, hyp, hyp_hidden, n_seq: int, ref, ref_hidden, n_ref_seq: int,
+              before_device: Optional[Callable[[], None]] = None) -> None:
+    """The checks that come before any launch and need no lengths, each naming its argument: int64 `hyp` and `ref`
+    without hidden dimensions, with the same number of sequences, on the same device; and last (so that every other
+    refusal can be met without a GPU) the tokens on a HIP device."""
+    for name, t, hidden in (('hyp', hyp, hyp_hidden), ('ref', ref, ref_hidden)):
+        if not isinstance(t, Tensor) or t.dtype != torch.int64:
+            raise L.RuaError(f'{what}: `{name}` holds torch.int64 tokens; got '
+                             f'{t.dtype if isinstance(t, Tensor) else type(t).__name__}')
+        if len(hidden):
+            raise L.RuaError(f'{what}: `{name}` holds ONE token per position; got hidden dimensions {tuple(hidden)}')
+    if n_ref_seq != n_seq:
+        raise L.RuaError(f'{what}: `ref` holds {n_ref_seq} sequences, `hyp` {n_seq}')
+    if ref.device != hyp.device:
+        raise L.RuaError(f'{what}: `ref` lives on {ref.device}, `hyp` on {hyp.device}')
+    if before_device is not None:
+        before_device()
+    if not hyp.is_cuda:
+        raise L.RuaError(f'{what}: `hyp` lives on {hyp.device}; move it to a HIP device (there is no CPU fallback by '
+                         f'design)')
+
+
+def edit_ref_bound(what: str, s_max: int) -> int:
+    """The longest reference of the batch, which sizes the launch.  Longer than EDIT_MAX_REF: refused, before any launch."""
+    if s_max > L.EDIT_MAX_REF:
+        raise L.RuaError(f'{what}: the longest of `ref` has {s_max} tokens; at most {L.EDIT_MAX_REF} (`hyp` is unbounded: '
+                         f'swap the arguments — the distance is symmetric, insertions and deletions trade places)')
+    return max(s_max, 0)
+
+
+class EditPlan(NamedTuple):
+    """What both edit-distance launches of one call share: the two layouts and the column bound."""
+    hyp: M.Lay
+    ref: M.Lay
+    S_max: int
+
+
+def launch_edit_forward(plan: EditPlan, hyp: Tensor, ref: Tensor, want_codes: bool = False):
+    """rua_segment_edit_forward: ONE launch.  (distance [B] int64, codes [*hyp storage, S_max] uint8 or None).  The
+    distance-only launch allocates and writes no table.  B == 0: empty results without a launch."""
+    dev = L.require_device(hyp, ref)
+    hyp, ref = hyp.contiguous(), ref.contiguous()
+    dist = torch.empty(plan.hyp.B, dtype=torch.int64, device=dev)
+    codes = torch.empty(tuple(hyp.shape) + (plan.S_max,), dtype=torch.uint8, device=dev) if want_codes else None
+    if plan.hyp.B:
+        # (a table without an element has no address: the launch then writes none)
+        _call('edit_align' if want_codes else 'edit_distance', 'rua_segment_edit_forward', dev, plan.hyp.ref(),
+              plan.ref.ref(), L.ptr(hyp), L.ptr(ref), L.ptr(dist), L.ptr(codes) if want_codes and codes.numel() else 0,
+              plan.S_max)
+    return dist, codes
+
+
+def launch_edit_backtrace(plan: EditPlan, codes: Tensor, lead_shape: Sequence[int]):
+    """rua_segment_edit_backtrace: a launch of its own on the same stream; (positions, one per row of the hyp storage,
+    substitutions, insertions, deletions [B]), all int64."""
+    dev = codes.device
+    positions = torch.empty(tuple(lead_shape), dtype=torch.int64, device=dev)      # padding rows: zeroed by the call
+    subs, ins, dels = (torch.empty(plan.hyp.B, dtype=torch.int64, device=dev) for _ in range(3))
+    if plan.hyp.B:
+        _call('edit_backtrace', 'rua_segment_edit_backtrace', dev, plan.hyp.ref(), plan.ref.ref(),
+              L.ptr(codes) if codes.numel() else 0, L.ptr(positions) if positions.numel() else 0, L.ptr(subs),
+              L.ptr(ins), L.ptr(dels), plan.S_max)
+    return positions, subs, ins, dels
+
+
 # ------------------------------------------------------------------ per-sequence gated linear recurrence (an extension)
 def _gate_arg(data: Tensor, gate) -> Tuple[Optional[Tensor], float]:
     """(the gate tensor or None, the scalar gate): a tensor of the payload's storage shape, dtype and device, or ONE
