@@ -742,6 +742,38 @@ int rua_segment_edit_forward(const rua_layout* hyp, const rua_layout* ref, const
 int rua_segment_edit_backtrace(const rua_layout* hyp, const rua_layout* ref, const void* codes, void* positions,
                                void* substitutions, void* insertions, void* deletions, int32_t S_max, void* stream);
 
+/* Per-sequence attention (an EXTENSION, added to ABI 6 — the version number did not move; csrc/rua_attention.hip; DESIGN
+ * 3.2r).  `q` describes q_ptr / out / grad_out / grad_q, `kv` describes k_ptr / v_ptr / grad_k / grad_v (ANY layout each,
+ * independently of each other); both have the same B and sequence b is the same sequence in both (a PACK layout: through
+ * `unsorted`).  Every row holds `heads` x D elements of `dtype` (RUA_BF16 / RUA_F16; D = 32, 64 or 128).  For query t,
+ * head h of sequence b, over the kv tokens s of the SAME sequence (causal != 0: those with s <= t, positions counted from
+ * the start of the sequence):
+ *   out[row_q(b,t), h, :] = sum_s softmax_s(scale * q[row_q(b,t), h, :] . k[row_kv(b,s), h, :]) * v[row_kv(b,s), h, :]
+ *   lse[row_q(b,t), h]    = log sum_s exp(scale * q . k)      (fp32, [q storage rows, heads])
+ * fp32 accumulation on the matrix unit; the weights are rounded ONCE to `dtype` before they meet v (RUA_BF16: the rounded
+ * remainder follows through a second MFMA, in the forward and in dV), their sum is taken unrounded, every output element is rounded once.  A sequence without kv tokens gives ZERO rows and lse = -inf (torch
+ * gives NaN).  Padding rows of an L / R result are written as zeros, padding rows of the inputs are never read.  Tiles
+ * are cut by position inside the sequence: the same bits for all 16 pairs of layouts.  T_max bounds the q lengths and
+ * sizes the launch (blocks of 128 queries; at most 2 048 workgroups stride over the (sequence, head, block) items); the
+ * kv lengths are read on the device.
+ * rua_segment_attention_backward: three launches, no atomics — `ws` (n_rows of q x heads floats) receives
+ * delta = sum_d grad_out * out; a dK / dV kernel over (sequence, head, block of 128 keys), sized by S_max, walks the
+ * queries; a dQ kernel over (sequence, head, block of 128 queries) walks the keys; P is recomputed from lse.  Every
+ * gradient row is written exactly once, padding rows as zeros.  T_max == 0 / S_max == 0 skip the launches of that side
+ * (the caller zero-fills).
+ * Checks, before any HIP call: a null or malformed layout, different B, heads <= 0, another D or dtype, a scale that is
+ * not finite, a negative bound, a missing pointer, a gradient that aliases an input (RUA_EINVAL); B == 0 returns 0 without
+ * a launch; a payload pointer off 16 bytes, lse / ws off 4 (RUA_EALIGN).  Trace: `seg_attn_forward_kernel`,
+ * `seg_attn_dkdv_kernel`, `seg_attn_dq_kernel` (D=, heads=, causal=, kind=, kvkind=, grid=), `seg_attn_delta_kernel`. */
+int rua_segment_attention_forward(const rua_layout* q, const rua_layout* kv, const void* q_ptr, const void* k_ptr,
+                                  const void* v_ptr, void* out, void* lse, int32_t heads, int32_t D, int32_t dtype,
+                                  int32_t causal, double scale, int64_t T_max, void* stream);
+int rua_segment_attention_backward(const rua_layout* q, const rua_layout* kv, const void* q_ptr, const void* k_ptr,
+                                   const void* v_ptr, const void* out, const void* lse, const void* grad_out,
+                                   void* grad_q, void* grad_k, void* grad_v, void* ws, int32_t heads, int32_t D,
+                                   int32_t dtype, int32_t causal, double scale, int64_t T_max, int64_t S_max,
+                                   void* stream);
+
 /* Per-sequence gated linear recurrence (an EXTENSION, added to ABI 6 — the version number did not move: the reference's
  * users pad, loop over the time steps with elementwise kernels and cast back).  For every sequence b of `lay` (ANY
  * layout) and column h, with u the position along the scan (u = t; reverse != 0: u = len - 1 - t):

@@ -51,6 +51,9 @@ DTYPES = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16, torch.fl
 INT_DTYPES = {torch.int64: I64, torch.int32: I32, torch.int16: I16, torch.int8: I8, torch.uint8: U8}
 # per-sequence cumsum (rua_segment_cumsum): the float types and int64
 SCAN_DTYPES = {**DTYPES, torch.int64: I64}
+# per-sequence attention (rua_segment_attention_*): the payloads of the matrix instructions it uses, and its head sizes
+ATTN_DTYPES = {torch.bfloat16: BF16, torch.float16: F16}
+ATTN_HEAD_DIMS = (32, 64, 128)
 
 
 class RuaLayout(Structure):
@@ -147,6 +150,12 @@ SYMBOLS = {
                                          c_int32, c_void_p]),
     'rua_segment_edit_backtrace': (c_int, [POINTER(RuaLayout), POINTER(RuaLayout), c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_int32, c_void_p]),
+    'rua_segment_attention_forward': (c_int, [POINTER(RuaLayout), POINTER(RuaLayout), c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_double, c_int64,
+                                              c_void_p]),
+    'rua_segment_attention_backward': (c_int, [POINTER(RuaLayout), POINTER(RuaLayout), c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                               c_int32, c_int32, c_int32, c_int32, c_double, c_int64, c_int64, c_void_p]),
     'rua_linear_scan_ws_bytes': (c_int64, [POINTER(RuaLayout), c_int64, c_int32]),
     'rua_segment_linear_scan': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_double, c_void_p, c_int64, c_int32,
                                         c_int32, c_void_p, c_void_p]),

@@ -1433,6 +1433,123 @@ def launch_edit_backtrace(plan: EditPlan, codes: Tensor, lead_shape: Sequence[in
     return positions, subs, ins, dels
 
 
+# ------------------------------------------------------------------ per-sequence attention (an extension)
+def attention_args(what: str, q, q_hidden, n_seq: int, k, k_hidden, n_k_seq: int, v, v_hidden, n_v_seq: int, scale,
+                   before_device: Optional[Callable[[], None]] = None) -> Tuple[int, int, float]:
+    """(heads, D, scale) after the checks that come before any launch and need no lengths, each naming its argument:
+    bf16 / f16 payloads of ONE dtype with exactly the hidden dimensions (heads, D), D of ATTN_HEAD_DIMS, the same on
+    all three; the same number of sequences; one device; a finite `scale` (None: D ** -0.5); and last (so that every
+    other refusal can be met without a GPU) the payloads on a HIP device."""
+    for name, t in (('q', q), ('k', k), ('v', v)):
+        if not isinstance(t, Tensor) or t.dtype not in L.ATTN_DTYPES:
+            raise L.RuaError(f'{what}: `{name}` is one of {list(L.ATTN_DTYPES)}; got '
+                             f'{t.dtype if isinstance(t, Tensor) else type(t).__name__}')
+    for name, t in (('k', k), ('v', v)):
+        if t.dtype != q.dtype:
+            raise L.RuaError(f'{what}: `{name}` has dtype {t.dtype}, `q` {q.dtype}')
+    if len(q_hidden) != 2:
+        raise L.RuaError(f'{what}: `q` has exactly the hidden dimensions (heads, D); got {tuple(q_hidden)}')
+    for name, hidden in (('k', k_hidden), ('v', v_hidden)):
+        if tuple(hidden) != tuple(q_hidden):
+            raise L.RuaError(f'{what}: `{name}` has the hidden dimensions {tuple(hidden)}, `q` {tuple(q_hidden)} '
+                             f'(grouped-query heads are out of scope)')
+    heads, D = int(q_hidden[0]), int(q_hidden[1])
+    if D not in L.ATTN_HEAD_DIMS or heads < 1:
+        raise L.RuaError(f'{what}: `q` has heads = {heads}, D = {D}; D is one of {L.ATTN_HEAD_DIMS} and heads >= 1')
+    for name, n in (('k', n_k_seq), ('v', n_v_seq)):
+        if n != n_seq:
+            raise L.RuaError(f'{what}: `{name}` holds {n} sequences, `q` {n_seq}')
+    for name, t in (('k', k), ('v', v)):
+        if t.device != q.device:
+            raise L.RuaError(f'{what}: `{name}` lives on {t.device}, `q` on {q.device}')
+    if scale is None:
+        scale = D ** -0.5
+    if isinstance(scale, bool) or not isinstance(scale, (int, float)) or scale != scale or scale in (float('inf'), -float('inf')):
+        raise L.RuaError(f'{what}: `scale` = {scale!r} is not a finite number')
+    if before_device is not None:
+        before_device()
+    if not q.is_cuda:
+        raise L.RuaError(f'{what}: `q` lives on {q.device}; move it to a HIP device (there is no CPU fallback by design)')
+    return heads, D, float(scale)
+
+
+class AttentionPlan(NamedTuple):
+    """What every attention launch of one call shares.  `kv_bound()` is the longest kv sequence: only the backward's
+    key-side grid needs it, so it is asked for there (one read-back at most, attached to the container)."""
+    q: M.Lay
+    kv: M.Lay
+    heads: int
+    D: int
+    causal: bool
+    scale: float
+    T_max: int
+    kv_bound: Callable[[], int]
+
+
+def launch_attention_forward(plan: AttentionPlan, q: Tensor, k: Tensor, v: Tensor) -> Tuple[Tensor, Tensor]:
+    """rua_segment_attention_forward: ONE launch.  (out of q's storage shape and dtype, lse [*q storage rows, heads]
+    fp32).  No sequence or no query: zeros and -inf without a launch."""
+    dev = L.require_device(q, k, v)
+    code = L.ATTN_DTYPES[q.dtype]
+    lead = tuple(q.shape[:-2])
+    if not plan.q.B or not plan.T_max or not q.numel():
+        return torch.zeros_like(q), torch.full(lead + (plan.heads,), float('-inf'), dtype=torch.float32, device=dev)
+    q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+    out = torch.empty_like(q)
+    lse = torch.empty(lead + (plan.heads,), dtype=torch.float32, device=dev)
+    _call('attention', 'rua_segment_attention_forward', dev, plan.q.ref(), plan.kv.ref(), L.ptr(q), L.ptr(k), L.ptr(v),
+          L.ptr(out), L.ptr(lse), plan.heads, plan.D, code, int(plan.causal), plan.scale, plan.T_max)
+    return out, lse
+
+
+def launch_attention_backward(plan: AttentionPlan, grad: Tensor, q: Tensor, k: Tensor, v: Tensor, out: Tensor,
+                              lse: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """rua_segment_attention_backward: delta, then dK / dV, then dQ; every gradient row written once."""
+    dev = L.require_device(grad, q, k, v, out, lse)
+    if grad.dtype != q.dtype or tuple(grad.shape) != tuple(q.shape):
+        raise L.RuaError(f'attention backward: the cotangent is a {q.dtype} tensor of shape {tuple(q.shape)}')
+    code = L.ATTN_DTYPES[q.dtype]
+    s_max = plan.kv_bound() if plan.q.B and k.numel() else 0
+    t_max = plan.T_max if q.numel() else 0
+    gq = torch.empty_like(q) if t_max else torch.zeros_like(q)
+    gk, gv = (torch.empty_like(k), torch.empty_like(v)) if s_max else (torch.zeros_like(k), torch.zeros_like(v))
+    if plan.q.B and (s_max or t_max):
+        # bound to names until the launches are queued (see launch_crf_backward)
+        grad, q, k, v, out, lse = (grad.contiguous(), q.contiguous(), k.contiguous(), v.contiguous(), out.contiguous(),
+                                   lse.contiguous())
+        ws = torch.empty(max(lse.numel(), 1), dtype=torch.float32, device=dev)
+        _call('attention_bwd', 'rua_segment_attention_backward', dev, plan.q.ref(), plan.kv.ref(), L.ptr(q), L.ptr(k),
+              L.ptr(v), L.ptr(out), L.ptr(lse), L.ptr(grad), L.ptr(gq), L.ptr(gk), L.ptr(gv), L.ptr(ws), plan.heads,
+              plan.D, code, int(plan.causal), plan.scale, t_max, s_max)
+    return gq, gk, gv
+
+
+class _Attention(torch.autograd.Function):
+    """softmax(q k^T scale) v inside every sequence.  Saves q, k, v, the rounded output and the fp32 logsumexp
+    [*q storage rows, heads]; the backward recomputes the weights from it.  Second derivatives are out of scope."""
+
+    @staticmethod
+    def forward(ctx, q: Tensor, k: Tensor, v: Tensor, plan: AttentionPlan):
+        out, lse = launch_attention_forward(plan, q, k, v)
+        ctx.plan = plan
+        ctx.save_for_backward(q, k, v, out, lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad: Tensor):
+        if torch.is_grad_enabled():
+            raise L.RuaError('attention: second derivatives (create_graph=True) are out of scope')
+        q, k, v, out, lse = ctx.saved_tensors
+        return (*launch_attention_backward(ctx.plan, grad, q, k, v, out, lse), None)
+
+
+def attention(q: Tensor, k: Tensor, v: Tensor, plan: AttentionPlan) -> Tensor:
+    if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
+        # contiguous HERE, before the Function (as in cumsum()): a copy made inside forward() would carry no history
+        return _Attention.apply(q.contiguous(), k.contiguous(), v.contiguous(), plan)
+    return launch_attention_forward(plan, _plain(q), _plain(k), _plain(v))[0]
+
+
 # ------------------------------------------------------------------ per-sequence gated linear recurrence (an extension)
 def _gate_arg(data: Tensor, gate) -> Tuple[Optional[Tensor], float]:
     """(the gate tensor or None, the scalar gate): a tensor of the payload's storage shape, dtype and device, or ONE

@@ -1,0 +1,124 @@
+"""Attention inside every sequence of a ragged batch, over unpadded storage — an extension, and the library's first
+contraction: the operator users of ragged containers otherwise pad for (`left()` + a masked
+`scaled_dot_product_attention` on the [B, T_max, ...] tensors the containers exist to avoid; nothing at all for a
+PackedSequence).  Fused HIP kernels on the gfx950 matrix unit (csrc/rua_attention.hip), the same bits for
+all 4 x 4 pairs of layouts.
+
+    attention(q, k, v, causal=False, scale=None) -> container of q's type     also q.attention(k, v, causal=False, scale=None)
+    segment_attention(q, q_sizes, k, v, kv_sizes, causal=False, scale=None) -> Tensor [N, heads, D]
+
+`q` is a container (C / L / P / R) with exactly the hidden dimensions (heads, D); `k` and `v` are containers of ONE type
+— any of the four, chosen independently of q's — with the same hidden shape, the same lengths as each other, and the same
+number of sequences, dtype and device as `q`.  Sequence b is the same sequence in all three (a P: the original batch
+order).  `q.attention(q, q)` is self-attention; other kv lengths give cross-attention.  For query t of sequence b and
+head h the output row is
+
+    sum_s softmax_s(scale * q[t, h, :] . k[s, h, :]) * v[s, h, :]          over the kv tokens of sequence b only
+
+returned in q's container type, storage shape and dtype, with q's metadata objects; padding rows of L / R are zeros.
+`scale=None` is D ** -0.5.  `causal=True`: key s is visible to query t iff s <= t, positions counted inside the
+sequence from its START (for self-attention the usual mask; no end-aligned variant is offered).  bfloat16 / float16,
+D in {32, 64, 128}.
+
+SEMANTICS — every input has one answer.  A sequence without queries produces no rows.  A sequence with queries but NO
+keys gets ZERO output rows and zero gradients (torch's softmax over nothing gives NaN: a documented deviation).  Under
+`causal` every query sees key 0, so no other all-masked row exists.  Non-finite inputs stay inside their own (sequence,
+head).  fp32 accumulation; the weights are rounded once to the payload dtype before they meet `v` (bf16: hi + lo, the
+rounded remainder follows), their sum is taken unrounded, every output element is rounded once (DESIGN 3.2r derives
+the error bound the tests assert).
+
+AUTOGRAD.  Gradients flow to q, k and v; the forward saves them, the rounded output and an fp32 logsumexp
+[q storage rows, heads]; the backward recomputes the weights, uses no atomics and is bitwise reproducible.
+`create_graph=True` raises.
+
+LENGTHS.  The launch is sized by the longest `q` sequence: with host lengths (C.new, with_host_sizes, a P, an earlier
+read-back) nothing is read back, otherwise there is ONE blocking copy of [B], attached to the container.  The kv lengths
+are needed on the host only by the backward's key-side grid (the same rule, and only when a gradient is requested).  When
+`k` and `v` carry different device-only length tensors whose host copies are unknown, their equality is not checked.
+
+REFUSALS, all before any launch, each a RuaError naming the argument: something that is no container; a dtype other
+than bf16 / f16 or dtypes that differ; hidden dimensions that are not exactly (heads, D) or that differ; D outside
+{32, 64, 128}; `k` and `v` of different container type or lengths; another number of sequences or device; a `scale` that
+is not a finite number; and last a CPU tensor.
+
+OUT OF SCOPE: grouped-query heads, additive bias or arbitrary masks, dropout, sliding windows, end-aligned causal masks,
+fp32 / fp64 payloads, other D, returning the weights, second derivatives, split-K over one very long sequence.
+"""
+import torch
+
+from torchrua_amd import _meta as M
+from torchrua_amd import _ops as O
+from torchrua_amd.layout import (P, T, Z, cat_lay, cls_of, hidden_of, install, lay_hidden, lens_of, n_seq, rewrap)
+from torchrua_amd._lib import RuaError
+
+__all__ = ['attention', 'segment_attention']
+
+
+def _known_bound(z: Z):
+    """The longest sequence if the host can tell without a device (None: it cannot)."""
+    if isinstance(z, P):
+        return int(z.batch_sizes.numel())
+    return M.known_max_len(z.token_sizes) if z.token_sizes.numel() else 0
+
+
+def _bound(z: Z) -> int:
+    known = _known_bound(z)
+    return known if known is not None else M.max_len(lens_of(z))
+
+
+def _same_lengths(what: str, k: Z, v: Z) -> None:
+    """`k` and `v` walk the same tokens: one type, one storage, the same lengths wherever the host can tell."""
+    if cls_of(k) is not cls_of(v):
+        raise RuaError(f'{what}: `k` and `v` are containers of ONE type; got {type(k).__name__} and {type(v).__name__}')
+    a, b = (k.batch_sizes, v.batch_sizes) if isinstance(k, P) else (k.token_sizes, v.token_sizes)
+    same = a is b
+    if not same and M.host_known(a) and M.host_known(b):
+        ha, hb = M.host_lens(a), M.host_lens(b)
+        same = ha.shape == hb.shape and bool(torch.equal(ha.to(torch.long), hb.to(torch.long)))
+    elif not same:
+        same = a.shape == b.shape
+    if not same or tuple(k.data.shape[:-2]) != tuple(v.data.shape[:-2]):
+        raise RuaError(f'{what}: `k` and `v` have the same lengths (one key and one value per kv token)')
+
+
+def _plan(what: str, q: Z, k: Z, v: Z, causal, scale) -> O.AttentionPlan:
+    for name, z in (('q', q), ('k', k), ('v', v)):
+        if cls_of(z) is None:
+            raise RuaError(f'{what}: `{name}` is a container (C / L / P / R); got {type(z).__name__}')
+    heads, D, scale = O.attention_args(what, q.data, hidden_of(q), n_seq(q), k.data, hidden_of(k), n_seq(k), v.data,
+                                       hidden_of(v), n_seq(v), scale, before_device=lambda: _same_lengths(what, k, v))
+    return O.AttentionPlan(lay_hidden(q)[0], lay_hidden(k)[0], heads, D, bool(causal), scale, _bound(q), lambda: _bound(k))
+
+
+def attention(q: Z, k: Z, v: Z, causal: bool = False, scale=None) -> Z:
+    """softmax(q k^T * scale) v inside every sequence, in q's container type with its metadata objects."""
+    plan = _plan('attention', q, k, v, causal, scale)
+    return rewrap(q, O.attention(q.data, k.data, v.data, plan))
+
+
+def segment_attention(q: T, q_sizes: T, k: T, v: T, kv_sizes: T, causal: bool = False, scale=None) -> T:
+    """Attention of every run of `q_sizes` rows of `q` [N, heads, D] over the run of `kv_sizes` rows of `k` / `v`
+    [M, heads, D]."""
+    what = 'segment_attention'
+    for name, t in (('q', q), ('q_sizes', q_sizes), ('k', k), ('v', v), ('kv_sizes', kv_sizes)):
+        if not isinstance(t, torch.Tensor):
+            raise RuaError(f'{what}: `{name}` is a tensor; got {type(t).__name__}')
+
+    def rows():
+        if tuple(k.shape[:1]) != tuple(v.shape[:1]):
+            raise RuaError(f'{what}: `k` and `v` have the same lengths (one key and one value per kv token)')
+
+    n_kv = int(kv_sizes.numel())
+    heads, D, scale = O.attention_args(what, q, tuple(q.shape[1:]), int(q_sizes.numel()), k, tuple(k.shape[1:]), n_kv, v,
+                                       tuple(v.shape[1:]), n_kv, scale, before_device=rows)
+
+    def bound(sizes):
+        known = M.known_max_len(sizes) if sizes.numel() else 0
+        return known if known is not None else M.max_len(sizes)
+
+    plan = O.AttentionPlan(cat_lay(q, q_sizes), cat_lay(k, kv_sizes), heads, D, bool(causal), scale, bound(q_sizes),
+                           lambda: bound(kv_sizes))
+    return O.attention(q, k, v, plan)
+
+
+install(attention=attention)
