@@ -774,6 +774,36 @@ int rua_segment_attention_backward(const rua_layout* q, const rua_layout* kv, co
                                    int32_t dtype, int32_t causal, double scale, int64_t T_max, int64_t S_max,
                                    void* stream);
 
+/* Per-sequence attention, the BAND form (an EXTENSION, added to ABI 6 — the version number did not move;
+ * csrc/rua_attention.hip): grouped-query heads, a window, and masks aligned at the end.  The arguments of
+ * rua_segment_attention_forward / _backward with `causal` replaced by `heads_kv, left, right, align_end`; everything not
+ * said here is as above.  A q row holds `heads` x D elements, a kv row (k_ptr, v_ptr, grad_k, grad_v) `heads_kv` x D;
+ * query head h reads kv head h / (heads / heads_kv).  With T_b queries and S_b keys in sequence b, shift_b = S_b - T_b
+ * when align_end != 0 (the last query sits on the last key; it may be negative) and 0 otherwise, query t sees key s iff
+ *   0 <= s < S_b   and   -left <= s - (t + shift_b) <= right          (a NEGATIVE bound: unbounded on that side)
+ * so (left, right) = (-1, 0) is the causal mask and (W - 1, 0) a causal window of W keys.  The comparison is made on the
+ * difference, for any int64 bound.  A query WITHOUT a visible key (no keys; align_end with T_b > S_b; a bounded left
+ * with t + shift_b - left >= S_b) gives a ZERO row, lse = -inf, a zero grad_q row, and nothing in grad_k / grad_v.
+ * Only the key tiles that meet the band of a block of 128 queries are visited (forward, dQ), only the query tiles that
+ * meet the band of a block of 128 keys (dK / dV); tiles stay cut by position from 0: the same bits for all 16 pairs of
+ * layouts, and the bits of the plain form wherever the two masks coincide and heads_kv == heads.
+ * rua_segment_attention_band_backward: the dK / dV kernel works over (sequence, KV head, block of 128 keys), sized by
+ * S_max and heads_kv; it keeps its accumulators in registers over the query heads of its group in ascending order, and
+ * for each over the query tiles in ascending order, and writes every grad_k / grad_v row once (the sum over the group in
+ * fp32, rounded once; no atomics, no workspace beyond `ws`).  `lse` and `ws` stay [q storage rows, heads].
+ * Checks, before any HIP call: those of the plain form, and heads_kv <= 0 or heads % heads_kv != 0 (RUA_EINVAL).
+ * Trace: `seg_attn_band_forward_kernel`, `seg_attn_band_dkdv_kernel`, `seg_attn_band_dq_kernel` (D=, heads=, kvheads=,
+ * left=, right=, end=, kind=, kvkind=, grid=; an unbounded side prints -1), `seg_attn_delta_kernel`. */
+int rua_segment_attention_band_forward(const rua_layout* q, const rua_layout* kv, const void* q_ptr, const void* k_ptr,
+                                       const void* v_ptr, void* out, void* lse, int32_t heads, int32_t D, int32_t dtype,
+                                       int32_t heads_kv, int64_t left, int64_t right, int32_t align_end, double scale,
+                                       int64_t T_max, void* stream);
+int rua_segment_attention_band_backward(const rua_layout* q, const rua_layout* kv, const void* q_ptr, const void* k_ptr,
+                                        const void* v_ptr, const void* out, const void* lse, const void* grad_out,
+                                        void* grad_q, void* grad_k, void* grad_v, void* ws, int32_t heads, int32_t D,
+                                        int32_t dtype, int32_t heads_kv, int64_t left, int64_t right, int32_t align_end,
+                                        double scale, int64_t T_max, int64_t S_max, void* stream);
+
 /* Per-sequence gated linear recurrence (an EXTENSION, added to ABI 6 — the version number did not move: the reference's
  * users pad, loop over the time steps with elementwise kernels and cast back).  For every sequence b of `lay` (ANY
  * layout) and column h, with u the position along the scan (u = t; reverse != 0: u = len - 1 - t):

@@ -1434,12 +1434,36 @@ def launch_edit_backtrace(plan: EditPlan, codes: Tensor, lead_shape: Sequence[in
 
 
 # ------------------------------------------------------------------ per-sequence attention (an extension)
+def _window(what: str, window) -> Tuple[int, int]:
+    """(left, right) of `window`: None, an int >= 0 (both sides) or a pair of such or None; -1 is an unbounded side."""
+    sides = tuple(window) if isinstance(window, (tuple, list)) else (window, window)
+    if len(sides) != 2 or any(w is not None and (isinstance(w, bool) or not isinstance(w, int) or w < 0) for w in sides):
+        raise L.RuaError(f'{what}: `window` = {window!r} is None, an int >= 0, or a pair (left, right) of such or None')
+    left, right = (-1 if w is None else min(w, 2 ** 63 - 1) for w in sides)  # no sequence is that long: the same mask
+    return left, right
+
+
+class AttentionArgs(NamedTuple):
+    """What attention_args() settles.  `left` / `right` are the window as given, -1 for an unbounded side; `causal` is
+    kept next to them and closes the right side at 0 where the mask is applied."""
+    heads: int
+    heads_kv: int
+    D: int
+    scale: float
+    left: int
+    right: int
+    align_end: bool
+
+
 def attention_args(what: str, q, q_hidden, n_seq: int, k, k_hidden, n_k_seq: int, v, v_hidden, n_v_seq: int, scale,
-                   before_device: Optional[Callable[[], None]] = None) -> Tuple[int, int, float]:
-    """(heads, D, scale) after the checks that come before any launch and need no lengths, each naming its argument:
-    bf16 / f16 payloads of ONE dtype with exactly the hidden dimensions (heads, D), D of ATTN_HEAD_DIMS, the same on
-    all three; the same number of sequences; one device; a finite `scale` (None: D ** -0.5); and last (so that every
-    other refusal can be met without a GPU) the payloads on a HIP device."""
+                   causal=False, window=None, align='start',
+                   before_device: Optional[Callable[[], None]] = None) -> AttentionArgs:
+    """AttentionArgs after the checks that come before any launch and need no lengths, each naming its argument:
+    bf16 / f16 payloads of ONE dtype; `q` with exactly the hidden dimensions (heads, D), `k` with (heads_kv, D), heads a
+    multiple of heads_kv, `v` like `k`; D of ATTN_HEAD_DIMS; the same number of sequences; one device; a finite `scale`
+    (None: D ** -0.5); a `window` that is None, an int >= 0 or a pair of such or None, whose right side does not
+    contradict `causal`; an `align` of 'start' / 'end'; and last (so that every other refusal can be met without a GPU)
+    the payloads on a HIP device."""
     for name, t in (('q', q), ('k', k), ('v', v)):
         if not isinstance(t, Tensor) or t.dtype not in L.ATTN_DTYPES:
             raise L.RuaError(f'{what}: `{name}` is one of {list(L.ATTN_DTYPES)}; got '
@@ -1449,11 +1473,16 @@ def attention_args(what: str, q, q_hidden, n_seq: int, k, k_hidden, n_k_seq: int
             raise L.RuaError(f'{what}: `{name}` has dtype {t.dtype}, `q` {q.dtype}')
     if len(q_hidden) != 2:
         raise L.RuaError(f'{what}: `q` has exactly the hidden dimensions (heads, D); got {tuple(q_hidden)}')
-    for name, hidden in (('k', k_hidden), ('v', v_hidden)):
-        if tuple(hidden) != tuple(q_hidden):
-            raise L.RuaError(f'{what}: `{name}` has the hidden dimensions {tuple(hidden)}, `q` {tuple(q_hidden)} '
-                             f'(grouped-query heads are out of scope)')
     heads, D = int(q_hidden[0]), int(q_hidden[1])
+    if len(k_hidden) != 2 or int(k_hidden[1]) != D:
+        raise L.RuaError(f'{what}: `k` has the hidden dimensions {tuple(k_hidden)}, `q` {tuple(q_hidden)}: '
+                         f'(heads_kv, D) with q\'s D')
+    heads_kv = int(k_hidden[0])
+    if heads_kv < 1 or heads % heads_kv:
+        raise L.RuaError(f'{what}: `k` has {heads_kv} heads, `q` {heads}: the query heads are a multiple of the kv heads '
+                         f'(query head h reads kv head h // (heads // heads_kv))')
+    if tuple(v_hidden) != tuple(k_hidden):
+        raise L.RuaError(f'{what}: `v` has the hidden dimensions {tuple(v_hidden)}, `k` {tuple(k_hidden)}')
     if D not in L.ATTN_HEAD_DIMS or heads < 1:
         raise L.RuaError(f'{what}: `q` has heads = {heads}, D = {D}; D is one of {L.ATTN_HEAD_DIMS} and heads >= 1')
     for name, n in (('k', n_k_seq), ('v', n_v_seq)):
@@ -1466,16 +1495,25 @@ def attention_args(what: str, q, q_hidden, n_seq: int, k, k_hidden, n_k_seq: int
         scale = D ** -0.5
     if isinstance(scale, bool) or not isinstance(scale, (int, float)) or scale != scale or scale in (float('inf'), -float('inf')):
         raise L.RuaError(f'{what}: `scale` = {scale!r} is not a finite number')
+    left, right = _window(what, window)
+    if causal and right > 0 and isinstance(window, (tuple, list)):      # an int is (w, w), whose right side `causal` closes
+        raise L.RuaError(f'{what}: `window` = {window!r} has right = {right} and `causal` is set: under `causal` the right '
+                         f'side is 0 or None')
+    if align not in ('start', 'end'):
+        raise L.RuaError(f"{what}: `align` = {align!r} is 'start' or 'end'")
     if before_device is not None:
         before_device()
     if not q.is_cuda:
         raise L.RuaError(f'{what}: `q` lives on {q.device}; move it to a HIP device (there is no CPU fallback by design)')
-    return heads, D, float(scale)
+    return AttentionArgs(heads, heads_kv, D, float(scale), left, right, align == 'end')
 
 
 class AttentionPlan(NamedTuple):
     """What every attention launch of one call shares.  `kv_bound()` is the longest kv sequence: only the backward's
-    key-side grid needs it, so it is asked for there (one read-back at most, attached to the container)."""
+    key-side grid needs it, so it is asked for there (one read-back at most, attached to the container).  `left` /
+    `right` are the window as given (-1: unbounded); `causal` closes the right side at 0.  A plan with heads_kv ==
+    heads, no window and start alignment is today's operator and goes through the plain entry points; every other one
+    through rua_segment_attention_band_*."""
     q: M.Lay
     kv: M.Lay
     heads: int
@@ -1484,11 +1522,25 @@ class AttentionPlan(NamedTuple):
     scale: float
     T_max: int
     kv_bound: Callable[[], int]
+    heads_kv: int
+    left: int
+    right: int
+    align_end: bool
+
+    @property
+    def band(self) -> bool:
+        return self.heads_kv != self.heads or self.left >= 0 or self.right >= 0 or self.align_end
+
+    def mask_args(self) -> tuple:
+        """What stands in the argument list where the plain entry points take `causal`."""
+        if not self.band:
+            return (int(self.causal),)
+        return self.heads_kv, self.left, 0 if self.causal else self.right, int(self.align_end)
 
 
 def launch_attention_forward(plan: AttentionPlan, q: Tensor, k: Tensor, v: Tensor) -> Tuple[Tensor, Tensor]:
-    """rua_segment_attention_forward: ONE launch.  (out of q's storage shape and dtype, lse [*q storage rows, heads]
-    fp32).  No sequence or no query: zeros and -inf without a launch."""
+    """rua_segment_attention_forward, or its band form: ONE launch.  (out of q's storage shape and dtype, lse [*q storage
+    rows, heads] fp32).  No sequence or no query: zeros and -inf without a launch."""
     dev = L.require_device(q, k, v)
     code = L.ATTN_DTYPES[q.dtype]
     lead = tuple(q.shape[:-2])
@@ -1497,14 +1549,16 @@ def launch_attention_forward(plan: AttentionPlan, q: Tensor, k: Tensor, v: Tenso
     q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
     out = torch.empty_like(q)
     lse = torch.empty(lead + (plan.heads,), dtype=torch.float32, device=dev)
-    _call('attention', 'rua_segment_attention_forward', dev, plan.q.ref(), plan.kv.ref(), L.ptr(q), L.ptr(k), L.ptr(v),
-          L.ptr(out), L.ptr(lse), plan.heads, plan.D, code, int(plan.causal), plan.scale, plan.T_max)
+    _call('attention', 'rua_segment_attention_band_forward' if plan.band else 'rua_segment_attention_forward', dev,
+          plan.q.ref(), plan.kv.ref(), L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), L.ptr(lse), plan.heads, plan.D, code,
+          *plan.mask_args(), plan.scale, plan.T_max)
     return out, lse
 
 
 def launch_attention_backward(plan: AttentionPlan, grad: Tensor, q: Tensor, k: Tensor, v: Tensor, out: Tensor,
                               lse: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
-    """rua_segment_attention_backward: delta, then dK / dV, then dQ; every gradient row written once."""
+    """rua_segment_attention_backward, or its band form: delta, then dK / dV, then dQ; every gradient row written once
+    (grad_k / grad_v in the kv shape: the sum over the group)."""
     dev = L.require_device(grad, q, k, v, out, lse)
     if grad.dtype != q.dtype or tuple(grad.shape) != tuple(q.shape):
         raise L.RuaError(f'attention backward: the cotangent is a {q.dtype} tensor of shape {tuple(q.shape)}')
@@ -1518,9 +1572,10 @@ def launch_attention_backward(plan: AttentionPlan, grad: Tensor, q: Tensor, k: T
         grad, q, k, v, out, lse = (grad.contiguous(), q.contiguous(), k.contiguous(), v.contiguous(), out.contiguous(),
                                    lse.contiguous())
         ws = torch.empty(max(lse.numel(), 1), dtype=torch.float32, device=dev)
-        _call('attention_bwd', 'rua_segment_attention_backward', dev, plan.q.ref(), plan.kv.ref(), L.ptr(q), L.ptr(k),
-              L.ptr(v), L.ptr(out), L.ptr(lse), L.ptr(grad), L.ptr(gq), L.ptr(gk), L.ptr(gv), L.ptr(ws), plan.heads,
-              plan.D, code, int(plan.causal), plan.scale, t_max, s_max)
+        _call('attention_bwd', 'rua_segment_attention_band_backward' if plan.band else 'rua_segment_attention_backward',
+              dev, plan.q.ref(), plan.kv.ref(), L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), L.ptr(lse), L.ptr(grad),
+              L.ptr(gq), L.ptr(gk), L.ptr(gv), L.ptr(ws), plan.heads, plan.D, code, *plan.mask_args(), plan.scale,
+              t_max, s_max)
     return gq, gk, gv
 
 

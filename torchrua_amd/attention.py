@@ -4,28 +4,39 @@ contraction: the operator users of ragged containers otherwise pad for (`left()`
 PackedSequence).  Fused HIP kernels on the gfx950 matrix unit (csrc/rua_attention.hip), the same bits for
 all 4 x 4 pairs of layouts.
 
-    attention(q, k, v, causal=False, scale=None) -> container of q's type     also q.attention(k, v, causal=False, scale=None)
-    segment_attention(q, q_sizes, k, v, kv_sizes, causal=False, scale=None) -> Tensor [N, heads, D]
+    attention(q, k, v, causal=False, scale=None, window=None, align='start') -> container of q's type
+                                                                                    also q.attention(k, v, ...)
+    segment_attention(q, q_sizes, k, v, kv_sizes, causal=False, scale=None, window=None, align='start')
+                                                                                    -> Tensor [N, heads, D]
 
 `q` is a container (C / L / P / R) with exactly the hidden dimensions (heads, D); `k` and `v` are containers of ONE type
-— any of the four, chosen independently of q's — with the same hidden shape, the same lengths as each other, and the same
-number of sequences, dtype and device as `q`.  Sequence b is the same sequence in all three (a P: the original batch
-order).  `q.attention(q, q)` is self-attention; other kv lengths give cross-attention.  For query t of sequence b and
-head h the output row is
+— any of the four, chosen independently of q's — with the hidden dimensions (heads_kv, D), the same as each other, the
+same lengths as each other, and the same number of sequences, dtype and device as `q`.  Sequence b is the same sequence
+in all three (a P: the original batch order).  `q.attention(q, q)` is self-attention; other kv lengths give
+cross-attention.  For query t of sequence b and head h the output row is
 
-    sum_s softmax_s(scale * q[t, h, :] . k[s, h, :]) * v[s, h, :]          over the kv tokens of sequence b only
+    sum_s softmax_s(scale * q[t, h, :] . k[s, h // G, :]) * v[s, h // G, :]      over the VISIBLE kv tokens of sequence b
 
 returned in q's container type, storage shape and dtype, with q's metadata objects; padding rows of L / R are zeros.
-`scale=None` is D ** -0.5.  `causal=True`: key s is visible to query t iff s <= t, positions counted inside the
-sequence from its START (for self-attention the usual mask; no end-aligned variant is offered).  bfloat16 / float16,
-D in {32, 64, 128}.
+`scale=None` is D ** -0.5.  bfloat16 / float16, D in {32, 64, 128}.
 
-SEMANTICS — every input has one answer.  A sequence without queries produces no rows.  A sequence with queries but NO
-keys gets ZERO output rows and zero gradients (torch's softmax over nothing gives NaN: a documented deviation).  Under
-`causal` every query sees key 0, so no other all-masked row exists.  Non-finite inputs stay inside their own (sequence,
-head).  fp32 accumulation; the weights are rounded once to the payload dtype before they meet `v` (bf16: hi + lo, the
-rounded remainder follows), their sum is taken unrounded, every output element is rounded once (DESIGN 3.2r derives
-the error bound the tests assert).
+HEADS.  heads % heads_kv == 0; with G = heads // heads_kv query head h reads kv head h // G (the `repeat_interleave`
+convention: grouped-query attention, heads_kv == 1 multi-query).  K and V are never expanded; `grad_k` / `grad_v` have
+the kv shape, the sum over the group taken in fp32 and rounded once.  G == 1 is the plain operator.
+
+MASK.  Per sequence b with T_b queries and S_b keys, shift_b = 0 for align='start' and S_b - T_b for align='end' (the
+last query sits on the last key: chunked prefill against a cache, a decoder over a memory plus its own prefix; it may
+be negative).  Query t sees key s iff 0 <= s < S_b and -left <= s - (t + shift_b) <= right.  `window=None`: both sides
+unbounded; `window=w` (an int >= 0): (w, w); `window=(left, right)`: each an int >= 0 or None (unbounded).
+`causal=True` sets right = 0, so a causal window that sees W keys, the query's own included, is `causal=True,
+window=W - 1`.  Only the tiles that meet the band are visited: a window makes the cost O(T W).
+
+SEMANTICS — every input has one answer.  A sequence without queries produces no rows.  A query with NO visible key — a
+sequence without keys; align='end' with T_b > S_b; a bounded left with t + shift_b - left >= S_b — gets a ZERO output
+row, lse = -inf and zero gradients, and contributes nothing to grad_k / grad_v (torch's softmax over nothing gives NaN:
+a documented deviation).  Non-finite inputs stay inside their own (sequence, head).  fp32 accumulation; the weights are
+rounded once to the payload dtype before they meet `v` (bf16: hi + lo, the rounded remainder follows), their sum is taken
+unrounded, every output element is rounded once (DESIGN 3.2r derives the error bound the tests assert).
 
 AUTOGRAD.  Gradients flow to q, k and v; the forward saves them, the rounded output and an fp32 logsumexp
 [q storage rows, heads]; the backward recomputes the weights, uses no atomics and is bitwise reproducible.
@@ -33,16 +44,21 @@ AUTOGRAD.  Gradients flow to q, k and v; the forward saves them, the rounded out
 
 LENGTHS.  The launch is sized by the longest `q` sequence: with host lengths (C.new, with_host_sizes, a P, an earlier
 read-back) nothing is read back, otherwise there is ONE blocking copy of [B], attached to the container.  The kv lengths
-are needed on the host only by the backward's key-side grid (the same rule, and only when a gradient is requested).  When
-`k` and `v` carry different device-only length tensors whose host copies are unknown, their equality is not checked.
+are needed on the host only by the backward's key-side grid (the same rule, and only when a gradient is requested);
+align='end' takes S_b - T_b on the device and reads nothing back.  When `k` and `v` carry different device-only length
+tensors whose host copies are unknown, their equality is not checked.
 
 REFUSALS, all before any launch, each a RuaError naming the argument: something that is no container; a dtype other
-than bf16 / f16 or dtypes that differ; hidden dimensions that are not exactly (heads, D) or that differ; D outside
+than bf16 / f16 or dtypes that differ; hidden dimensions of `q` that are not exactly (heads, D); a `k` that is not
+(heads_kv, D) with q's D, or whose heads do not divide q's; a `v` whose hidden dimensions differ from k's; D outside
 {32, 64, 128}; `k` and `v` of different container type or lengths; another number of sequences or device; a `scale` that
-is not a finite number; and last a CPU tensor.
+is not a finite number; a `window` that is not None, an int >= 0 or a pair of such or None (bools are refused); a
+`window` whose right side is neither None nor 0 together with `causal=True`; an `align` other than 'start' / 'end'; and
+last a CPU tensor.
 
-OUT OF SCOPE: grouped-query heads, additive bias or arbitrary masks, dropout, sliding windows, end-aligned causal masks,
-fp32 / fp64 payloads, other D, returning the weights, second derivatives, split-K over one very long sequence.
+OUT OF SCOPE: additive bias or arbitrary masks, dropout, fp32 / fp64 payloads, other D, returning the weights, second
+derivatives, split-K over one very long sequence, a decode kernel that packs a group's heads into the matrix rows when
+T_b is tiny (the band form is correct there and wastes the tile).
 """
 import torch
 
@@ -81,24 +97,27 @@ def _same_lengths(what: str, k: Z, v: Z) -> None:
         raise RuaError(f'{what}: `k` and `v` have the same lengths (one key and one value per kv token)')
 
 
-def _plan(what: str, q: Z, k: Z, v: Z, causal, scale) -> O.AttentionPlan:
+def _plan(what: str, q: Z, k: Z, v: Z, causal, scale, window, align) -> O.AttentionPlan:
     for name, z in (('q', q), ('k', k), ('v', v)):
         if cls_of(z) is None:
             raise RuaError(f'{what}: `{name}` is a container (C / L / P / R); got {type(z).__name__}')
-    heads, D, scale = O.attention_args(what, q.data, hidden_of(q), n_seq(q), k.data, hidden_of(k), n_seq(k), v.data,
-                                       hidden_of(v), n_seq(v), scale, before_device=lambda: _same_lengths(what, k, v))
-    return O.AttentionPlan(lay_hidden(q)[0], lay_hidden(k)[0], heads, D, bool(causal), scale, _bound(q), lambda: _bound(k))
+    a = O.attention_args(what, q.data, hidden_of(q), n_seq(q), k.data, hidden_of(k), n_seq(k), v.data, hidden_of(v),
+                         n_seq(v), scale, causal, window, align, before_device=lambda: _same_lengths(what, k, v))
+    return O.AttentionPlan(lay_hidden(q)[0], lay_hidden(k)[0], a.heads, a.D, bool(causal), a.scale, _bound(q),
+                           lambda: _bound(k), a.heads_kv, a.left, a.right, a.align_end)
 
 
-def attention(q: Z, k: Z, v: Z, causal: bool = False, scale=None) -> Z:
-    """softmax(q k^T * scale) v inside every sequence, in q's container type with its metadata objects."""
-    plan = _plan('attention', q, k, v, causal, scale)
+def attention(q: Z, k: Z, v: Z, causal: bool = False, scale=None, window=None, align: str = 'start') -> Z:
+    """softmax(q k^T * scale) v over the visible keys inside every sequence, in q's container type with its metadata
+    objects."""
+    plan = _plan('attention', q, k, v, causal, scale, window, align)
     return rewrap(q, O.attention(q.data, k.data, v.data, plan))
 
 
-def segment_attention(q: T, q_sizes: T, k: T, v: T, kv_sizes: T, causal: bool = False, scale=None) -> T:
+def segment_attention(q: T, q_sizes: T, k: T, v: T, kv_sizes: T, causal: bool = False, scale=None, window=None,
+                      align: str = 'start') -> T:
     """Attention of every run of `q_sizes` rows of `q` [N, heads, D] over the run of `kv_sizes` rows of `k` / `v`
-    [M, heads, D]."""
+    [M, heads_kv, D]."""
     what = 'segment_attention'
     for name, t in (('q', q), ('q_sizes', q_sizes), ('k', k), ('v', v), ('kv_sizes', kv_sizes)):
         if not isinstance(t, torch.Tensor):
@@ -109,15 +128,15 @@ def segment_attention(q: T, q_sizes: T, k: T, v: T, kv_sizes: T, causal: bool = 
             raise RuaError(f'{what}: `k` and `v` have the same lengths (one key and one value per kv token)')
 
     n_kv = int(kv_sizes.numel())
-    heads, D, scale = O.attention_args(what, q, tuple(q.shape[1:]), int(q_sizes.numel()), k, tuple(k.shape[1:]), n_kv, v,
-                                       tuple(v.shape[1:]), n_kv, scale, before_device=rows)
+    a = O.attention_args(what, q, tuple(q.shape[1:]), int(q_sizes.numel()), k, tuple(k.shape[1:]), n_kv, v,
+                         tuple(v.shape[1:]), n_kv, scale, causal, window, align, before_device=rows)
 
     def bound(sizes):
         known = M.known_max_len(sizes) if sizes.numel() else 0
         return known if known is not None else M.max_len(sizes)
 
-    plan = O.AttentionPlan(cat_lay(q, q_sizes), cat_lay(k, kv_sizes), heads, D, bool(causal), scale, bound(q_sizes),
-                           lambda: bound(kv_sizes))
+    plan = O.AttentionPlan(cat_lay(q, q_sizes), cat_lay(k, kv_sizes), a.heads, a.D, bool(causal), a.scale, bound(q_sizes),
+                           lambda: bound(kv_sizes), a.heads_kv, a.left, a.right, a.align_end)
     return O.attention(q, k, v, plan)
 
 

@@ -46,8 +46,21 @@
 // it alone is off by up to 2^-8, as much as the rounding of the result itself; at rows with few keys the two together
 // exceed one ulp of the result.  f16 (11 bits) takes the single MFMA.  dS is rounded once in both types.
 //
-// KNOWN LIMITS: one workgroup walks all the keys of a (sequence, head, query block) — no split-K; the transposed tiles are
-// written to LDS with 2-byte stores; heads_kv == heads.
+// THE BAND FORM (rua_segment_attention_band_*; the BAND switch of the same three templates).  Query t sees key s iff
+// -left <= s - (t + shift) <= right, shift = S - T under end alignment, and query head h reads kv head h / G, G = heads /
+// heads_kv.  It parametrises the walk and nothing else: the forward and the dQ kernel visit only the key tiles between
+// the band edges of their block of 128 queries, the first rounded down to a multiple of 64 so that tiles stay cut by
+// position from 0; a wave skips a 32-key sub-tile wholly outside the band of its own 32 queries, on either side; every
+// other key outside the band is selected away like the causal diagonal.  A skipped tile and a wholly masked tile give the
+// same bits (m_use / alpha below), so the plain form's bits come out wherever the masks coincide.  K / V rows are staged
+// from head h / G with row stride heads_kv x D.  The dK / dV kernel works over (sequence, KV head, key block): its
+// accumulators stay in registers over the G query heads of the group in ascending order, and for each over the query
+// tiles that can see the block in ascending order; every dK / dV row is stored once — no atomics, no workspace, a fixed
+// order of adds.  A query without a visible key (an empty band) gets zeros, lse = -inf and zero gradients.
+//
+// KNOWN LIMITS: one workgroup walks all the visible keys of a (sequence, head, query block) — no split-K; the
+// transposed tiles are written to LDS with 2-byte stores; the query heads of a group stage the same K / V tile once each
+// in the forward (no sharing between them); a sequence with a handful of queries (decode) still fills a 128-query block.
 #include <stdio.h>
 #include <stdint.h>
 #include <math.h>
@@ -178,14 +191,36 @@ template <bool CAUSAL> __device__ __forceinline__ int64_t attn_key_end(int64_t S
   return (CAUSAL && q0 + ATTN_BLOCK_TOK < S) ? q0 + ATTN_BLOCK_TOK : S;
 }
 
+// THE BAND FORM (rua_segment_attention_band_*; BAND = true, CAUSAL = false).  Query t of a sequence with T queries and S
+// keys sees key s iff  -left <= s - (t + shift) <= right,  shift = S - T when the masks are aligned at the END of the
+// sequence and 0 otherwise; a negative bound is no bound.  Query head h reads kv head h / (heads / heads_kv), a kv row
+// holds heads_kv x D elements.  Every comparison is made on the difference d = s - (t + shift), whose terms are lengths;
+// `t + shift + right` is never formed (a bound may be any int64).
+struct attn_band {
+  int64_t left, right;
+  int32_t heads_kv, align_end;
+};
+
+__device__ __forceinline__ bool attn_band_sees(const attn_band& bd, int64_t d) {
+  return (bd.left < 0 || d >= -bd.left) && (bd.right < 0 || d <= bd.right);
+}
+// max(0, a - w), w < 0: unbounded — the first position that a band edge `w` below position `a` leaves visible
+__device__ __forceinline__ int64_t attn_band_lo(int64_t a, int64_t w) { return (w < 0 || a <= w) ? 0 : a - w; }
+// min(n, c + w + 1), w < 0: unbounded — one past the last of n positions that a band edge `w` above `c` leaves visible
+// (it may be <= 0: an empty band)
+__device__ __forceinline__ int64_t attn_band_hi(int64_t c, int64_t w, int64_t n) {
+  return (w < 0 || w >= n - 1 - c) ? n : c + w + 1;
+}
+
 // ---------------------------------------------------------------- forward: one flash-style pass
-template <typename X, int D, bool CAUSAL>
+template <typename X, int D, bool CAUSAL, bool BAND = false>
 __global__ __launch_bounds__(RUA_BLOCK) void seg_attn_forward_kernel(rua_layout LQ, rua_layout LK,
                                                                      const uint16_t* __restrict__ q,
                                                                      const uint16_t* __restrict__ k,
                                                                      const uint16_t* __restrict__ v,
                                                                      uint16_t* __restrict__ out, float* __restrict__ lse,
-                                                                     int heads, float scale, int64_t nblk, int64_t items) {
+                                                                     int heads, float scale, int64_t nblk, int64_t items,
+                                                                     attn_band bd) {
   constexpr int PS = D + 8, TS = ATTN_KB + 8, NS = D / 16, ND = D / 32;
   __shared__ __attribute__((aligned(16))) uint16_t sK[ATTN_KB * PS];
   __shared__ __attribute__((aligned(16))) uint16_t sVt[D * TS];
@@ -219,17 +254,26 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_attn_forward_kernel(rua_layout 
       for (int r = 0; r < 16; ++r) acc[dt][r] = 0.f;
     float m = NEG_INF, l = 0.f;
 
-    const int64_t kend = attn_key_end<CAUSAL>(S, q0);
-    for (int64_t k0 = 0; k0 < kend; k0 += ATTN_KB) {
+    // the kv head and the heads of a kv row; the keys the block may see, walked in tiles cut by position from 0 (an
+    // empty band: no tile, and the zero rows and lse = -inf below)
+    const int hkv = BAND ? bd.heads_kv : heads, hk = BAND ? h / (heads / hkv) : h;
+    const int64_t shift = (BAND && bd.align_end) ? S - T : 0;
+    const int64_t kbeg = BAND ? attn_band_lo(q0 + shift, bd.left) / ATTN_KB * ATTN_KB : 0;
+    const int64_t kend = BAND ? attn_band_hi(q0 + ATTN_BLOCK_TOK - 1 + shift, bd.right, S) : attn_key_end<CAUSAL>(S, q0);
+    for (int64_t k0 = kbeg; k0 < kend; k0 += ATTN_KB) {
       __syncthreads();                                          // the tile before is consumed
-      attn_stage<D, ATTN_KB, true, false>(LK, b, S, k0, h, heads, k, sK, nullptr, tid);
-      attn_stage<D, ATTN_KB, false, true>(LK, b, S, k0, h, heads, v, nullptr, sVt, tid);
+      attn_stage<D, ATTN_KB, true, false>(LK, b, S, k0, hk, hkv, k, sK, nullptr, tid);
+      attn_stage<D, ATTN_KB, false, true>(LK, b, S, k0, hk, hkv, v, nullptr, sVt, tid);
       __syncthreads();
       if (!live) continue;
 #pragma unroll
       for (int sub = 0; sub < ATTN_KB / 32; ++sub) {
         const int64_t ks = k0 + 32 * sub;
         if (ks >= kend || (CAUSAL && ks > w0 + 31)) break;      // past the end, or wholly above the wave's diagonal
+        if constexpr (BAND) {                                   // wholly right / left of the band of the wave's queries
+          if (bd.right >= 0 && ks - (w0 + 31 + shift) > bd.right) break;
+          if (bd.left >= 0 && ks + 31 - (w0 + shift) < -bd.left) continue;
+        }
         attn_f32x16 s;
 #pragma unroll
         for (int r = 0; r < 16; ++r) s[r] = 0.f;
@@ -241,7 +285,7 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_attn_forward_kernel(rua_layout 
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int64_t key = ks + 8 * (r >> 2) + 4 * g + (r & 3);
-          const bool ok = key < S && (!CAUSAL || key <= tq);
+          const bool ok = key < S && (!CAUSAL || key <= tq) && (!BAND || attn_band_sees(bd, key - (tq + shift)));
           sv[r] = ok ? s[r] * scale : NEG_INF;
           mx = fmaxf(mx, sv[r]);
         }
@@ -278,7 +322,7 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_attn_forward_kernel(rua_layout 
       }
     }
 
-    if (qrow >= 0) {                                            // a sequence without keys: zeros and lse = -inf
+    if (qrow >= 0) {                                            // a query without a visible key: zeros and lse = -inf
       attn_store_row<X, D>(acc, l > 0.f ? 1.f / l : 0.f, out + (qrow * heads + h) * (int64_t)D, g);
       if (g == 0) lse[qrow * heads + h] = l > 0.f ? m + logf(l) : NEG_INF;
     }
@@ -303,7 +347,10 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_attn_delta_kernel(const uint16_
 }
 
 // ---------------------------------------------------------------- backward 2: dK and dV, a lane is a key
-template <typename X, int D, bool CAUSAL>
+// BAND: the work item is (sequence, KV head, key block).  The accumulators stay in registers across the whole group: the
+// query heads hk G .. hk G + G - 1 of the kv head in ASCENDING order, and for each the query tiles that can see the block
+// in ascending order — a fixed order of fp32 adds, so the sum over the group is reproducible and is rounded once.
+template <typename X, int D, bool CAUSAL, bool BAND = false>
 __global__ __launch_bounds__(RUA_BLOCK) void seg_attn_dkdv_kernel(rua_layout LQ, rua_layout LK,
                                                                   const uint16_t* __restrict__ q,
                                                                   const uint16_t* __restrict__ k,
@@ -312,7 +359,8 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_attn_dkdv_kernel(rua_layout LQ,
                                                                   const float* __restrict__ lse,
                                                                   const float* __restrict__ delta,
                                                                   uint16_t* __restrict__ gk, uint16_t* __restrict__ gv,
-                                                                  int heads, float scale, int64_t nblk, int64_t items) {
+                                                                  int heads, float scale, int64_t nblk, int64_t items,
+                                                                  attn_band bd) {
   constexpr int PS = D + 8, TS = ATTN_QB + 8, NS = D / 16, ND = D / 32;
   __shared__ __attribute__((aligned(16))) uint16_t sQ[ATTN_QB * PS];
   __shared__ __attribute__((aligned(16))) uint16_t sQt[D * TS];
@@ -322,12 +370,13 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_attn_dkdv_kernel(rua_layout LQ,
   const int tid = (int)threadIdx.x, lane = tid & (RUA_WAVE - 1), j = lane & 31, g = lane >> 5;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
 
+  const int hkv = BAND ? bd.heads_kv : heads, G = BAND ? heads / hkv : 1;   // the heads of a kv row; the group
   for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
     const int64_t blk = item % nblk, bh = item / nblk;
-    const int h = (int)(bh % heads);
-    const int64_t b = bh / heads;
+    const int hk = (int)(bh % hkv);
+    const int64_t b = bh / hkv;
     const int64_t S = safe_len(LK, b);
-    if (blk == 0) attn_zero_padding<D>(LK, b, S, h, heads, gk, gv, nullptr, tid);
+    if (blk == 0) attn_zero_padding<D>(LK, b, S, hk, hkv, gk, gv, nullptr, tid);
     const int64_t k0 = blk * ATTN_BLOCK_TOK;
     if (k0 >= S) continue;
     const int64_t T = safe_len(LQ, b);
@@ -340,8 +389,8 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_attn_dkdv_kernel(rua_layout LQ,
     for (int st = 0; st < NS; ++st) {
       kf[st] = vf[st] = make_uint4(0u, 0u, 0u, 0u);
       if (krow >= 0) {
-        kf[st] = *(const uint4*)(k + (krow * heads + h) * (int64_t)D + 16 * st + 8 * g);
-        vf[st] = *(const uint4*)(v + (krow * heads + h) * (int64_t)D + 16 * st + 8 * g);
+        kf[st] = *(const uint4*)(k + (krow * hkv + hk) * (int64_t)D + 16 * st + 8 * g);
+        vf[st] = *(const uint4*)(v + (krow * hkv + hk) * (int64_t)D + 16 * st + 8 * g);
       }
     }
     attn_f32x16 dk[ND], dv[ND];
@@ -350,65 +399,76 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_attn_dkdv_kernel(rua_layout LQ,
 #pragma unroll
       for (int r = 0; r < 16; ++r) dk[dt][r] = dv[dt][r] = 0.f;
 
-    // under `causal` the queries below the block's first key see none of its keys
-    for (int64_t t0 = CAUSAL ? k0 : 0; t0 < T; t0 += ATTN_QB) {
-      __syncthreads();
-      attn_stage<D, ATTN_QB, true, true>(LQ, b, T, t0, h, heads, q, sQ, sQt, tid);
-      attn_stage<D, ATTN_QB, true, true>(LQ, b, T, t0, h, heads, go, sG, sGt, tid);
-      if (tid < ATTN_QB) {
-        const int64_t row = attn_row(LQ, b, t0 + tid, T);
-        sLse[tid] = row >= 0 ? lse[row * heads + h] : 0.f;
-        sDelta[tid] = row >= 0 ? delta[row * heads + h] : 0.f;
-      }
-      __syncthreads();
-      if (!live || (CAUSAL && t0 + ATTN_QB - 1 < w0)) continue;  // wholly above the wave's diagonal
-      attn_f32x16 s, dp;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) s[r] = dp[r] = 0.f;
-#pragma unroll
-      for (int st = 0; st < NS; ++st) {
-        s = X::mfma(*(const uint4*)(sQ + j * PS + 16 * st + 8 * g), kf[st], s);
-        dp = X::mfma(*(const uint4*)(sG + j * PS + 16 * st + 8 * g), vf[st], dp);
-      }
-      float p[16], ds[16];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int i = 8 * (r >> 2) + 4 * g + (r & 3);           // the query of this register
-        const int64_t t = t0 + i;
-        const bool ok = t < T && key < S && (!CAUSAL || key <= t);
-        p[r] = ok ? expf(s[r] * scale - sLse[i]) : 0.f;
-        ds[r] = ok ? p[r] * (dp[r] - sDelta[i]) : 0.f;
-      }
-      const uint4 db0 = attn_pack8<X>(ds), db1 = attn_pack8<X>(ds + 8);
-      const uint4 pb0 = attn_pack8<X>(p), pb1 = attn_pack8<X>(p + 8);
-      uint4 pl0 = pb0, pl1 = pb1;
-      if constexpr (X::SPLIT) {
-        pl0 = attn_pack8_lo<X>(p);
-        pl1 = attn_pack8_lo<X>(p + 8);
-      }
-#pragma unroll
-      for (int dt = 0; dt < ND; ++dt) {
-        const uint4 g0 = attn_ld_t<TS>(sGt, 32 * dt + j, 0, 0, g), g1 = attn_ld_t<TS>(sGt, 32 * dt + j, 0, 1, g);
-        dv[dt] = X::mfma(g0, pb0, dv[dt]);
-        dv[dt] = X::mfma(g1, pb1, dv[dt]);
-        if constexpr (X::SPLIT) {
-          dv[dt] = X::mfma(g0, pl0, dv[dt]);
-          dv[dt] = X::mfma(g1, pl1, dv[dt]);
+    // the queries that can see the block (under `causal` those below its first key see none of its keys), in tiles cut
+    // by position from 0
+    const int64_t shift = (BAND && bd.align_end) ? S - T : 0;
+    const int64_t tbeg = BAND ? attn_band_lo(k0 - shift, bd.right) / ATTN_QB * ATTN_QB : (CAUSAL ? k0 : 0);
+    const int64_t tend = BAND ? attn_band_hi(k0 + ATTN_BLOCK_TOK - 1 - shift, bd.left, T) : T;
+    for (int gi = 0; gi < G; ++gi) {
+      const int h = hk * G + gi;
+      for (int64_t t0 = tbeg; t0 < tend; t0 += ATTN_QB) {
+        __syncthreads();
+        attn_stage<D, ATTN_QB, true, true>(LQ, b, T, t0, h, heads, q, sQ, sQt, tid);
+        attn_stage<D, ATTN_QB, true, true>(LQ, b, T, t0, h, heads, go, sG, sGt, tid);
+        if (tid < ATTN_QB) {
+          const int64_t row = attn_row(LQ, b, t0 + tid, T);
+          sLse[tid] = row >= 0 ? lse[row * heads + h] : 0.f;
+          sDelta[tid] = row >= 0 ? delta[row * heads + h] : 0.f;
         }
-        dk[dt] = X::mfma(attn_ld_t<TS>(sQt, 32 * dt + j, 0, 0, g), db0, dk[dt]);
-        dk[dt] = X::mfma(attn_ld_t<TS>(sQt, 32 * dt + j, 0, 1, g), db1, dk[dt]);
+        __syncthreads();
+        if (!live || (CAUSAL && t0 + ATTN_QB - 1 < w0)) continue;  // wholly above the wave's diagonal
+        if constexpr (BAND) {                                     // wholly outside the band of the wave's keys
+          if (bd.right >= 0 && w0 - (t0 + ATTN_QB - 1 + shift) > bd.right) continue;
+          if (bd.left >= 0 && w0 + 31 - (t0 + shift) < -bd.left) continue;
+        }
+        attn_f32x16 s, dp;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s[r] = dp[r] = 0.f;
+#pragma unroll
+        for (int st = 0; st < NS; ++st) {
+          s = X::mfma(*(const uint4*)(sQ + j * PS + 16 * st + 8 * g), kf[st], s);
+          dp = X::mfma(*(const uint4*)(sG + j * PS + 16 * st + 8 * g), vf[st], dp);
+        }
+        float p[16], ds[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int i = 8 * (r >> 2) + 4 * g + (r & 3);           // the query of this register
+          const int64_t t = t0 + i;
+          const bool ok = t < T && key < S && (!CAUSAL || key <= t) && (!BAND || attn_band_sees(bd, key - (t + shift)));
+          p[r] = ok ? expf(s[r] * scale - sLse[i]) : 0.f;
+          ds[r] = ok ? p[r] * (dp[r] - sDelta[i]) : 0.f;
+        }
+        const uint4 db0 = attn_pack8<X>(ds), db1 = attn_pack8<X>(ds + 8);
+        const uint4 pb0 = attn_pack8<X>(p), pb1 = attn_pack8<X>(p + 8);
+        uint4 pl0 = pb0, pl1 = pb1;
+        if constexpr (X::SPLIT) {
+          pl0 = attn_pack8_lo<X>(p);
+          pl1 = attn_pack8_lo<X>(p + 8);
+        }
+#pragma unroll
+        for (int dt = 0; dt < ND; ++dt) {
+          const uint4 g0 = attn_ld_t<TS>(sGt, 32 * dt + j, 0, 0, g), g1 = attn_ld_t<TS>(sGt, 32 * dt + j, 0, 1, g);
+          dv[dt] = X::mfma(g0, pb0, dv[dt]);
+          dv[dt] = X::mfma(g1, pb1, dv[dt]);
+          if constexpr (X::SPLIT) {
+            dv[dt] = X::mfma(g0, pl0, dv[dt]);
+            dv[dt] = X::mfma(g1, pl1, dv[dt]);
+          }
+          dk[dt] = X::mfma(attn_ld_t<TS>(sQt, 32 * dt + j, 0, 0, g), db0, dk[dt]);
+          dk[dt] = X::mfma(attn_ld_t<TS>(sQt, 32 * dt + j, 0, 1, g), db1, dk[dt]);
+        }
       }
     }
 
     if (krow >= 0) {
-      attn_store_row<X, D>(dk, scale, gk + (krow * heads + h) * (int64_t)D, g);
-      attn_store_row<X, D>(dv, 1.f, gv + (krow * heads + h) * (int64_t)D, g);
+      attn_store_row<X, D>(dk, scale, gk + (krow * hkv + hk) * (int64_t)D, g);
+      attn_store_row<X, D>(dv, 1.f, gv + (krow * hkv + hk) * (int64_t)D, g);
     }
   }
 }
 
 // ---------------------------------------------------------------- backward 3: dQ, a lane is a query
-template <typename X, int D, bool CAUSAL>
+template <typename X, int D, bool CAUSAL, bool BAND = false>
 __global__ __launch_bounds__(RUA_BLOCK) void seg_attn_dq_kernel(rua_layout LQ, rua_layout LK,
                                                                 const uint16_t* __restrict__ q,
                                                                 const uint16_t* __restrict__ k,
@@ -417,7 +477,7 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_attn_dq_kernel(rua_layout LQ, r
                                                                 const float* __restrict__ lse,
                                                                 const float* __restrict__ delta,
                                                                 uint16_t* __restrict__ gq, int heads, float scale,
-                                                                int64_t nblk, int64_t items) {
+                                                                int64_t nblk, int64_t items, attn_band bd) {
   constexpr int PS = D + 8, TS = ATTN_KB + 8, NS = D / 16, ND = D / 32;
   __shared__ __attribute__((aligned(16))) uint16_t sK[ATTN_KB * PS];
   __shared__ __attribute__((aligned(16))) uint16_t sKt[D * TS];
@@ -455,17 +515,25 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_attn_dq_kernel(rua_layout LQ, r
 #pragma unroll
       for (int r = 0; r < 16; ++r) dq[dt][r] = 0.f;
 
-    const int64_t kend = attn_key_end<CAUSAL>(S, q0);
-    for (int64_t k0 = 0; k0 < kend; k0 += ATTN_KB) {
+    // the same walk as the forward's
+    const int hkv = BAND ? bd.heads_kv : heads, hk = BAND ? h / (heads / hkv) : h;
+    const int64_t shift = (BAND && bd.align_end) ? S - T : 0;
+    const int64_t kbeg = BAND ? attn_band_lo(q0 + shift, bd.left) / ATTN_KB * ATTN_KB : 0;
+    const int64_t kend = BAND ? attn_band_hi(q0 + ATTN_BLOCK_TOK - 1 + shift, bd.right, S) : attn_key_end<CAUSAL>(S, q0);
+    for (int64_t k0 = kbeg; k0 < kend; k0 += ATTN_KB) {
       __syncthreads();
-      attn_stage<D, ATTN_KB, true, true>(LK, b, S, k0, h, heads, k, sK, sKt, tid);
-      attn_stage<D, ATTN_KB, true, false>(LK, b, S, k0, h, heads, v, sV, nullptr, tid);
+      attn_stage<D, ATTN_KB, true, true>(LK, b, S, k0, hk, hkv, k, sK, sKt, tid);
+      attn_stage<D, ATTN_KB, true, false>(LK, b, S, k0, hk, hkv, v, sV, nullptr, tid);
       __syncthreads();
       if (!live) continue;
 #pragma unroll
       for (int sub = 0; sub < ATTN_KB / 32; ++sub) {
         const int64_t ks = k0 + 32 * sub;
         if (ks >= kend || (CAUSAL && ks > w0 + 31)) break;
+        if constexpr (BAND) {
+          if (bd.right >= 0 && ks - (w0 + 31 + shift) > bd.right) break;
+          if (bd.left >= 0 && ks + 31 - (w0 + shift) < -bd.left) continue;
+        }
         attn_f32x16 s, dp;
 #pragma unroll
         for (int r = 0; r < 16; ++r) s[r] = dp[r] = 0.f;
@@ -478,7 +546,7 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_attn_dq_kernel(rua_layout LQ, r
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int64_t key = ks + 8 * (r >> 2) + 4 * g + (r & 3);
-          const bool ok = qrow >= 0 && key < S && (!CAUSAL || key <= tq);
+          const bool ok = qrow >= 0 && key < S && (!CAUSAL || key <= tq) && (!BAND || attn_band_sees(bd, key - (tq + shift)));
           ds[r] = ok ? expf(s[r] * scale - my_lse) * (dp[r] - my_delta) : 0.f;
         }
         const uint4 db0 = attn_pack8<X>(ds), db1 = attn_pack8<X>(ds + 8);
@@ -495,13 +563,14 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_attn_dq_kernel(rua_layout LQ, r
 }
 
 // ---------------------------------------------------------------- host side
-static int attn_check_entry(const rua_layout* lq, const rua_layout* lk, int32_t heads, int32_t D, int32_t dtype,
-                            double scale, int64_t bound) {
+static int attn_check_entry(const rua_layout* lq, const rua_layout* lk, int32_t heads, int32_t heads_kv, int32_t D,
+                            int32_t dtype, double scale, int64_t bound) {
   int e;
   if ((e = sm_check_layout(lq)) != 0) return e;
   if ((e = sm_check_layout(lk)) != 0) return e;
   if (lk->B != lq->B) return RUA_EINVAL;
   if (heads <= 0 || (D != 32 && D != 64 && D != 128)) return RUA_EINVAL;
+  if (heads_kv <= 0 || heads % heads_kv != 0) return RUA_EINVAL;
   if (dtype != RUA_BF16 && dtype != RUA_F16) return RUA_EINVAL;
   if (!(scale == scale) || scale - scale != 0.0 || bound < 0) return RUA_EINVAL;    // a finite number
   return 0;
@@ -532,45 +601,71 @@ static bool attn_items(int64_t B, int32_t heads, int64_t bound, int64_t& nblk, i
     }                                                                                                                  \
   } while (0)
 
-}  // namespace rua
+// LAUNCH(payload type, D) by (dtype, D): the band instantiations <X, D, false, true>
+#define RUA_ATTN_DISPATCH_BAND(dtype, D, LAUNCH)                                                                       \
+  do {                                                                                                                 \
+    if ((dtype) == RUA_BF16) {                                                                                         \
+      if ((D) == 32) LAUNCH(at_bf16, 32); else if ((D) == 64) LAUNCH(at_bf16, 64); else LAUNCH(at_bf16, 128);          \
+    } else {                                                                                                           \
+      if ((D) == 32) LAUNCH(at_f16, 32); else if ((D) == 64) LAUNCH(at_f16, 64); else LAUNCH(at_f16, 128);             \
+    }                                                                                                                  \
+  } while (0)
 
-extern "C" int rua_segment_attention_forward(const rua_layout* q, const rua_layout* kv, const void* q_ptr,
-                                             const void* k_ptr, const void* v_ptr, void* out, void* lse, int32_t heads,
-                                             int32_t D, int32_t dtype, int32_t causal, double scale, int64_t T_max,
-                                             void* stream) {
-  using namespace rua;
+// the trace line of one of the three walks: the plain form names `causal`, the band form its four words
+static void attn_trace(const char* role, const attn_band* band, int32_t D, int32_t heads, bool causal, const rua_layout& LQ,
+                       const rua_layout& LK, unsigned grid) {
+  if (band)
+    seg_trace("seg_attn_band_%s_kernel D=%d heads=%d kvheads=%d left=%lld right=%lld end=%d kind=%d kvkind=%d grid=%u", role,
+              D, heads, band->heads_kv, (long long)band->left, (long long)band->right, band->align_end, LQ.kind, LK.kind,
+              grid);
+  else
+    seg_trace("seg_attn_%s_kernel D=%d heads=%d causal=%d kind=%d kvkind=%d grid=%u", role, D, heads, (int)causal, LQ.kind,
+              LK.kind, grid);
+}
+
+// both forward entry points; `band` is null for the plain form, which launches the <X, D, CAUSAL> instantiations
+static int attn_forward(const rua_layout* q, const rua_layout* kv, const void* q_ptr, const void* k_ptr,
+                        const void* v_ptr, void* out, void* lse, int32_t heads, int32_t D, int32_t dtype, bool causal,
+                        double scale, int64_t T_max, void* stream, const attn_band* band) {
+  const int32_t heads_kv = band ? band->heads_kv : heads;
   int e;
-  if ((e = attn_check_entry(q, kv, heads, D, dtype, scale, T_max)) != 0) return e;
+  if ((e = attn_check_entry(q, kv, heads, heads_kv, D, dtype, scale, T_max)) != 0) return e;
   if (q->B == 0 || T_max == 0) return 0;
   if ((q->n_rows > 0 && (!q_ptr || !out || !lse)) || (kv->n_rows > 0 && (!k_ptr || !v_ptr))) return RUA_EINVAL;
   if (attn_misaligned(q_ptr) || attn_misaligned(k_ptr) || attn_misaligned(v_ptr) || attn_misaligned(out) ||
       ((uintptr_t)lse & 3))
     return RUA_EALIGN;
-  if (seg_too_large(q, (int64_t)heads * D, 2) || seg_too_large(kv, (int64_t)heads * D, 2)) return RUA_ERANGE;
+  if (seg_too_large(q, (int64_t)heads * D, 2) || seg_too_large(kv, (int64_t)heads_kv * D, 2)) return RUA_ERANGE;
   int64_t nblk, items;
   unsigned grid;
   if (!attn_items(q->B, heads, T_max, nblk, items, grid)) return RUA_ERANGE;
   const hipStream_t s = (hipStream_t)stream;
   const rua_layout LQ = *q, LK = *kv;
-  seg_trace("seg_attn_forward_kernel D=%d heads=%d causal=%d kind=%d kvkind=%d grid=%u", D, heads, (int)(causal != 0),
-            LQ.kind, LK.kind, grid);
-#define RUA_ATTN_FWD(XX, DD, CC)                                                                                       \
-  hipLaunchKernelGGL((seg_attn_forward_kernel<XX, DD, CC>), dim3(grid), dim3(RUA_BLOCK), 0, s, LQ, LK,                 \
-                     (const uint16_t*)q_ptr, (const uint16_t*)k_ptr, (const uint16_t*)v_ptr, (uint16_t*)out,           \
-                     (float*)lse, (int)heads, (float)scale, nblk, items)
-  RUA_ATTN_DISPATCH(dtype, D, causal != 0, RUA_ATTN_FWD);
+  const attn_band bd = band ? *band : attn_band{-1, -1, heads, 0};
+  attn_trace("forward", band, D, heads, causal, LQ, LK, grid);
+#define RUA_ATTN_FWD_ARGS                                                                                              \
+  dim3(grid), dim3(RUA_BLOCK), 0, s, LQ, LK, (const uint16_t*)q_ptr, (const uint16_t*)k_ptr, (const uint16_t*)v_ptr,   \
+      (uint16_t*)out, (float*)lse, (int)heads, (float)scale, nblk, items, bd
+#define RUA_ATTN_FWD(XX, DD, CC) hipLaunchKernelGGL((seg_attn_forward_kernel<XX, DD, CC>), RUA_ATTN_FWD_ARGS)
+#define RUA_ATTN_FWD_BAND(XX, DD) hipLaunchKernelGGL((seg_attn_forward_kernel<XX, DD, false, true>), RUA_ATTN_FWD_ARGS)
+  if (band)
+    RUA_ATTN_DISPATCH_BAND(dtype, D, RUA_ATTN_FWD_BAND);
+  else
+    RUA_ATTN_DISPATCH(dtype, D, causal, RUA_ATTN_FWD);
+#undef RUA_ATTN_FWD_BAND
 #undef RUA_ATTN_FWD
+#undef RUA_ATTN_FWD_ARGS
   return (int)hipGetLastError();
 }
 
-extern "C" int rua_segment_attention_backward(const rua_layout* q, const rua_layout* kv, const void* q_ptr,
-                                              const void* k_ptr, const void* v_ptr, const void* out, const void* lse,
-                                              const void* grad_out, void* grad_q, void* grad_k, void* grad_v, void* ws,
-                                              int32_t heads, int32_t D, int32_t dtype, int32_t causal, double scale,
-                                              int64_t T_max, int64_t S_max, void* stream) {
-  using namespace rua;
+// both backward entry points: delta, then dK / dV (over the kv heads in the band form), then dQ
+static int attn_backward(const rua_layout* q, const rua_layout* kv, const void* q_ptr, const void* k_ptr,
+                         const void* v_ptr, const void* out, const void* lse, const void* grad_out, void* grad_q,
+                         void* grad_k, void* grad_v, void* ws, int32_t heads, int32_t D, int32_t dtype, bool c,
+                         double scale, int64_t T_max, int64_t S_max, void* stream, const attn_band* band) {
+  const int32_t heads_kv = band ? band->heads_kv : heads;
   int e;
-  if ((e = attn_check_entry(q, kv, heads, D, dtype, scale, T_max)) != 0) return e;
+  if ((e = attn_check_entry(q, kv, heads, heads_kv, D, dtype, scale, T_max)) != 0) return e;
   if (S_max < 0) return RUA_EINVAL;
   if (q->B == 0) return 0;
   if (q->n_rows > 0 && (!q_ptr || !out || !lse || !grad_out || !grad_q || !ws)) return RUA_EINVAL;
@@ -583,10 +678,10 @@ extern "C" int rua_segment_attention_backward(const rua_layout* q, const rua_lay
   for (const void* p : ptrs)
     if (attn_misaligned(p)) return RUA_EALIGN;
   if (((uintptr_t)lse & 3) || ((uintptr_t)ws & 3)) return RUA_EALIGN;
-  if (seg_too_large(q, (int64_t)heads * D, 2) || seg_too_large(kv, (int64_t)heads * D, 2)) return RUA_ERANGE;
+  if (seg_too_large(q, (int64_t)heads * D, 2) || seg_too_large(kv, (int64_t)heads_kv * D, 2)) return RUA_ERANGE;
   const hipStream_t s = (hipStream_t)stream;
   const rua_layout LQ = *q, LK = *kv;
-  const bool c = causal != 0;
+  const attn_band bd = band ? *band : attn_band{-1, -1, heads, 0};
   float* delta = (float*)ws;
 
   if (T_max > 0 && q->n_rows > 0) {
@@ -603,28 +698,78 @@ extern "C" int rua_segment_attention_backward(const rua_layout* q, const rua_lay
   int64_t nblk, items;
   unsigned grid;
   if (S_max > 0) {
-    if (!attn_items(q->B, heads, S_max, nblk, items, grid)) return RUA_ERANGE;
-    seg_trace("seg_attn_dkdv_kernel D=%d heads=%d causal=%d kind=%d kvkind=%d grid=%u", D, heads, (int)c, LQ.kind, LK.kind,
-              grid);
-#define RUA_ATTN_DKDV(XX, DD, CC)                                                                                      \
-  hipLaunchKernelGGL((seg_attn_dkdv_kernel<XX, DD, CC>), dim3(grid), dim3(RUA_BLOCK), 0, s, LQ, LK,                    \
-                     (const uint16_t*)q_ptr, (const uint16_t*)k_ptr, (const uint16_t*)v_ptr, (const uint16_t*)grad_out, \
-                     (const float*)lse, (const float*)delta, (uint16_t*)grad_k, (uint16_t*)grad_v, (int)heads,         \
-                     (float)scale, nblk, items)
-    RUA_ATTN_DISPATCH(dtype, D, c, RUA_ATTN_DKDV);
+    if (!attn_items(q->B, heads_kv, S_max, nblk, items, grid)) return RUA_ERANGE;
+    attn_trace("dkdv", band, D, heads, c, LQ, LK, grid);
+#define RUA_ATTN_DKDV_ARGS                                                                                             \
+  dim3(grid), dim3(RUA_BLOCK), 0, s, LQ, LK, (const uint16_t*)q_ptr, (const uint16_t*)k_ptr, (const uint16_t*)v_ptr,   \
+      (const uint16_t*)grad_out, (const float*)lse, (const float*)delta, (uint16_t*)grad_k, (uint16_t*)grad_v,         \
+      (int)heads, (float)scale, nblk, items, bd
+#define RUA_ATTN_DKDV(XX, DD, CC) hipLaunchKernelGGL((seg_attn_dkdv_kernel<XX, DD, CC>), RUA_ATTN_DKDV_ARGS)
+#define RUA_ATTN_DKDV_BAND(XX, DD) hipLaunchKernelGGL((seg_attn_dkdv_kernel<XX, DD, false, true>), RUA_ATTN_DKDV_ARGS)
+    if (band)
+      RUA_ATTN_DISPATCH_BAND(dtype, D, RUA_ATTN_DKDV_BAND);
+    else
+      RUA_ATTN_DISPATCH(dtype, D, c, RUA_ATTN_DKDV);
+#undef RUA_ATTN_DKDV_BAND
 #undef RUA_ATTN_DKDV
+#undef RUA_ATTN_DKDV_ARGS
     if ((e = (int)hipGetLastError()) != 0) return e;
   }
   if (T_max > 0) {
     if (!attn_items(q->B, heads, T_max, nblk, items, grid)) return RUA_ERANGE;
-    seg_trace("seg_attn_dq_kernel D=%d heads=%d causal=%d kind=%d kvkind=%d grid=%u", D, heads, (int)c, LQ.kind, LK.kind,
-              grid);
-#define RUA_ATTN_DQ(XX, DD, CC)                                                                                        \
-  hipLaunchKernelGGL((seg_attn_dq_kernel<XX, DD, CC>), dim3(grid), dim3(RUA_BLOCK), 0, s, LQ, LK,                      \
-                     (const uint16_t*)q_ptr, (const uint16_t*)k_ptr, (const uint16_t*)v_ptr, (const uint16_t*)grad_out, \
-                     (const float*)lse, (const float*)delta, (uint16_t*)grad_q, (int)heads, (float)scale, nblk, items)
-    RUA_ATTN_DISPATCH(dtype, D, c, RUA_ATTN_DQ);
+    attn_trace("dq", band, D, heads, c, LQ, LK, grid);
+#define RUA_ATTN_DQ_ARGS                                                                                               \
+  dim3(grid), dim3(RUA_BLOCK), 0, s, LQ, LK, (const uint16_t*)q_ptr, (const uint16_t*)k_ptr, (const uint16_t*)v_ptr,   \
+      (const uint16_t*)grad_out, (const float*)lse, (const float*)delta, (uint16_t*)grad_q, (int)heads, (float)scale,  \
+      nblk, items, bd
+#define RUA_ATTN_DQ(XX, DD, CC) hipLaunchKernelGGL((seg_attn_dq_kernel<XX, DD, CC>), RUA_ATTN_DQ_ARGS)
+#define RUA_ATTN_DQ_BAND(XX, DD) hipLaunchKernelGGL((seg_attn_dq_kernel<XX, DD, false, true>), RUA_ATTN_DQ_ARGS)
+    if (band)
+      RUA_ATTN_DISPATCH_BAND(dtype, D, RUA_ATTN_DQ_BAND);
+    else
+      RUA_ATTN_DISPATCH(dtype, D, c, RUA_ATTN_DQ);
+#undef RUA_ATTN_DQ_BAND
 #undef RUA_ATTN_DQ
+#undef RUA_ATTN_DQ_ARGS
   }
   return (int)hipGetLastError();
+}
+
+}  // namespace rua
+
+extern "C" int rua_segment_attention_forward(const rua_layout* q, const rua_layout* kv, const void* q_ptr,
+                                             const void* k_ptr, const void* v_ptr, void* out, void* lse, int32_t heads,
+                                             int32_t D, int32_t dtype, int32_t causal, double scale, int64_t T_max,
+                                             void* stream) {
+  return rua::attn_forward(q, kv, q_ptr, k_ptr, v_ptr, out, lse, heads, D, dtype, causal != 0, scale, T_max, stream,
+                           nullptr);
+}
+
+extern "C" int rua_segment_attention_backward(const rua_layout* q, const rua_layout* kv, const void* q_ptr,
+                                              const void* k_ptr, const void* v_ptr, const void* out, const void* lse,
+                                              const void* grad_out, void* grad_q, void* grad_k, void* grad_v, void* ws,
+                                              int32_t heads, int32_t D, int32_t dtype, int32_t causal, double scale,
+                                              int64_t T_max, int64_t S_max, void* stream) {
+  return rua::attn_backward(q, kv, q_ptr, k_ptr, v_ptr, out, lse, grad_out, grad_q, grad_k, grad_v, ws, heads, D, dtype,
+                            causal != 0, scale, T_max, S_max, stream, nullptr);
+}
+
+extern "C" int rua_segment_attention_band_forward(const rua_layout* q, const rua_layout* kv, const void* q_ptr,
+                                                  const void* k_ptr, const void* v_ptr, void* out, void* lse,
+                                                  int32_t heads, int32_t D, int32_t dtype, int32_t heads_kv, int64_t left,
+                                                  int64_t right, int32_t align_end, double scale, int64_t T_max,
+                                                  void* stream) {
+  const rua::attn_band bd = {left < 0 ? -1 : left, right < 0 ? -1 : right, heads_kv, align_end != 0};
+  return rua::attn_forward(q, kv, q_ptr, k_ptr, v_ptr, out, lse, heads, D, dtype, false, scale, T_max, stream, &bd);
+}
+
+extern "C" int rua_segment_attention_band_backward(const rua_layout* q, const rua_layout* kv, const void* q_ptr,
+                                                   const void* k_ptr, const void* v_ptr, const void* out,
+                                                   const void* lse, const void* grad_out, void* grad_q, void* grad_k,
+                                                   void* grad_v, void* ws, int32_t heads, int32_t D, int32_t dtype,
+                                                   int32_t heads_kv, int64_t left, int64_t right, int32_t align_end,
+                                                   double scale, int64_t T_max, int64_t S_max, void* stream) {
+  const rua::attn_band bd = {left < 0 ? -1 : left, right < 0 ? -1 : right, heads_kv, align_end != 0};
+  return rua::attn_backward(q, kv, q_ptr, k_ptr, v_ptr, out, lse, grad_out, grad_q, grad_k, grad_v, ws, heads, D, dtype,
+                            false, scale, T_max, S_max, stream, &bd);
 }
