@@ -804,6 +804,43 @@ int rua_segment_attention_band_backward(const rua_layout* q, const rua_layout* k
                                         int32_t dtype, int32_t heads_kv, int64_t left, int64_t right, int32_t align_end,
                                         double scale, int64_t T_max, int64_t S_max, void* stream);
 
+/* Per-sequence attention for DECODE steps (an EXTENSION, added to ABI 6 — the version number did not move;
+ * csrc/rua_attention_decode.hip, csrc/rua_attention_decode_plan.h): the forward of the band form for
+ * sequences of at most 32 queries over a ragged KV cache, as a split-KV kernel; no backward.
+ * rua_attention_decode_plan is a PURE HOST function (no device, no allocation) of its integer arguments: with G = heads /
+ * heads_kv and ncb = ceil(T_max G / 32) column blocks it answers
+ *   kv_chunk   the keys per split: kv_chunk_in when that is > 0 (a multiple of 128), else chosen so that about 2 048
+ *              work items exist (an untuned heuristic), never below 128; the whole cache (rounded up to 128) when
+ *              B heads_kv ncb already reaches that or S_max <= 128;
+ *   n_split    max(1, ceil(S_max / kv_chunk));
+ *   ws_bytes   n_split > 1: B heads_kv ncb n_split x 32 (D + 2) x 4 (a slot per work item: m[32], l[32], acc[32][D],
+ *              fp32); n_split == 1: 0.
+ * RUA_EINVAL: B < 0, heads or heads_kv <= 0 or heads % heads_kv != 0, D outside {32, 64, 128}, T_max < 0 or > 32,
+ * S_max < 0, kv_chunk_in < 0 or no multiple of 128; RUA_ERANGE: the items or the bytes do not fit 63 bits.
+ * rua_segment_attention_decode: the arguments of rua_segment_attention_band_forward, and `ws` / `ws_bytes` (at least the
+ * plan's bytes for the same arguments; 16-byte aligned; may be NULL when the plan asks for 0), `S_max` (the longest kv
+ * sequence) and `kv_chunk` (the plan's answer, or any positive multiple of 128).  The matrix columns of (sequence, kv
+ * head) are c = t G + gi — query position t, head hk G + gi — in blocks of 32; a work item is (sequence, kv head, column
+ * block, split), at most 4 096 workgroups stride over them; split sp owns the keys [sp kv_chunk, (sp + 1) kv_chunk) by
+ * position; the four waves of a workgroup divide the keys of every step of 128, and their (m, l, acc) are merged in the
+ * fixed order 0, 1, 2, 3.  n_split == 1: ONE launch writes out and lse.  n_split > 1: every live (column, split with
+ * sp kv_chunk < S_b) writes its unnormalised fp32 state to `ws`, and a second kernel merges the splits of every (query
+ * row, head) in ascending order by the same rule, rounds once and writes out and lse — no atomics, bitwise reproducible.
+ * The bits of a sequence depend on kv_chunk; they do not depend on the layouts.  `lse` is ALWAYS written (-inf where no
+ * key is visible, 0 in the padding rows of an L / R result, which get zero output rows).  T_max == 0 launches nothing
+ * except the padding zeros of an L / R result.
+ * Checks, before any HIP call: those of the band form, and S_max < 0, T_max > 32, a kv_chunk that is not a positive
+ * multiple of 128, ws_bytes below the plan's or a missing `ws` (RUA_EINVAL); a payload pointer or `ws` off 16 bytes, lse
+ * off 4 (RUA_EALIGN).  Trace: `seg_attn_decode_kernel` (D=, heads=, kvheads=, left=, right=, end=, cols= T_max G,
+ * chunk=, splits=, kind=, kvkind=, grid=) and, when n_split > 1, `seg_attn_decode_combine_kernel`. */
+int rua_attention_decode_plan(int64_t B, int32_t heads, int32_t heads_kv, int32_t D, int64_t T_max, int64_t S_max,
+                              int64_t kv_chunk_in, int64_t* kv_chunk, int64_t* n_split, int64_t* ws_bytes);
+int rua_segment_attention_decode(const rua_layout* q, const rua_layout* kv, const void* q_ptr, const void* k_ptr,
+                                 const void* v_ptr, void* out, void* lse, void* ws, int64_t ws_bytes, int32_t heads,
+                                 int32_t D, int32_t dtype, int32_t heads_kv, int64_t left, int64_t right,
+                                 int32_t align_end, double scale, int64_t T_max, int64_t S_max, int64_t kv_chunk,
+                                 void* stream);
+
 /* Per-sequence gated linear recurrence (an EXTENSION, added to ABI 6 — the version number did not move: the reference's
  * users pad, loop over the time steps with elementwise kernels and cast back).  For every sequence b of `lay` (ANY
  * layout) and column h, with u the position along the scan (u = t; reverse != 0: u = len - 1 - t):

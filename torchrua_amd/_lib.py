@@ -54,6 +54,7 @@ SCAN_DTYPES = {**DTYPES, torch.int64: I64}
 # per-sequence attention (rua_segment_attention_*): the payloads of the matrix instructions it uses, and its head sizes
 ATTN_DTYPES = {torch.bfloat16: BF16, torch.float16: F16}
 ATTN_HEAD_DIMS = (32, 64, 128)
+ATTN_DECODE_MAX_T = 32     # rua.h: the most queries per sequence of rua_segment_attention_decode
 
 
 class RuaLayout(Structure):
@@ -163,6 +164,11 @@ SYMBOLS = {
                                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                     c_int32, c_int32, c_int32, c_int32, c_int64, c_int64, c_int32,
                                                     c_double, c_int64, c_int64, c_void_p]),
+    'rua_attention_decode_plan': (c_int, [c_int64, c_int32, c_int32, c_int32, c_int64, c_int64, c_int64, POINTER(c_int64),
+                                          POINTER(c_int64), POINTER(c_int64)]),
+    'rua_segment_attention_decode': (c_int, [POINTER(RuaLayout), POINTER(RuaLayout), c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32,
+                                             c_int64, c_int64, c_int32, c_double, c_int64, c_int64, c_int64, c_void_p]),
     'rua_linear_scan_ws_bytes': (c_int64, [POINTER(RuaLayout), c_int64, c_int32]),
     'rua_segment_linear_scan': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_double, c_void_p, c_int64, c_int32,
                                         c_int32, c_void_p, c_void_p]),

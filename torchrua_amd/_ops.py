@@ -1605,6 +1605,35 @@ def attention(q: Tensor, k: Tensor, v: Tensor, plan: AttentionPlan) -> Tensor:
     return launch_attention_forward(plan, _plain(q), _plain(k), _plain(v))[0]
 
 
+def attention_decode_plan(B: int, heads: int, heads_kv: int, D: int, T_max: int, S_max: int,
+                          kv_chunk: Optional[int]) -> Tuple[int, int, int]:
+    """rua_attention_decode_plan, a pure host function: (kv_chunk, n_split, ws_bytes)."""
+    chunk, n_split, ws_bytes = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+    L.check(L.load().rua_attention_decode_plan(B, heads, heads_kv, D, T_max, S_max, kv_chunk or 0, ctypes.byref(chunk),
+                                               ctypes.byref(n_split), ctypes.byref(ws_bytes)), 'rua_attention_decode_plan')
+    return chunk.value, n_split.value, ws_bytes.value
+
+
+def attention_decode(q: Tensor, k: Tensor, v: Tensor, plan: AttentionPlan, kv_chunk: Optional[int]) -> Tuple[Tensor, Tensor]:
+    """rua_segment_attention_decode: one launch, or two when the plan splits the keys.  (out of q's storage shape and
+    dtype, lse [*q storage rows, heads] fp32), without a graph.  No sequence or no query: zeros without a launch."""
+    q, k, v = _plain(q), _plain(k), _plain(v)
+    dev = L.require_device(q, k, v)
+    lead = tuple(q.shape[:-2])
+    if not plan.q.B or not plan.T_max or not q.numel():
+        return torch.zeros_like(q), torch.zeros(lead + (plan.heads,), dtype=torch.float32, device=dev)
+    s_max = plan.kv_bound() if k.numel() else 0
+    chunk, _, ws_bytes = attention_decode_plan(plan.q.B, plan.heads, plan.heads_kv, plan.D, plan.T_max, s_max, kv_chunk)
+    q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+    out = torch.empty_like(q)
+    lse = torch.empty(lead + (plan.heads,), dtype=torch.float32, device=dev)
+    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev) if ws_bytes else None
+    _call('attention_decode', 'rua_segment_attention_decode', dev, plan.q.ref(), plan.kv.ref(), L.ptr(q), L.ptr(k),
+          L.ptr(v), L.ptr(out), L.ptr(lse), L.ptr(ws), ws_bytes, plan.heads, plan.D, L.ATTN_DTYPES[q.dtype], plan.heads_kv,
+          plan.left, 0 if plan.causal else plan.right, int(plan.align_end), plan.scale, plan.T_max, s_max, chunk)
+    return out, lse
+
+
 # ------------------------------------------------------------------ per-sequence gated linear recurrence (an extension)
 def _gate_arg(data: Tensor, gate) -> Tuple[Optional[Tensor], float]:
     """(the gate tensor or None, the scalar gate): a tensor of the payload's storage shape, dtype and device, or ONE

@@ -57,17 +57,44 @@ is not a finite number; a `window` that is not None, an int >= 0 or a pair of su
 last a CPU tensor.
 
 OUT OF SCOPE: additive bias or arbitrary masks, dropout, fp32 / fp64 payloads, other D, returning the weights, second
-derivatives, split-K over one very long sequence, a decode kernel that packs a group's heads into the matrix rows when
-T_b is tiny (the band form is correct there and wastes the tile).
+derivatives.  Decode steps — a handful of queries per sequence against a long cache — are `attention_decode` below: it
+splits the keys of one sequence across workgroups and packs a group's heads into the matrix columns; `attention` is
+correct there and wastes the tile, and never dispatches to it (the fold order differs).
+
+DECODE.
+
+    attention_decode(q, k, v, causal=True, scale=None, window=None, align='end', kv_chunk=None, return_lse=False)
+                                                                                    also q.attention_decode(k, v, ...)
+    segment_attention_decode(q, q_sizes, k, v, kv_sizes, ...the same keywords...)   -> Tensor [N, heads, D]
+
+The forward of `attention` for sequences of at most 32 queries (one new token per sequence, or a few for speculative
+decoding or verification) over a ragged KV cache, as a split-KV kernel (csrc/rua_attention_decode.hip).  The
+mathematics, the containers, the argument checks and the one-answer semantics are those above.  The differences:
+  * THE DEFAULTS ARE THE DECODE MASK, `causal=True, align='end'` — not `attention`'s (`causal=False, align='start'`).
+  * Forward only: the result carries no graph; with grad mode on and a `q.data` / `k.data` / `v.data` that requires grad
+    it raises and names `attention`, the differentiable operator.
+  * At most 32 queries per sequence; a longer one is refused and pointed to `attention` — from the host bound before any
+    device work when the lengths are known, else after the one [B] read-back `attention` also makes.
+  * The kv lengths are needed on the host (the longest one sizes the splits): nothing is read back with host lengths,
+    otherwise ONE blocking [B] copy, attached to the container.
+  * `kv_chunk`: the keys per split, None (the plan chooses: rua_attention_decode_plan, from B, the head counts, the
+    longest q and kv sequence — never from a layout) or a positive multiple of 128.  THE BITS OF ONE SEQUENCE DEPEND ON
+    THE PLAN — on `kv_chunk`, and through `kv_chunk=None` on the batch it is computed in; pin `kv_chunk` for run-to-run
+    identical bits across batches.  For one batch all 4 x 4 pairs of layouts give the same bits; every call is bitwise
+    reproducible (no atomics).
+  * `return_lse=True` returns (out, lse): lse fp32 [*q storage rows, heads], the logsumexp of the scaled visible scores,
+    -inf where nothing is visible, 0 in padding rows — what merging with attention over another cache segment needs.
+Out of scope there: gradients, more than 32 queries, paged or block-table caches, fp8 caches, additive bias, merging
+across calls (`return_lse` makes it possible outside), tuning the plan.
 """
 import torch
 
 from torchrua_amd import _meta as M
 from torchrua_amd import _ops as O
 from torchrua_amd.layout import (P, T, Z, cat_lay, cls_of, hidden_of, install, lay_hidden, lens_of, n_seq, rewrap)
-from torchrua_amd._lib import RuaError
+from torchrua_amd._lib import ATTN_DECODE_MAX_T, RuaError
 
-__all__ = ['attention', 'segment_attention']
+__all__ = ['attention', 'segment_attention', 'attention_decode', 'segment_attention_decode']
 
 
 def _known_bound(z: Z):
@@ -140,4 +167,75 @@ def segment_attention(q: T, q_sizes: T, k: T, v: T, kv_sizes: T, causal: bool = 
     return O.attention(q, k, v, plan)
 
 
-install(attention=attention)
+def _decode_checks(what: str, tensors, kv_chunk, q_bound) -> None:
+    """What attention_decode refuses on top of attention's checks, before the CPU-tensor refusal."""
+    if kv_chunk is not None and (isinstance(kv_chunk, bool) or not isinstance(kv_chunk, int) or kv_chunk <= 0 or
+                                 kv_chunk % 128):
+        raise RuaError(f'{what}: `kv_chunk` = {kv_chunk!r} is None or a positive multiple of 128 (the keys per split)')
+    if torch.is_grad_enabled():
+        for name, t in zip(('q', 'k', 'v'), tensors):
+            if t.requires_grad:
+                raise RuaError(f'{what}: `{name}` requires grad and {what} is forward only; `attention` is the '
+                               f'differentiable operator')
+    _at_most_decode(what, q_bound)
+
+
+def _at_most_decode(what: str, q_bound) -> None:
+    if q_bound is not None and q_bound > ATTN_DECODE_MAX_T:
+        raise RuaError(f'{what}: `q` holds a sequence of {q_bound} queries; a decode step has at most '
+                       f'{ATTN_DECODE_MAX_T} per sequence — use `attention`')
+
+
+def attention_decode(q: Z, k: Z, v: Z, causal: bool = True, scale=None, window=None, align: str = 'end', kv_chunk=None,
+                     return_lse: bool = False):
+    """`attention` for decode steps: at most 32 queries per sequence over a ragged KV cache, forward only, the keys split
+    across workgroups.  THE DEFAULTS ARE THE DECODE MASK (`causal=True, align='end'`), unlike `attention`'s."""
+    what = 'attention_decode'
+    for name, z in (('q', q), ('k', k), ('v', v)):
+        if cls_of(z) is None:
+            raise RuaError(f'{what}: `{name}` is a container (C / L / P / R); got {type(z).__name__}')
+
+    def before_device():
+        _same_lengths(what, k, v)
+        _decode_checks(what, (q.data, k.data, v.data), kv_chunk, _known_bound(q))
+
+    a = O.attention_args(what, q.data, hidden_of(q), n_seq(q), k.data, hidden_of(k), n_seq(k), v.data, hidden_of(v),
+                         n_seq(v), scale, causal, window, align, before_device=before_device)
+    t_max = _bound(q)
+    _at_most_decode(what, t_max)
+    plan = O.AttentionPlan(lay_hidden(q)[0], lay_hidden(k)[0], a.heads, a.D, bool(causal), a.scale, t_max,
+                           lambda: _bound(k), a.heads_kv, a.left, a.right, a.align_end)
+    out, lse = O.attention_decode(q.data, k.data, v.data, plan, kv_chunk)
+    return (rewrap(q, out), lse) if return_lse else rewrap(q, out)
+
+
+def segment_attention_decode(q: T, q_sizes: T, k: T, v: T, kv_sizes: T, causal: bool = True, scale=None, window=None,
+                             align: str = 'end', kv_chunk=None, return_lse: bool = False):
+    """`attention_decode` of every run of `q_sizes` rows of `q` [N, heads, D] over the run of `kv_sizes` rows of `k` / `v`
+    [M, heads_kv, D]."""
+    what = 'segment_attention_decode'
+    for name, t in (('q', q), ('q_sizes', q_sizes), ('k', k), ('v', v), ('kv_sizes', kv_sizes)):
+        if not isinstance(t, torch.Tensor):
+            raise RuaError(f'{what}: `{name}` is a tensor; got {type(t).__name__}')
+
+    def bound(sizes, known_only=False):
+        known = M.known_max_len(sizes) if sizes.numel() else 0
+        return known if known is not None or known_only else M.max_len(sizes)
+
+    def before_device():
+        if tuple(k.shape[:1]) != tuple(v.shape[:1]):
+            raise RuaError(f'{what}: `k` and `v` have the same lengths (one key and one value per kv token)')
+        _decode_checks(what, (q, k, v), kv_chunk, bound(q_sizes, True))
+
+    n_kv = int(kv_sizes.numel())
+    a = O.attention_args(what, q, tuple(q.shape[1:]), int(q_sizes.numel()), k, tuple(k.shape[1:]), n_kv, v,
+                         tuple(v.shape[1:]), n_kv, scale, causal, window, align, before_device=before_device)
+    t_max = bound(q_sizes)
+    _at_most_decode(what, t_max)
+    plan = O.AttentionPlan(cat_lay(q, q_sizes), cat_lay(k, kv_sizes), a.heads, a.D, bool(causal), a.scale, t_max,
+                           lambda: bound(kv_sizes), a.heads_kv, a.left, a.right, a.align_end)
+    out, lse = O.attention_decode(q, k, v, plan, kv_chunk)
+    return (out, lse) if return_lse else out
+
+
+install(attention=attention, attention_decode=attention_decode)
