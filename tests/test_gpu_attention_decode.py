@@ -1,7 +1,9 @@
 """attention_decode on the GPU against the float64 yardsticks of attention_band_util.reference (out) and
 attention_decode_util.lse_reference (lse), within the bounds of DESIGN 3.2s: the tile and split edges of every mask and
 group, the 4 x 4 pairs of layouts bit for bit with their read-backs, the band's two edges across splits, a plan that
-splits by itself and a batch larger than the grid.  `build`, `padding`, the names and `draw` are the attention tests'."""
+splits by itself and a batch larger than the grid.  `build`, `padding`, the names and `draw` are the attention tests'.
+In EDGES `kv_chunk=None` plans chunk 128 / 3 splits, the same as `kv_chunk=128`, and every split here is ONE 128-key
+step; the plan's other choices and walks of several steps are test_gpu_attention_decode_walk.py's."""
 import re
 
 import pytest
