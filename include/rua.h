@@ -841,6 +841,33 @@ int rua_segment_attention_decode(const rua_layout* q, const rua_layout* kv, cons
                                  int32_t align_end, double scale, int64_t T_max, int64_t S_max, int64_t kv_chunk,
                                  void* stream);
 
+/* rua_segment_attention_decode over an 8-BIT KV CACHE (an EXTENSION, added to ABI 6 — the version number did not move;
+ * csrc/rua_attention_decode_fp8.hip).  The arguments of rua_segment_attention_decode, and
+ *   kv_dtype            the element type of k_ptr / v_ptr: RUA_KV_E4M3 (OCP e4m3, torch.float8_e4m3fn: no infinities, NaN
+ *                       = 0x7F / 0xFF), one BYTE per element, a kv row holds heads_kv x D bytes; other codes are kept
+ *                       for other formats and are RUA_EINVAL today;
+ *   k_scale, v_scale    device float[heads_kv], or NULL for ones;
+ *   k_scale_by_value, v_scale_by_value   finite and > 0; the effective scale of kv head hk is the product (in fp32) of
+ *                       the by-value number with the tensor's entry.
+ * `dtype` stays the type of q and out (RUA_BF16 / RUA_F16).  The value of a cache element is float(code) * scale[hk],
+ * and the result is rua_segment_attention_decode of that dequantised cache: the same columns, work items, splits,
+ * merge order, workspace (rua_attention_decode_plan is the plan of both; the combine kernel is shared), zero rows, lse
+ * = -inf and padding zeros.  The codes are converted EXACTLY in registers (every finite e4m3 value is a bf16 and an f16
+ * value) and meet q in the 16-bit matrix instruction of `dtype`; k's scale is folded once per work item into the
+ * softmax scale, v's multiplies the merged fp32 accumulator once, before the finish (n_split == 1) or the partial
+ * (n_split > 1); powers of two make both exact.  Nothing saturates or clamps; a NaN code stays inside its (sequence,
+ * kv head).  `lse` is that of the scaled scores.
+ * Checks, before any HIP call: those of rua_segment_attention_decode, and an unknown kv_dtype, a by-value scale that is
+ * not finite and positive (RUA_EINVAL); a scale pointer off 4 bytes (RUA_EALIGN).  Trace: `seg_attn_decode_fp8_kernel`
+ * with the fields of `seg_attn_decode_kernel`, and `seg_attn_decode_combine_kernel` when n_split > 1. */
+#define RUA_KV_E4M3 1
+int rua_segment_attention_decode_fp8(const rua_layout* q, const rua_layout* kv, const void* q_ptr, const void* k_ptr,
+                                     const void* v_ptr, void* out, void* lse, void* ws, int64_t ws_bytes, int32_t heads,
+                                     int32_t D, int32_t dtype, int32_t heads_kv, int64_t left, int64_t right,
+                                     int32_t align_end, double scale, int64_t T_max, int64_t S_max, int64_t kv_chunk,
+                                     int32_t kv_dtype, const float* k_scale, const float* v_scale,
+                                     double k_scale_by_value, double v_scale_by_value, void* stream);
+
 /* Per-sequence gated linear recurrence (an EXTENSION, added to ABI 6 — the version number did not move: the reference's
  * users pad, loop over the time steps with elementwise kernels and cast back).  For every sequence b of `lay` (ANY
  * layout) and column h, with u the position along the scan (u = t; reverse != 0: u = len - 1 - t):

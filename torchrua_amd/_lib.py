@@ -55,6 +55,8 @@ SCAN_DTYPES = {**DTYPES, torch.int64: I64}
 ATTN_DTYPES = {torch.bfloat16: BF16, torch.float16: F16}
 ATTN_HEAD_DIMS = (32, 64, 128)
 ATTN_DECODE_MAX_T = 32     # rua.h: the most queries per sequence of rua_segment_attention_decode
+# rua.h: the kv_dtype codes of rua_segment_attention_decode_fp8 (RUA_KV_E4M3): the 8-bit caches attention_decode reads
+ATTN_KV_DTYPES = {torch.float8_e4m3fn: 1}
 
 
 class RuaLayout(Structure):
@@ -169,6 +171,10 @@ SYMBOLS = {
     'rua_segment_attention_decode': (c_int, [POINTER(RuaLayout), POINTER(RuaLayout), c_void_p, c_void_p, c_void_p,
                                              c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32,
                                              c_int64, c_int64, c_int32, c_double, c_int64, c_int64, c_int64, c_void_p]),
+    'rua_segment_attention_decode_fp8': (c_int, [POINTER(RuaLayout), POINTER(RuaLayout), c_void_p, c_void_p, c_void_p,
+                                                 c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32,
+                                                 c_int32, c_int64, c_int64, c_int32, c_double, c_int64, c_int64, c_int64,
+                                                 c_int32, c_void_p, c_void_p, c_double, c_double, c_void_p]),
     'rua_linear_scan_ws_bytes': (c_int64, [POINTER(RuaLayout), c_int64, c_int32]),
     'rua_segment_linear_scan': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_double, c_void_p, c_int64, c_int32,
                                         c_int32, c_void_p, c_void_p]),

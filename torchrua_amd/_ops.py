@@ -1457,19 +1457,26 @@ class AttentionArgs(NamedTuple):
 
 def attention_args(what: str, q, q_hidden, n_seq: int, k, k_hidden, n_k_seq: int, v, v_hidden, n_v_seq: int, scale,
                    causal=False, window=None, align='start',
-                   before_device: Optional[Callable[[], None]] = None) -> AttentionArgs:
+                   before_device: Optional[Callable[[], None]] = None, kv_8bit: bool = False) -> AttentionArgs:
     """AttentionArgs after the checks that come before any launch and need no lengths, each naming its argument:
     bf16 / f16 payloads of ONE dtype; `q` with exactly the hidden dimensions (heads, D), `k` with (heads_kv, D), heads a
     multiple of heads_kv, `v` like `k`; D of ATTN_HEAD_DIMS; the same number of sequences; one device; a finite `scale`
     (None: D ** -0.5); a `window` that is None, an int >= 0 or a pair of such or None, whose right side does not
     contradict `causal`; an `align` of 'start' / 'end'; and last (so that every other refusal can be met without a GPU)
-    the payloads on a HIP device."""
+    the payloads on a HIP device.  `kv_8bit` (attention_decode): `k` and `v` may BOTH be an 8-bit cache of
+    ATTN_KV_DTYPES instead of q's dtype; any other 1-byte dtype is refused by the name of the one that is read."""
+    cache = tuple(L.ATTN_KV_DTYPES) if kv_8bit else ()
     for name, t in (('q', q), ('k', k), ('v', v)):
-        if not isinstance(t, Tensor) or t.dtype not in L.ATTN_DTYPES:
+        if kv_8bit and name != 'q' and isinstance(t, Tensor) and t.dtype not in cache and t.element_size() == 1:
+            raise L.RuaError(f'{what}: `{name}` has dtype {t.dtype}; the 8-bit cache that is read is '
+                             f'{" / ".join(str(d) for d in cache)} (OCP e4m3)')
+        if not isinstance(t, Tensor) or t.dtype not in L.ATTN_DTYPES and (name == 'q' or t.dtype not in cache):
             raise L.RuaError(f'{what}: `{name}` is one of {list(L.ATTN_DTYPES)}; got '
                              f'{t.dtype if isinstance(t, Tensor) else type(t).__name__}')
+    if (k.dtype in cache) != (v.dtype in cache):
+        raise L.RuaError(f'{what}: `v` has dtype {v.dtype}, `k` {k.dtype}: an 8-bit cache holds both')
     for name, t in (('k', k), ('v', v)):
-        if t.dtype != q.dtype:
+        if t.dtype != q.dtype and t.dtype not in cache:
             raise L.RuaError(f'{what}: `{name}` has dtype {t.dtype}, `q` {q.dtype}')
     if len(q_hidden) != 2:
         raise L.RuaError(f'{what}: `q` has exactly the hidden dimensions (heads, D); got {tuple(q_hidden)}')
@@ -1614,11 +1621,34 @@ def attention_decode_plan(B: int, heads: int, heads_kv: int, D: int, T_max: int,
     return chunk.value, n_split.value, ws_bytes.value
 
 
-def attention_decode(q: Tensor, k: Tensor, v: Tensor, plan: AttentionPlan, kv_chunk: Optional[int]) -> Tuple[Tensor, Tensor]:
+def cache_scale(what: str, name: str, scale, cache: Tensor, heads_kv: int, q: Tensor) -> Tuple[Optional[Tensor], float]:
+    """(the scale tensor or None, the scale by value) of an 8-bit cache, checked before any launch: None (exactly 1), a
+    finite positive Python number, or a float32 tensor [heads_kv] on q's device without a graph.  A bf16 / f16 cache
+    has no scale."""
+    if scale is None:
+        return None, 1.0
+    if cache.dtype not in L.ATTN_KV_DTYPES:
+        raise L.RuaError(f'{what}: `{name}` is given and the cache has dtype {cache.dtype}: a scale belongs to an 8-bit '
+                         f'cache ({" / ".join(str(d) for d in L.ATTN_KV_DTYPES)})')
+    if isinstance(scale, Tensor):
+        if scale.dtype != torch.float32 or tuple(scale.shape) != (heads_kv,) or scale.device != q.device or scale.requires_grad:
+            raise L.RuaError(f'{what}: `{name}` is a float32 tensor [heads_kv] = [{heads_kv}] on {q.device} that does not '
+                             f'require grad; got {scale.dtype} {tuple(scale.shape)} on {scale.device}'
+                             f'{", requiring grad" if scale.requires_grad else ""}')
+        return scale, 1.0
+    if isinstance(scale, bool) or not isinstance(scale, (int, float)) or not 0 < scale < float('inf'):
+        raise L.RuaError(f'{what}: `{name}` = {scale!r} is None, a finite number > 0 or a float32 tensor [heads_kv]')
+    return None, float(scale)
+
+
+def attention_decode(q: Tensor, k: Tensor, v: Tensor, plan: AttentionPlan, kv_chunk: Optional[int],
+                     k_scale=(None, 1.0), v_scale=(None, 1.0)) -> Tuple[Tensor, Tensor]:
     """rua_segment_attention_decode: one launch, or two when the plan splits the keys.  (out of q's storage shape and
-    dtype, lse [*q storage rows, heads] fp32), without a graph.  No sequence or no query: zeros without a launch."""
+    dtype, lse [*q storage rows, heads] fp32), without a graph.  No sequence or no query: zeros without a launch.  An
+    8-bit cache (ATTN_KV_DTYPES) goes through rua_segment_attention_decode_fp8 with its scales, each cache_scale()'s
+    pair; the number travels by value: no fill launch."""
     q, k, v = _plain(q), _plain(k), _plain(v)
-    dev = L.require_device(q, k, v)
+    dev = L.require_device(q, k, v, k_scale[0], v_scale[0])
     lead = tuple(q.shape[:-2])
     if not plan.q.B or not plan.T_max or not q.numel():
         return torch.zeros_like(q), torch.zeros(lead + (plan.heads,), dtype=torch.float32, device=dev)
@@ -1628,9 +1658,15 @@ def attention_decode(q: Tensor, k: Tensor, v: Tensor, plan: AttentionPlan, kv_ch
     out = torch.empty_like(q)
     lse = torch.empty(lead + (plan.heads,), dtype=torch.float32, device=dev)
     ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev) if ws_bytes else None
-    _call('attention_decode', 'rua_segment_attention_decode', dev, plan.q.ref(), plan.kv.ref(), L.ptr(q), L.ptr(k),
-          L.ptr(v), L.ptr(out), L.ptr(lse), L.ptr(ws), ws_bytes, plan.heads, plan.D, L.ATTN_DTYPES[q.dtype], plan.heads_kv,
-          plan.left, 0 if plan.causal else plan.right, int(plan.align_end), plan.scale, plan.T_max, s_max, chunk)
+    args = (plan.q.ref(), plan.kv.ref(), L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), L.ptr(lse), L.ptr(ws), ws_bytes,
+            plan.heads, plan.D, L.ATTN_DTYPES[q.dtype], plan.heads_kv, plan.left, 0 if plan.causal else plan.right,
+            int(plan.align_end), plan.scale, plan.T_max, s_max, chunk)
+    if k.dtype in L.ATTN_KV_DTYPES:
+        ks, vs = (None if t is None else t.contiguous() for t in (k_scale[0], v_scale[0]))
+        _call('attention_decode_fp8', 'rua_segment_attention_decode_fp8', dev, *args, L.ATTN_KV_DTYPES[k.dtype], L.ptr(ks),
+              L.ptr(vs), k_scale[1], v_scale[1])
+    else:
+        _call('attention_decode', 'rua_segment_attention_decode', dev, *args)
     return out, lse
 
 

@@ -63,7 +63,8 @@ correct there and wastes the tile, and never dispatches to it (the fold order di
 
 DECODE.
 
-    attention_decode(q, k, v, causal=True, scale=None, window=None, align='end', kv_chunk=None, return_lse=False)
+    attention_decode(q, k, v, causal=True, scale=None, window=None, align='end', kv_chunk=None, return_lse=False,
+                     k_scale=None, v_scale=None)
                                                                                     also q.attention_decode(k, v, ...)
     segment_attention_decode(q, q_sizes, k, v, kv_sizes, ...the same keywords...)   -> Tensor [N, heads, D]
 
@@ -84,8 +85,20 @@ mathematics, the containers, the argument checks and the one-answer semantics ar
     reproducible (no atomics).
   * `return_lse=True` returns (out, lse): lse fp32 [*q storage rows, heads], the logsumexp of the scaled visible scores,
     -inf where nothing is visible, 0 in padding rows — what merging with attention over another cache segment needs.
-Out of scope there: gradients, more than 32 queries, paged or block-table caches, fp8 caches, additive bias, merging
-across calls (`return_lse` makes it possible outside), tuning the plan.
+  * AN 8-BIT CACHE: `k` and `v` may BOTH be `torch.float8_e4m3fn` (OCP e4m3) while `q` stays bf16 / f16 and fixes the
+    compute and output dtype (csrc/rua_attention_decode_fp8.hip).  `k_scale` / `v_scale` are None (exactly
+    1), a finite Python number > 0 (passed by value: no fill launch) or a float32 tensor [heads_kv] on q's device; the
+    value of a cache element is float(code) * scale[hk], and the result is attention_decode of that dequantised cache —
+    softmax_s(scale * q . (k8 * k_scale)) (v8 * v_scale), `lse` of those scaled scores — with the same zero rows, -inf
+    and padding zeros.  The codes are converted exactly in registers; power-of-two scales add no rounding at all, others
+    two to the score scale and one to the accumulator.  Nothing saturates or clamps; a NaN code (0x7F / 0xFF) stays
+    inside its (sequence, kv head).  Refused: an fp8 `q`; one cache fp8 and the other not; any other 1-byte dtype
+    (float8_e5m2, the fnuz types, uint8); a scale with a bf16 / f16 cache; a scale tensor that is not float32
+    [heads_kv] on q's device or requires grad; a scale number that is not finite and > 0 (bools are refused).
+    `attention` itself refuses fp8.
+Out of scope there: gradients, more than 32 queries, paged or block-table caches, additive bias, merging across calls
+(`return_lse` makes it possible outside), tuning the plan; of 8-bit caches: float8_e5m2 and the fnuz formats, per-token
+or per-block scales, int8 / int4, an fp8 `q` or output and the fp8 matrix instruction, a quantising `join`.
 """
 import torch
 
@@ -187,30 +200,35 @@ def _at_most_decode(what: str, q_bound) -> None:
 
 
 def attention_decode(q: Z, k: Z, v: Z, causal: bool = True, scale=None, window=None, align: str = 'end', kv_chunk=None,
-                     return_lse: bool = False):
+                     return_lse: bool = False, k_scale=None, v_scale=None):
     """`attention` for decode steps: at most 32 queries per sequence over a ragged KV cache, forward only, the keys split
-    across workgroups.  THE DEFAULTS ARE THE DECODE MASK (`causal=True, align='end'`), unlike `attention`'s."""
+    across workgroups.  THE DEFAULTS ARE THE DECODE MASK (`causal=True, align='end'`), unlike `attention`'s.  `k` / `v`
+    may be a float8_e4m3fn cache with per-kv-head `k_scale` / `v_scale`."""
     what = 'attention_decode'
     for name, z in (('q', q), ('k', k), ('v', v)):
         if cls_of(z) is None:
             raise RuaError(f'{what}: `{name}` is a container (C / L / P / R); got {type(z).__name__}')
 
+    scales = []
+
     def before_device():
         _same_lengths(what, k, v)
         _decode_checks(what, (q.data, k.data, v.data), kv_chunk, _known_bound(q))
+        scales.extend(O.cache_scale(what, name, s, z.data, hidden_of(k)[0], q.data)
+                      for name, s, z in (('k_scale', k_scale, k), ('v_scale', v_scale, v)))
 
     a = O.attention_args(what, q.data, hidden_of(q), n_seq(q), k.data, hidden_of(k), n_seq(k), v.data, hidden_of(v),
-                         n_seq(v), scale, causal, window, align, before_device=before_device)
+                         n_seq(v), scale, causal, window, align, before_device=before_device, kv_8bit=True)
     t_max = _bound(q)
     _at_most_decode(what, t_max)
     plan = O.AttentionPlan(lay_hidden(q)[0], lay_hidden(k)[0], a.heads, a.D, bool(causal), a.scale, t_max,
                            lambda: _bound(k), a.heads_kv, a.left, a.right, a.align_end)
-    out, lse = O.attention_decode(q.data, k.data, v.data, plan, kv_chunk)
+    out, lse = O.attention_decode(q.data, k.data, v.data, plan, kv_chunk, *scales)
     return (rewrap(q, out), lse) if return_lse else rewrap(q, out)
 
 
 def segment_attention_decode(q: T, q_sizes: T, k: T, v: T, kv_sizes: T, causal: bool = True, scale=None, window=None,
-                             align: str = 'end', kv_chunk=None, return_lse: bool = False):
+                             align: str = 'end', kv_chunk=None, return_lse: bool = False, k_scale=None, v_scale=None):
     """`attention_decode` of every run of `q_sizes` rows of `q` [N, heads, D] over the run of `kv_sizes` rows of `k` / `v`
     [M, heads_kv, D]."""
     what = 'segment_attention_decode'
@@ -226,15 +244,18 @@ def segment_attention_decode(q: T, q_sizes: T, k: T, v: T, kv_sizes: T, causal: 
         if tuple(k.shape[:1]) != tuple(v.shape[:1]):
             raise RuaError(f'{what}: `k` and `v` have the same lengths (one key and one value per kv token)')
         _decode_checks(what, (q, k, v), kv_chunk, bound(q_sizes, True))
+        scales.extend(O.cache_scale(what, name, s, t, int(k.shape[1]), q)
+                      for name, s, t in (('k_scale', k_scale, k), ('v_scale', v_scale, v)))
 
+    scales = []
     n_kv = int(kv_sizes.numel())
     a = O.attention_args(what, q, tuple(q.shape[1:]), int(q_sizes.numel()), k, tuple(k.shape[1:]), n_kv, v,
-                         tuple(v.shape[1:]), n_kv, scale, causal, window, align, before_device=before_device)
+                         tuple(v.shape[1:]), n_kv, scale, causal, window, align, before_device=before_device, kv_8bit=True)
     t_max = bound(q_sizes)
     _at_most_decode(what, t_max)
     plan = O.AttentionPlan(cat_lay(q, q_sizes), cat_lay(k, kv_sizes), a.heads, a.D, bool(causal), a.scale, t_max,
                            lambda: bound(kv_sizes), a.heads_kv, a.left, a.right, a.align_end)
-    out, lse = O.attention_decode(q, k, v, plan, kv_chunk)
+    out, lse = O.attention_decode(q, k, v, plan, kv_chunk, *scales)
     return (out, lse) if return_lse else out
 
 

@@ -46,14 +46,12 @@
 #include <stdio.h>
 #include <stdint.h>
 #include <math.h>
-#include "rua_attention_dev.h"
-#include "rua_attention_decode_plan.h"
+#include "rua_attention_decode_dev.h"
 
 namespace rua {
 
 static_assert(DEC_STEP == 32 * RUA_WAVES_PER_BLOCK && DEC_COLS == 32, "a wave owns 32 keys of a step; a tile is 32 x 32");
 constexpr int DEC_TS = 32 + 8;                     // tokens of a transposed V row in LDS, padded by 16 bytes
-constexpr int DEC_SLOT_HEAD = 2 * DEC_COLS;        // floats before acc in a workspace slot: m[32], l[32]
 
 // K (the A operand of the scores) and V (staged transposed below) of the 32 keys [ks, ks + 32): lane (j, g) takes the 16
 // bytes 16 st + 8 g .. + 7 of key ks + j, st = 0 .. D / 16 - 1; zeros when the key is past the end or `on` is false
@@ -71,11 +69,6 @@ __device__ __forceinline__ void dec_load(const rua_layout& LK, int64_t b, int64_
       vf[st] = *(const uint4*)(v + at + 16 * st);
     }
   }
-}
-
-// m* and the factor of every wave from the four (m_i) of a column: the merge rule, in the fixed order 0, 1, 2, 3
-__device__ __forceinline__ float dec_factor(float mi, float mstar) {
-  return mstar == -__builtin_inff() ? 0.f : expf(mi - mstar);
 }
 
 // ---------------------------------------------------------------- the walk: one (sequence, kv head, column block, split)
@@ -299,6 +292,55 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_attn_decode_combine_kernel(rua_
   if (dl == 0) lse[row * heads + h] = lstar > 0.f ? mstar + logf(lstar) : NEG_INF;
 }
 
+int dec_prepare(const rua_layout* q, const rua_layout* kv, const void* q_ptr, const void* k_ptr, const void* v_ptr,
+                const void* out, const void* lse, const void* ws, int64_t ws_bytes, int32_t heads, int32_t D,
+                int32_t dtype, int32_t heads_kv, int64_t left, int64_t right, int32_t align_end, double scale,
+                int64_t T_max, int64_t S_max, int64_t kv_chunk, int kv_es, dec_launch& L) {
+  int e;
+  dec_plan& p = L.p;
+  L.run = false;
+  if ((e = attn_check_entry(q, kv, heads, heads_kv, D, dtype, scale, T_max)) != 0) return e;
+  if (S_max < 0 || T_max > DEC_MAX_T || kv_chunk <= 0 || kv_chunk % DEC_STEP != 0) return RUA_EINVAL;
+  if ((e = dec_make_plan(q->B, heads, heads_kv, D, T_max, S_max, kv_chunk, p)) != 0) return e;
+  if (ws_bytes < p.ws_bytes || (p.ws_bytes > 0 && !ws)) return RUA_EINVAL;
+  if (q->B == 0) return 0;
+  const bool padded = q->kind == RUA_LEFT || q->kind == RUA_RIGHT;
+  if (T_max == 0) {                                             // nothing but the padding zeros of an L / R result
+    if (!padded || q->n_rows == 0) return 0;
+    p.ncb = 1;
+    p.n_split = 1;
+  }
+  if ((q->n_rows > 0 && (!q_ptr || !out || !lse)) || (kv->n_rows > 0 && (!k_ptr || !v_ptr))) return RUA_EINVAL;
+  if (attn_misaligned(q_ptr) || attn_misaligned(k_ptr) || attn_misaligned(v_ptr) || attn_misaligned(out) ||
+      attn_misaligned(ws) || ((uintptr_t)lse & 3))
+    return RUA_EALIGN;
+  if (seg_too_large(q, (int64_t)heads * D, 2) || seg_too_large(kv, (int64_t)heads_kv * D, kv_es)) return RUA_ERANGE;
+  if ((double)q->B * (double)heads_kv * (double)p.ncb * (double)p.n_split >= 4.0e18) return RUA_ERANGE;
+  L.items = q->B * heads_kv * p.ncb * p.n_split;
+  L.grid = (unsigned)(L.items < DEC_MAX_GRID ? L.items : DEC_MAX_GRID);
+  L.pairs = q->B * T_max * heads;
+  L.cgrid = (L.pairs * (D / 4) + RUA_BLOCK - 1) / RUA_BLOCK;
+  if (p.n_split > 1 && L.cgrid > 0x7fffffffLL) return RUA_ERANGE;
+  L.bd = {left < 0 ? -1 : left, right < 0 ? -1 : right, heads_kv, align_end != 0};
+  L.run = true;
+  return 0;
+}
+
+int dec_combine(const rua_layout* q, const rua_layout* kv, const dec_launch& L, const void* ws, void* out, void* lse,
+                int32_t heads, int32_t D, int32_t dtype, int32_t heads_kv, int64_t T_max, hipStream_t s) {
+  const rua_layout LQ = *q, LK = *kv;
+  const dec_plan& p = L.p;
+  seg_trace("seg_attn_decode_combine_kernel D=%d heads=%d kvheads=%d chunk=%lld splits=%lld grid=%lld", D, heads, heads_kv,
+            (long long)p.kv_chunk, (long long)p.n_split, (long long)L.cgrid);
+#define RUA_ATTN_COMBINE(XX, DD)                                                                                       \
+  hipLaunchKernelGGL((seg_attn_decode_combine_kernel<XX, DD>), dim3((unsigned)L.cgrid), dim3(RUA_BLOCK), 0, s, LQ, LK, \
+                     (const float*)ws, (uint16_t*)out, (float*)lse, (int)heads, (int)heads_kv, T_max, p.ncb,           \
+                     p.kv_chunk, p.n_split, L.pairs)
+  RUA_ATTN_DISPATCH_BAND(dtype, D, RUA_ATTN_COMBINE);
+#undef RUA_ATTN_COMBINE
+  return (int)hipGetLastError();
+}
+
 }  // namespace rua
 
 extern "C" int rua_attention_decode_plan(int64_t B, int32_t heads, int32_t heads_kv, int32_t D, int64_t T_max,
@@ -320,31 +362,16 @@ extern "C" int rua_segment_attention_decode(const rua_layout* q, const rua_layou
                                             int64_t S_max, int64_t kv_chunk, void* stream) {
   using namespace rua;
   int e;
-  if ((e = attn_check_entry(q, kv, heads, heads_kv, D, dtype, scale, T_max)) != 0) return e;
-  if (S_max < 0 || T_max > DEC_MAX_T || kv_chunk <= 0 || kv_chunk % DEC_STEP != 0) return RUA_EINVAL;
-  dec_plan p;
-  if ((e = dec_make_plan(q->B, heads, heads_kv, D, T_max, S_max, kv_chunk, p)) != 0) return e;
-  if (ws_bytes < p.ws_bytes || (p.ws_bytes > 0 && !ws)) return RUA_EINVAL;
-  if (q->B == 0) return 0;
-  const bool padded = q->kind == RUA_LEFT || q->kind == RUA_RIGHT;
-  if (T_max == 0) {                                             // nothing but the padding zeros of an L / R result
-    if (!padded || q->n_rows == 0) return 0;
-    p.ncb = 1;
-    p.n_split = 1;
-  }
-  if ((q->n_rows > 0 && (!q_ptr || !out || !lse)) || (kv->n_rows > 0 && (!k_ptr || !v_ptr))) return RUA_EINVAL;
-  if (attn_misaligned(q_ptr) || attn_misaligned(k_ptr) || attn_misaligned(v_ptr) || attn_misaligned(out) ||
-      attn_misaligned(ws) || ((uintptr_t)lse & 3))
-    return RUA_EALIGN;
-  if (seg_too_large(q, (int64_t)heads * D, 2) || seg_too_large(kv, (int64_t)heads_kv * D, 2)) return RUA_ERANGE;
-  if ((double)q->B * (double)heads_kv * (double)p.ncb * (double)p.n_split >= 4.0e18) return RUA_ERANGE;
-  const int64_t items = q->B * heads_kv * p.ncb * p.n_split;
-  const unsigned grid = (unsigned)(items < DEC_MAX_GRID ? items : DEC_MAX_GRID);
-  const int64_t pairs = q->B * T_max * heads, cgrid = (pairs * (D / 4) + RUA_BLOCK - 1) / RUA_BLOCK;
-  if (p.n_split > 1 && cgrid > 0x7fffffffLL) return RUA_ERANGE;
+  dec_launch L;
+  if ((e = dec_prepare(q, kv, q_ptr, k_ptr, v_ptr, out, lse, ws, ws_bytes, heads, D, dtype, heads_kv, left, right,
+                       align_end, scale, T_max, S_max, kv_chunk, 2, L)) != 0 || !L.run)
+    return e;
+  const dec_plan& p = L.p;
+  const unsigned grid = L.grid;
+  const int64_t items = L.items;
   const hipStream_t s = (hipStream_t)stream;
   const rua_layout LQ = *q, LK = *kv;
-  const attn_band bd = {left < 0 ? -1 : left, right < 0 ? -1 : right, heads_kv, align_end != 0};
+  const attn_band bd = L.bd;
   seg_trace("seg_attn_decode_kernel D=%d heads=%d kvheads=%d left=%lld right=%lld end=%d cols=%lld chunk=%lld splits=%lld "
             "kind=%d kvkind=%d grid=%u", D, heads, heads_kv, (long long)bd.left, (long long)bd.right, bd.align_end,
             (long long)(T_max * (heads / heads_kv)), (long long)p.kv_chunk, (long long)p.n_split, LQ.kind, LK.kind, grid);
@@ -355,13 +382,5 @@ extern "C" int rua_segment_attention_decode(const rua_layout* q, const rua_layou
   RUA_ATTN_DISPATCH_BAND(dtype, D, RUA_ATTN_DECODE);
 #undef RUA_ATTN_DECODE
   if ((e = (int)hipGetLastError()) != 0 || p.n_split == 1) return e;
-  seg_trace("seg_attn_decode_combine_kernel D=%d heads=%d kvheads=%d chunk=%lld splits=%lld grid=%lld", D, heads, heads_kv,
-            (long long)p.kv_chunk, (long long)p.n_split, (long long)cgrid);
-#define RUA_ATTN_COMBINE(XX, DD)                                                                                       \
-  hipLaunchKernelGGL((seg_attn_decode_combine_kernel<XX, DD>), dim3((unsigned)cgrid), dim3(RUA_BLOCK), 0, s, LQ, LK,   \
-                     (const float*)ws, (uint16_t*)out, (float*)lse, (int)heads, (int)heads_kv, T_max, p.ncb,           \
-                     p.kv_chunk, p.n_split, pairs)
-  RUA_ATTN_DISPATCH_BAND(dtype, D, RUA_ATTN_COMBINE);
-#undef RUA_ATTN_COMBINE
-  return (int)hipGetLastError();
+  return dec_combine(q, kv, L, ws, out, lse, heads, D, dtype, heads_kv, T_max, s);
 }
