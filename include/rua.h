@@ -868,6 +868,38 @@ int rua_segment_attention_decode_fp8(const rua_layout* q, const rua_layout* kv, 
                                      int32_t kv_dtype, const float* k_scale, const float* v_scale,
                                      double k_scale_by_value, double v_scale_by_value, void* stream);
 
+/* rua_segment_attention_decode over a PAGED KV CACHE addressed by a block table (an EXTENSION, added to ABI 6 — the
+ * version number did not move; csrc/rua_attention_decode_paged.hip).  ONE entry for both cache types: the
+ * arguments of rua_segment_attention_decode_fp8 — with kv_dtype RUA_KV_SAME (k_ptr / v_ptr hold `dtype`; then both scale
+ * pointers are NULL and both by-value scales exactly 1.0) or RUA_KV_E4M3 — and
+ *   k_ptr, v_ptr   the pool [num_pages][page_size][heads_kv][D], contiguous;
+ *   page_table     device int32 [B][max_pages], contiguous; row b names the pages of sequence b in order;
+ *   page_size      16, 32, 64, 128 or 256 keys.
+ * `kv` supplies ONLY THE LENGTHS S_b (a CAT layout over the kv sizes does; its rows are never addressed).  Key and
+ * value s of sequence b, 0 <= s < S_b, are row  page_table[b][s / page_size] * page_size + s % page_size  of the pool,
+ * and the result is rua_segment_attention_decode(_fp8) over those rows gathered into a CAT cache — for the same kv_chunk
+ * THE SAME BITS, out and lse: steps, sub-tiles and splits are cut by key position from 0 as there, the plan
+ * (rua_attention_decode_plan, which never sees a page), the workspace and the combine kernel are shared.  Pages may
+ * be shared between sequences.
+ * WHAT IS READ: table columns at or past ceil(S_b / page_size) never; the rows of a last page past S_b never (they count
+ * as zero rows whatever the pool holds).  MEMORY SAFETY DOES NOT REST ON THE CALLER: a page id outside [0, num_pages) is
+ * never dereferenced — its keys and values read as ZERO ROWS, a defined result — and a table column is only read
+ * below max_pages.
+ * Checks, before any HIP call and in front of those of rua_segment_attention_decode: an unknown kv_dtype, a scale with
+ * RUA_KV_SAME, a by-value scale that is not finite and positive, another page_size, max_pages or num_pages < 0, a missing
+ * table (B > 0 and max_pages > 0) or pool (num_pages > 0), S_max > max_pages * page_size — the longest sequence fits the
+ * table — (RUA_EINVAL); a table pointer off 4 bytes (RUA_EALIGN); max_pages >= 2^31, or a table or pool too large for
+ * 64-bit offsets (RUA_ERANGE).  Trace: `seg_attn_decode_paged_kernel` with the fields of `seg_attn_decode_kernel` except
+ * kvkind=, and fp8=, page=, pages=, table=; `seg_attn_decode_combine_kernel` when n_split > 1. */
+#define RUA_KV_SAME 0
+int rua_segment_attention_decode_paged(const rua_layout* q, const rua_layout* kv, const void* q_ptr, const void* k_ptr,
+                                       const void* v_ptr, void* out, void* lse, void* ws, int64_t ws_bytes,
+                                       int32_t heads, int32_t D, int32_t dtype, int32_t heads_kv, int64_t left,
+                                       int64_t right, int32_t align_end, double scale, int64_t T_max, int64_t S_max,
+                                       int64_t kv_chunk, int32_t kv_dtype, const float* k_scale, const float* v_scale,
+                                       double k_scale_by_value, double v_scale_by_value, const int32_t* page_table,
+                                       int64_t max_pages, int32_t page_size, int64_t num_pages, void* stream);
+
 /* Per-sequence gated linear recurrence (an EXTENSION, added to ABI 6 — the version number did not move: the reference's
  * users pad, loop over the time steps with elementwise kernels and cast back).  For every sequence b of `lay` (ANY
  * layout) and column h, with u the position along the scan (u = t; reverse != 0: u = len - 1 - t):

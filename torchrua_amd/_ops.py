@@ -1457,16 +1457,19 @@ class AttentionArgs(NamedTuple):
 
 def attention_args(what: str, q, q_hidden, n_seq: int, k, k_hidden, n_k_seq: int, v, v_hidden, n_v_seq: int, scale,
                    causal=False, window=None, align='start',
-                   before_device: Optional[Callable[[], None]] = None, kv_8bit: bool = False) -> AttentionArgs:
+                   before_device: Optional[Callable[[], None]] = None, kv_8bit: bool = False,
+                   kv_names: Tuple[str, str] = ('k', 'v')) -> AttentionArgs:
     """AttentionArgs after the checks that come before any launch and need no lengths, each naming its argument:
     bf16 / f16 payloads of ONE dtype; `q` with exactly the hidden dimensions (heads, D), `k` with (heads_kv, D), heads a
     multiple of heads_kv, `v` like `k`; D of ATTN_HEAD_DIMS; the same number of sequences; one device; a finite `scale`
     (None: D ** -0.5); a `window` that is None, an int >= 0 or a pair of such or None, whose right side does not
     contradict `causal`; an `align` of 'start' / 'end'; and last (so that every other refusal can be met without a GPU)
     the payloads on a HIP device.  `kv_8bit` (attention_decode): `k` and `v` may BOTH be an 8-bit cache of
-    ATTN_KV_DTYPES instead of q's dtype; any other 1-byte dtype is refused by the name of the one that is read."""
+    ATTN_KV_DTYPES instead of q's dtype; any other 1-byte dtype is refused by the name of the one that is read.
+    `kv_names`: what the refusals call `k` and `v` (attention_decode_paged: its pools)."""
+    kn, vn = kv_names
     cache = tuple(L.ATTN_KV_DTYPES) if kv_8bit else ()
-    for name, t in (('q', q), ('k', k), ('v', v)):
+    for name, t in (('q', q), (kn, k), (vn, v)):
         if kv_8bit and name != 'q' and isinstance(t, Tensor) and t.dtype not in cache and t.element_size() == 1:
             raise L.RuaError(f'{what}: `{name}` has dtype {t.dtype}; the 8-bit cache that is read is '
                              f'{" / ".join(str(d) for d in cache)} (OCP e4m3)')
@@ -1474,28 +1477,28 @@ def attention_args(what: str, q, q_hidden, n_seq: int, k, k_hidden, n_k_seq: int
             raise L.RuaError(f'{what}: `{name}` is one of {list(L.ATTN_DTYPES)}; got '
                              f'{t.dtype if isinstance(t, Tensor) else type(t).__name__}')
     if (k.dtype in cache) != (v.dtype in cache):
-        raise L.RuaError(f'{what}: `v` has dtype {v.dtype}, `k` {k.dtype}: an 8-bit cache holds both')
-    for name, t in (('k', k), ('v', v)):
+        raise L.RuaError(f'{what}: `{vn}` has dtype {v.dtype}, `{kn}` {k.dtype}: an 8-bit cache holds both')
+    for name, t in ((kn, k), (vn, v)):
         if t.dtype != q.dtype and t.dtype not in cache:
             raise L.RuaError(f'{what}: `{name}` has dtype {t.dtype}, `q` {q.dtype}')
     if len(q_hidden) != 2:
         raise L.RuaError(f'{what}: `q` has exactly the hidden dimensions (heads, D); got {tuple(q_hidden)}')
     heads, D = int(q_hidden[0]), int(q_hidden[1])
     if len(k_hidden) != 2 or int(k_hidden[1]) != D:
-        raise L.RuaError(f'{what}: `k` has the hidden dimensions {tuple(k_hidden)}, `q` {tuple(q_hidden)}: '
+        raise L.RuaError(f'{what}: `{kn}` has the hidden dimensions {tuple(k_hidden)}, `q` {tuple(q_hidden)}: '
                          f'(heads_kv, D) with q\'s D')
     heads_kv = int(k_hidden[0])
     if heads_kv < 1 or heads % heads_kv:
-        raise L.RuaError(f'{what}: `k` has {heads_kv} heads, `q` {heads}: the query heads are a multiple of the kv heads '
+        raise L.RuaError(f'{what}: `{kn}` has {heads_kv} heads, `q` {heads}: the query heads are a multiple of the kv heads '
                          f'(query head h reads kv head h // (heads // heads_kv))')
     if tuple(v_hidden) != tuple(k_hidden):
-        raise L.RuaError(f'{what}: `v` has the hidden dimensions {tuple(v_hidden)}, `k` {tuple(k_hidden)}')
+        raise L.RuaError(f'{what}: `{vn}` has the hidden dimensions {tuple(v_hidden)}, `{kn}` {tuple(k_hidden)}')
     if D not in L.ATTN_HEAD_DIMS or heads < 1:
         raise L.RuaError(f'{what}: `q` has heads = {heads}, D = {D}; D is one of {L.ATTN_HEAD_DIMS} and heads >= 1')
-    for name, n in (('k', n_k_seq), ('v', n_v_seq)):
+    for name, n in ((kn, n_k_seq), (vn, n_v_seq)):
         if n != n_seq:
             raise L.RuaError(f'{what}: `{name}` holds {n} sequences, `q` {n_seq}')
-    for name, t in (('k', k), ('v', v)):
+    for name, t in ((kn, k), (vn, v)):
         if t.device != q.device:
             raise L.RuaError(f'{what}: `{name}` lives on {t.device}, `q` on {q.device}')
     if scale is None:
@@ -1667,6 +1670,31 @@ def attention_decode(q: Tensor, k: Tensor, v: Tensor, plan: AttentionPlan, kv_ch
               L.ptr(vs), k_scale[1], v_scale[1])
     else:
         _call('attention_decode', 'rua_segment_attention_decode', dev, *args)
+    return out, lse
+
+
+def attention_decode_paged(q: Tensor, k_pages: Tensor, v_pages: Tensor, page_table: Tensor, plan: AttentionPlan,
+                           kv_chunk: Optional[int], k_scale=(None, 1.0), v_scale=(None, 1.0)) -> Tuple[Tensor, Tensor]:
+    """rua_segment_attention_decode_paged: attention_decode() over the pool `k_pages` / `v_pages` [num_pages, page_size,
+    heads_kv, D] addressed by `page_table` [B, max_pages]; `plan.kv` supplies the lengths alone and `plan.kv_bound()`
+    fits the table (the caller has checked both).  The same plan, workspace and results as attention_decode()."""
+    q, k_pages, v_pages = _plain(q), _plain(k_pages), _plain(v_pages)
+    dev = L.require_device(q, k_pages, v_pages, page_table, k_scale[0], v_scale[0])
+    lead = tuple(q.shape[:-2])
+    if not plan.q.B or not plan.T_max or not q.numel():
+        return torch.zeros_like(q), torch.zeros(lead + (plan.heads,), dtype=torch.float32, device=dev)
+    s_max = plan.kv_bound()
+    chunk, _, ws_bytes = attention_decode_plan(plan.q.B, plan.heads, plan.heads_kv, plan.D, plan.T_max, s_max, kv_chunk)
+    q = q.contiguous()
+    out = torch.empty_like(q)
+    lse = torch.empty(lead + (plan.heads,), dtype=torch.float32, device=dev)
+    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev) if ws_bytes else None
+    ks, vs = (None if t is None else t.contiguous() for t in (k_scale[0], v_scale[0]))
+    _call('attention_decode_paged', 'rua_segment_attention_decode_paged', dev, plan.q.ref(), plan.kv.ref(), L.ptr(q),
+          L.ptr(k_pages), L.ptr(v_pages), L.ptr(out), L.ptr(lse), L.ptr(ws), ws_bytes, plan.heads, plan.D,
+          L.ATTN_DTYPES[q.dtype], plan.heads_kv, plan.left, 0 if plan.causal else plan.right, int(plan.align_end),
+          plan.scale, plan.T_max, s_max, chunk, L.ATTN_KV_DTYPES.get(k_pages.dtype, 0), L.ptr(ks), L.ptr(vs), k_scale[1],
+          v_scale[1], L.ptr(page_table), int(page_table.size(1)), int(k_pages.size(1)), int(k_pages.size(0)))
     return out, lse
 
 

@@ -96,8 +96,25 @@ mathematics, the containers, the argument checks and the one-answer semantics ar
     (float8_e5m2, the fnuz types, uint8); a scale with a bf16 / f16 cache; a scale tensor that is not float32
     [heads_kv] on q's device or requires grad; a scale number that is not finite and > 0 (bools are refused).
     `attention` itself refuses fp8.
-Out of scope there: gradients, more than 32 queries, paged or block-table caches, additive bias, merging across calls
-(`return_lse` makes it possible outside), tuning the plan; of 8-bit caches: float8_e5m2 and the fnuz formats, per-token
+  * A PAGED CACHE: `attention_decode_paged(q, k_pages, v_pages, page_table, kv_sizes, ...the same keywords...)` (also
+    `q.attention_decode_paged(...)` and `segment_attention_decode_paged(q, q_sizes, k_pages, ...)`;
+    csrc/rua_attention_decode_paged.hip).  `k_pages` / `v_pages` are contiguous tensors [num_pages,
+    page_size, heads_kv, D] of q's dtype or both float8_e4m3fn, page_size in {16, 32, 64, 128, 256}; `page_table` a
+    contiguous int32 [B, max_pages] and `kv_sizes` an int64 [B] on q's device (sequence b of a P is the sequence in
+    original order).  Key and value s of sequence b, 0 <= s < kv_sizes[b], are k_pages[page_table[b, s // page_size],
+    s % page_size] and the same element of v_pages; THE RESULT IS attention_decode OVER THOSE ROWS GATHERED INTO A C
+    CONTAINER, with the same keywords — for the same `kv_chunk` the same bits, out and lse.  Host-known kv_sizes: nothing
+    is read back; otherwise ONE blocking [B] copy.  Table columns at or past ceil(kv_sizes[b] / page_size) and the rows of
+    a last page past kv_sizes[b] are never read; two sequences may name the same page.  MEMORY SAFETY DOES NOT REST ON
+    THE CALLER: a page id outside [0, num_pages) is never dereferenced — its keys and values read as zero rows, a
+    defined result — and a max(kv_sizes) above max_pages * page_size is refused before the launch.  Refused besides what
+    attention_decode refuses: pools that are not 4-D, differ from each other, are not contiguous, have another dtype,
+    page_size, D or head ratio; a `page_table` that is not contiguous int32 [B, max_pages] on q's device; `kv_sizes`
+    that are not int64 [B].
+Out of scope there: gradients, more than 32 queries, additive bias, merging across calls
+(`return_lse` makes it possible outside), tuning the plan; of paged caches: an append or quantising append kernel
+(`index_copy_` on the flat view of the pool does it), page sizes below 16 or not a power of two, int64 tables, the
+head-major page layout [pages, heads_kv, page_size, D]; of 8-bit caches: float8_e5m2 and the fnuz formats, per-token
 or per-block scales, int8 / int4, an fp8 `q` or output and the fp8 matrix instruction, a quantising `join`.
 """
 import torch
@@ -107,7 +124,8 @@ from torchrua_amd import _ops as O
 from torchrua_amd.layout import (P, T, Z, cat_lay, cls_of, hidden_of, install, lay_hidden, lens_of, n_seq, rewrap)
 from torchrua_amd._lib import ATTN_DECODE_MAX_T, RuaError
 
-__all__ = ['attention', 'segment_attention', 'attention_decode', 'segment_attention_decode']
+__all__ = ['attention', 'segment_attention', 'attention_decode', 'segment_attention_decode', 'attention_decode_paged',
+           'segment_attention_decode_paged']
 
 
 def _known_bound(z: Z):
@@ -180,13 +198,13 @@ def segment_attention(q: T, q_sizes: T, k: T, v: T, kv_sizes: T, causal: bool = 
     return O.attention(q, k, v, plan)
 
 
-def _decode_checks(what: str, tensors, kv_chunk, q_bound) -> None:
+def _decode_checks(what: str, tensors, kv_chunk, q_bound, names=('q', 'k', 'v')) -> None:
     """What attention_decode refuses on top of attention's checks, before the CPU-tensor refusal."""
     if kv_chunk is not None and (isinstance(kv_chunk, bool) or not isinstance(kv_chunk, int) or kv_chunk <= 0 or
                                  kv_chunk % 128):
         raise RuaError(f'{what}: `kv_chunk` = {kv_chunk!r} is None or a positive multiple of 128 (the keys per split)')
     if torch.is_grad_enabled():
-        for name, t in zip(('q', 'k', 'v'), tensors):
+        for name, t in zip(names, tensors):
             if t.requires_grad:
                 raise RuaError(f'{what}: `{name}` requires grad and {what} is forward only; `attention` is the '
                                f'differentiable operator')
@@ -259,4 +277,97 @@ def segment_attention_decode(q: T, q_sizes: T, k: T, v: T, kv_sizes: T, causal: 
     return (out, lse) if return_lse else out
 
 
-install(attention=attention, attention_decode=attention_decode)
+PAGE_SIZES = (16, 32, 64, 128, 256)
+
+
+def _table_fits(what: str, s_max, page_table: T, page_size: int) -> None:
+    if s_max is not None and s_max > int(page_table.size(1)) * page_size:
+        raise RuaError(f'{what}: `page_table` has {int(page_table.size(1))} columns of {page_size} keys and the longest '
+                       f'sequence of `kv_sizes` holds {s_max}: the table names the pages of every key')
+
+
+def _decode_paged(what: str, q: T, q_hidden, B: int, q_lay, q_bound, k_pages: T, v_pages: T, page_table: T, kv_sizes: T,
+                  causal, scale, window, align, kv_chunk, k_scale, v_scale):
+    """Both paged forms behind their own first checks.  `q` is the payload; `q_lay()` its layout; `q_bound(known_only)`
+    its longest sequence (None: only a read-back can tell, and `known_only` forbids one)."""
+    for name, t in (('k_pages', k_pages), ('v_pages', v_pages)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4:
+            raise RuaError(f'{what}: `{name}` is a tensor [num_pages, page_size, heads_kv, D]; got '
+                           f'{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}')
+    if tuple(v_pages.shape) != tuple(k_pages.shape):
+        raise RuaError(f'{what}: `v_pages` has the shape {tuple(v_pages.shape)}, `k_pages` {tuple(k_pages.shape)}')
+    for name, t in (('k_pages', k_pages), ('v_pages', v_pages)):
+        if not t.is_contiguous():
+            raise RuaError(f'{what}: `{name}` is contiguous (a pool is addressed by page id, never copied)')
+    page_size = int(k_pages.size(1))
+    if page_size not in PAGE_SIZES:
+        raise RuaError(f'{what}: `k_pages` has page_size = {page_size}; it is one of {PAGE_SIZES}')
+    scales = []
+
+    def before_device():
+        if (not isinstance(page_table, torch.Tensor) or page_table.dtype != torch.int32 or page_table.dim() != 2 or
+                int(page_table.size(0)) != B or not page_table.is_contiguous() or page_table.device != q.device):
+            got = (f'{page_table.dtype} {tuple(page_table.shape)} on {page_table.device}'
+                   if isinstance(page_table, torch.Tensor) else type(page_table).__name__)
+            raise RuaError(f'{what}: `page_table` is a contiguous int32 tensor [B, max_pages] = [{B}, max_pages] on '
+                           f'{q.device}; got {got}')
+        if (not isinstance(kv_sizes, torch.Tensor) or kv_sizes.dtype != torch.int64 or tuple(kv_sizes.shape) != (B,) or
+                kv_sizes.device != q.device):
+            got = (f'{kv_sizes.dtype} {tuple(kv_sizes.shape)} on {kv_sizes.device}'
+                   if isinstance(kv_sizes, torch.Tensor) else type(kv_sizes).__name__)
+            raise RuaError(f'{what}: `kv_sizes` is an int64 tensor [B] = [{B}] on {q.device}; got {got}')
+        _decode_checks(what, (q, k_pages, v_pages), kv_chunk, q_bound(True), ('q', 'k_pages', 'v_pages'))
+        scales.extend(O.cache_scale(what, name, s, t, int(k_pages.size(2)), q)
+                      for name, s, t in (('k_scale', k_scale, k_pages), ('v_scale', v_scale, v_pages)))
+        _table_fits(what, M.known_max_len(kv_sizes) if B else 0, page_table, page_size)
+
+    a = O.attention_args(what, q, q_hidden, B, k_pages, tuple(k_pages.shape[2:]), B, v_pages, tuple(v_pages.shape[2:]), B,
+                         scale, causal, window, align, before_device=before_device, kv_8bit=True,
+                         kv_names=('k_pages', 'v_pages'))
+    t_max = q_bound(False)
+    _at_most_decode(what, t_max)
+    s_max, kv_lay = 0, None
+    if B and t_max and q.numel():                               # (else: zeros without a launch, as attention_decode)
+        s_max = M.max_len(kv_sizes)                             # the ONE [B] read-back, when the host does not know them
+        _table_fits(what, s_max, page_table, page_size)
+        kv_lay = M.lay_cat(kv_sizes, B, M.total_len(kv_sizes))  # it supplies the lengths alone
+    plan = O.AttentionPlan(q_lay(), kv_lay, a.heads, a.D, bool(causal), a.scale, t_max, lambda: s_max, a.heads_kv, a.left,
+                           a.right, a.align_end)
+    return O.attention_decode_paged(q, k_pages, v_pages, page_table, plan, kv_chunk, *scales)
+
+
+def attention_decode_paged(q: Z, k_pages: T, v_pages: T, page_table: T, kv_sizes: T, causal: bool = True, scale=None,
+                           window=None, align: str = 'end', kv_chunk=None, return_lse: bool = False, k_scale=None,
+                           v_scale=None):
+    """`attention_decode` over a PAGED cache: `k_pages` / `v_pages` [num_pages, page_size, heads_kv, D] (q's dtype or
+    float8_e4m3fn), `page_table` int32 [B, max_pages], `kv_sizes` int64 [B].  Key s of sequence b is
+    k_pages[page_table[b, s // page_size], s % page_size]; the result is attention_decode over those rows gathered into a
+    C container — for the same `kv_chunk` the same bits."""
+    what = 'attention_decode_paged'
+    if cls_of(q) is None:
+        raise RuaError(f'{what}: `q` is a container (C / L / P / R); got {type(q).__name__}')
+    out, lse = _decode_paged(what, q.data, hidden_of(q), n_seq(q), lambda: lay_hidden(q)[0],
+                             lambda known_only: _known_bound(q) if known_only else _bound(q), k_pages, v_pages, page_table,
+                             kv_sizes, causal, scale, window, align, kv_chunk, k_scale, v_scale)
+    return (rewrap(q, out), lse) if return_lse else rewrap(q, out)
+
+
+def segment_attention_decode_paged(q: T, q_sizes: T, k_pages: T, v_pages: T, page_table: T, kv_sizes: T,
+                                   causal: bool = True, scale=None, window=None, align: str = 'end', kv_chunk=None,
+                                   return_lse: bool = False, k_scale=None, v_scale=None):
+    """`attention_decode_paged` of every run of `q_sizes` rows of `q` [N, heads, D]."""
+    what = 'segment_attention_decode_paged'
+    for name, t in (('q', q), ('q_sizes', q_sizes)):
+        if not isinstance(t, torch.Tensor):
+            raise RuaError(f'{what}: `{name}` is a tensor; got {type(t).__name__}')
+
+    def bound(known_only):
+        known = M.known_max_len(q_sizes) if q_sizes.numel() else 0
+        return known if known is not None or known_only else M.max_len(q_sizes)
+
+    out, lse = _decode_paged(what, q, tuple(q.shape[1:]), int(q_sizes.numel()), lambda: cat_lay(q, q_sizes), bound, k_pages,
+                             v_pages, page_table, kv_sizes, causal, scale, window, align, kv_chunk, k_scale, v_scale)
+    return (out, lse) if return_lse else out
+
+
+install(attention=attention, attention_decode=attention_decode, attention_decode_paged=attention_decode_paged)

@@ -51,7 +51,6 @@
 namespace rua {
 
 static_assert(DEC_STEP == 32 * RUA_WAVES_PER_BLOCK && DEC_COLS == 32, "a wave owns 32 keys of a step; a tile is 32 x 32");
-constexpr int DEC_TS = 32 + 8;                     // tokens of a transposed V row in LDS, padded by 16 bytes
 
 // K (the A operand of the scores) and V (staged transposed below) of the 32 keys [ks, ks + 32): lane (j, g) takes the 16
 // bytes 16 st + 8 g .. + 7 of key ks + j, st = 0 .. D / 16 - 1; zeros when the key is past the end or `on` is false

@@ -52,24 +52,6 @@
 
 namespace rua {
 
-constexpr int DEC8_TS = 32 + 4;                    // tokens of a transposed V row in LDS (see BANKS)
-
-typedef __bf16 dec8_bf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 dec8_f16x2 __attribute__((ext_vector_type(2)));
-
-// two e4m3 codes (the low or the high half of `w`) as two elements of X's type, exactly; the scale operand is 1.0
-template <typename X, bool HI> __device__ __forceinline__ uint32_t dec8_pair(uint32_t w) {
-  if constexpr (X::SPLIT)   // at_bf16
-    return __builtin_bit_cast(uint32_t, (dec8_bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, HI));
-  else
-    return __builtin_bit_cast(uint32_t, (dec8_f16x2)__builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, HI));
-}
-
-// eight codes (8 bytes) as one matrix operand of eight elements
-template <typename X> __device__ __forceinline__ uint4 dec8_up(uint32_t lo, uint32_t hi) {
-  return make_uint4(dec8_pair<X, false>(lo), dec8_pair<X, true>(lo), dec8_pair<X, false>(hi), dec8_pair<X, true>(hi));
-}
-
 // K and V codes of the 32 keys [ks, ks + 32): lane (j, g) takes the 16 bytes 32 s + 16 g .. + 15 of key ks + j, s = 0 ..
 // D / 32 - 1; zeros (code 0x00 = +0) when the key is past the end or `on` is false
 template <int D>
@@ -277,8 +259,6 @@ void seg_attn_decode_fp8_kernel(rua_layout LQ, rua_layout LK, const uint16_t* __
     }
   }
 }
-
-static bool dec8_bad_scale(double x) { return !(x > 0.0) || x - x != 0.0; }   // not a finite positive number
 
 }  // namespace rua
 
