@@ -900,6 +900,33 @@ int rua_segment_attention_decode_paged(const rua_layout* q, const rua_layout* kv
                                        double k_scale_by_value, double v_scale_by_value, const int32_t* page_table,
                                        int64_t max_pages, int32_t page_size, int64_t num_pages, void* stream);
 
+/* The forward of attention over a PAGED KV cache for ANY number of queries per sequence: a prompt, or a chunk of one,
+ * against the pool the decode steps read (an EXTENSION, added to ABI 6 — the version number did not move;
+ * csrc/rua_attention_paged.hip).  The arguments of rua_segment_attention_band_forward, then `S_max` (the
+ * longest kv sequence) and the cache arguments of rua_segment_attention_decode_paged with their meaning there: kv_dtype
+ * (RUA_KV_SAME / RUA_KV_E4M3), k_scale / v_scale, the two by-value scales, page_table, max_pages, page_size, num_pages;
+ * k_ptr / v_ptr are the pool and `kv` supplies ONLY THE LENGTHS.  THE RESULT IS rua_segment_attention_band_forward over
+ * the rows the table names gathered into a CAT cache (codes dequantised first) — the same bits, out and lse, whenever
+ * the dequantised cache is representable in `dtype` (always for RUA_KV_SAME; for codes with power-of-two scales).
+ * The matrix columns of (sequence, kv head) are c = t G + gi — query position t, head hk G + gi — in blocks of 128; a
+ * work item is (sequence, kv head, column block), at most 2 048 workgroups stride over them; the four waves of a
+ * workgroup own 32 columns each and walk ALL the visible keys of the block in tiles of 64 cut by position from 0,
+ * staged once per workgroup for the G heads: ONE launch, no workspace, no atomics, bitwise reproducible, the same bits
+ * for every q layout.  `lse` is always written (-inf where no key is visible, 0 in the padding rows of an L / R result,
+ * which get zero output rows).  WHAT IS READ and the memory-safety rules are those of the paged decode entry: a table
+ * column only below max_pages and for a key < S_b, a page id outside [0, num_pages) never dereferenced (zero rows).
+ * Checks, before any HIP call: those of the band form, S_max < 0, then those of the paged decode entry for kv_dtype, the
+ * scales, the page size, the table and the pool (the same codes); a payload pointer off 16 bytes, lse, a scale or the
+ * table off 4 (RUA_EALIGN).  B == 0 or T_max == 0 launches nothing.  Trace: `seg_attn_paged_forward_kernel` (D=, heads=,
+ * kvheads=, left=, right=, end=, cols= T_max G, kind=, fp8=, page=, pages=, table=, grid=). */
+int rua_segment_attention_paged_forward(const rua_layout* q, const rua_layout* kv, const void* q_ptr, const void* k_ptr,
+                                        const void* v_ptr, void* out, void* lse, int32_t heads, int32_t D,
+                                        int32_t dtype, int32_t heads_kv, int64_t left, int64_t right, int32_t align_end,
+                                        double scale, int64_t T_max, int64_t S_max, int32_t kv_dtype,
+                                        const float* k_scale, const float* v_scale, double k_scale_by_value,
+                                        double v_scale_by_value, const int32_t* page_table, int64_t max_pages,
+                                        int32_t page_size, int64_t num_pages, void* stream);
+
 /* Per-sequence gated linear recurrence (an EXTENSION, added to ABI 6 — the version number did not move: the reference's
  * users pad, loop over the time steps with elementwise kernels and cast back).  For every sequence b of `lay` (ANY
  * layout) and column h, with u the position along the scan (u = t; reverse != 0: u = len - 1 - t):

@@ -180,6 +180,11 @@ SYMBOLS = {
                                                    c_int32, c_int64, c_int64, c_int32, c_double, c_int64, c_int64,
                                                    c_int64, c_int32, c_void_p, c_void_p, c_double, c_double, c_void_p,
                                                    c_int64, c_int32, c_int64, c_void_p]),
+    'rua_segment_attention_paged_forward': (c_int, [POINTER(RuaLayout), POINTER(RuaLayout), c_void_p, c_void_p, c_void_p,
+                                                    c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int64,
+                                                    c_int64, c_int32, c_double, c_int64, c_int64, c_int32, c_void_p,
+                                                    c_void_p, c_double, c_double, c_void_p, c_int64, c_int32, c_int64,
+                                                    c_void_p]),
     'rua_linear_scan_ws_bytes': (c_int64, [POINTER(RuaLayout), c_int64, c_int32]),
     'rua_segment_linear_scan': (c_int, [POINTER(RuaLayout), c_void_p, c_void_p, c_double, c_void_p, c_int64, c_int32,
                                         c_int32, c_void_p, c_void_p]),

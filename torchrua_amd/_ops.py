@@ -1698,6 +1698,29 @@ def attention_decode_paged(q: Tensor, k_pages: Tensor, v_pages: Tensor, page_tab
     return out, lse
 
 
+def attention_paged(q: Tensor, k_pages: Tensor, v_pages: Tensor, page_table: Tensor, plan: AttentionPlan,
+                    k_scale=(None, 1.0), v_scale=(None, 1.0)) -> Tuple[Tensor, Tensor]:
+    """rua_segment_attention_paged_forward: the forward of attention() for any number of queries per sequence over the
+    pool `k_pages` / `v_pages` addressed by `page_table` — ONE launch, no workspace.  `plan.kv` supplies the lengths
+    alone and `plan.kv_bound()` fits the table (the caller has checked both).  (out of q's storage shape and dtype, lse
+    [*q storage rows, heads] fp32), without a graph.  No sequence or no query: zeros without a launch."""
+    q, k_pages, v_pages = _plain(q), _plain(k_pages), _plain(v_pages)
+    dev = L.require_device(q, k_pages, v_pages, page_table, k_scale[0], v_scale[0])
+    lead = tuple(q.shape[:-2])
+    if not plan.q.B or not plan.T_max or not q.numel():
+        return torch.zeros_like(q), torch.zeros(lead + (plan.heads,), dtype=torch.float32, device=dev)
+    q = q.contiguous()
+    out = torch.empty_like(q)
+    lse = torch.empty(lead + (plan.heads,), dtype=torch.float32, device=dev)
+    ks, vs = (None if t is None else t.contiguous() for t in (k_scale[0], v_scale[0]))
+    _call('attention_paged', 'rua_segment_attention_paged_forward', dev, plan.q.ref(), plan.kv.ref(), L.ptr(q),
+          L.ptr(k_pages), L.ptr(v_pages), L.ptr(out), L.ptr(lse), plan.heads, plan.D, L.ATTN_DTYPES[q.dtype],
+          plan.heads_kv, plan.left, 0 if plan.causal else plan.right, int(plan.align_end), plan.scale, plan.T_max,
+          plan.kv_bound(), L.ATTN_KV_DTYPES.get(k_pages.dtype, 0), L.ptr(ks), L.ptr(vs), k_scale[1], v_scale[1],
+          L.ptr(page_table), int(page_table.size(1)), int(k_pages.size(1)), int(k_pages.size(0)))
+    return out, lse
+
+
 # ------------------------------------------------------------------ per-sequence gated linear recurrence (an extension)
 def _gate_arg(data: Tensor, gate) -> Tuple[Optional[Tensor], float]:
     """(the gate tensor or None, the scalar gate): a tensor of the payload's storage shape, dtype and device, or ONE

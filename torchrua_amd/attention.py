@@ -111,7 +111,27 @@ mathematics, the containers, the argument checks and the one-answer semantics ar
     attention_decode refuses: pools that are not 4-D, differ from each other, are not contiguous, have another dtype,
     page_size, D or head ratio; a `page_table` that is not contiguous int32 [B, max_pages] on q's device; `kv_sizes`
     that are not int64 [B].
-Out of scope there: gradients, more than 32 queries, additive bias, merging across calls
+
+PREFILL OVER A PAGED CACHE.
+
+    attention_paged(q, k_pages, v_pages, page_table, kv_sizes, causal=True, scale=None, window=None, align='end',
+                    return_lse=False, k_scale=None, v_scale=None)                   also q.attention_paged(...)
+    segment_attention_paged(q, q_sizes, k_pages, v_pages, page_table, kv_sizes, ...the same keywords...)
+
+The forward of `attention` for ANY number of queries per sequence — a prompt, or a chunk of one — over the pool, table,
+sizes and scales of `attention_decode_paged`, a bf16 / f16 or float8_e4m3fn cache (csrc/rua_attention_paged.hip; DESIGN
+3.2v).  THE DEFAULTS ARE THE DECODE MASK.  THE RESULT IS attention(q, C(gathered k), C(gathered v), causal, scale, window,
+align) over the rows the table names, an fp8 cache dequantised first: q's container type and metadata objects, zeros in
+padding rows, a zero row and lse = -inf without a visible key; `return_lse=True` also returns attention_decode's lse.
+Forward only (an input that requires grad under grad mode is refused and pointed to `attention`); no `kv_chunk`, no
+32-query limit; ONE launch sized by the longest q sequence (attention's rule); `kv_sizes` by attention_decode_paged's
+rule (host-known: nothing read back, else ONE [B] copy; a max above max_pages * page_size refused before the launch).
+The refusals are attention_decode_paged's for the pool, table, sizes, scales and dtypes and attention's for the rest.  A
+group's G query heads are packed into the matrix columns: a K / V tile is staged once per kv head, and all four q
+layouts give the same bits — those of `attention` over the gathered cache, out and lse (an fp8 cache: with power-of-two
+scales; others add the rounding terms of attention_decode's fp8 cache).
+
+Out of scope there: gradients, more than 32 queries in a decode step, additive bias, merging across calls
 (`return_lse` makes it possible outside), tuning the plan; of paged caches: an append or quantising append kernel
 (`index_copy_` on the flat view of the pool does it), page sizes below 16 or not a power of two, int64 tables, the
 head-major page layout [pages, heads_kv, page_size, D]; of 8-bit caches: float8_e5m2 and the fnuz formats, per-token
@@ -125,7 +145,7 @@ from torchrua_amd.layout import (P, T, Z, cat_lay, cls_of, hidden_of, install, l
 from torchrua_amd._lib import ATTN_DECODE_MAX_T, RuaError
 
 __all__ = ['attention', 'segment_attention', 'attention_decode', 'segment_attention_decode', 'attention_decode_paged',
-           'segment_attention_decode_paged']
+           'segment_attention_decode_paged', 'attention_paged', 'segment_attention_paged']
 
 
 def _known_bound(z: Z):
@@ -203,12 +223,16 @@ def _decode_checks(what: str, tensors, kv_chunk, q_bound, names=('q', 'k', 'v'))
     if kv_chunk is not None and (isinstance(kv_chunk, bool) or not isinstance(kv_chunk, int) or kv_chunk <= 0 or
                                  kv_chunk % 128):
         raise RuaError(f'{what}: `kv_chunk` = {kv_chunk!r} is None or a positive multiple of 128 (the keys per split)')
+    _forward_only(what, tensors, names)
+    _at_most_decode(what, q_bound)
+
+
+def _forward_only(what: str, tensors, names) -> None:
     if torch.is_grad_enabled():
         for name, t in zip(names, tensors):
             if t.requires_grad:
                 raise RuaError(f'{what}: `{name}` requires grad and {what} is forward only; `attention` is the '
                                f'differentiable operator')
-    _at_most_decode(what, q_bound)
 
 
 def _at_most_decode(what: str, q_bound) -> None:
@@ -286,10 +310,12 @@ def _table_fits(what: str, s_max, page_table: T, page_size: int) -> None:
                        f'sequence of `kv_sizes` holds {s_max}: the table names the pages of every key')
 
 
-def _decode_paged(what: str, q: T, q_hidden, B: int, q_lay, q_bound, k_pages: T, v_pages: T, page_table: T, kv_sizes: T,
-                  causal, scale, window, align, kv_chunk, k_scale, v_scale):
-    """Both paged forms behind their own first checks.  `q` is the payload; `q_lay()` its layout; `q_bound(known_only)`
-    its longest sequence (None: only a read-back can tell, and `known_only` forbids one)."""
+def _paged_plan(what: str, q: T, q_hidden, B: int, q_lay, q_bound, k_pages: T, v_pages: T, page_table: T, kv_sizes: T,
+                causal, scale, window, align, k_scale, v_scale, decode: bool, kv_chunk=None):
+    """(the plan, the two scales) of every paged form behind its own first checks.  `q` is the payload; `q_lay()` its
+    layout; `q_bound(known_only)` its longest sequence (None: only a read-back can tell, and `known_only` forbids one).
+    `decode`: attention_decode's own refusals (`kv_chunk`, at most 32 queries) apply; otherwise only its forward-only
+    one does."""
     for name, t in (('k_pages', k_pages), ('v_pages', v_pages)):
         if not isinstance(t, torch.Tensor) or t.dim() != 4:
             raise RuaError(f'{what}: `{name}` is a tensor [num_pages, page_size, heads_kv, D]; got '
@@ -316,7 +342,10 @@ def _decode_paged(what: str, q: T, q_hidden, B: int, q_lay, q_bound, k_pages: T,
             got = (f'{kv_sizes.dtype} {tuple(kv_sizes.shape)} on {kv_sizes.device}'
                    if isinstance(kv_sizes, torch.Tensor) else type(kv_sizes).__name__)
             raise RuaError(f'{what}: `kv_sizes` is an int64 tensor [B] = [{B}] on {q.device}; got {got}')
-        _decode_checks(what, (q, k_pages, v_pages), kv_chunk, q_bound(True), ('q', 'k_pages', 'v_pages'))
+        if decode:
+            _decode_checks(what, (q, k_pages, v_pages), kv_chunk, q_bound(True), ('q', 'k_pages', 'v_pages'))
+        else:
+            _forward_only(what, (q, k_pages, v_pages), ('q', 'k_pages', 'v_pages'))
         scales.extend(O.cache_scale(what, name, s, t, int(k_pages.size(2)), q)
                       for name, s, t in (('k_scale', k_scale, k_pages), ('v_scale', v_scale, v_pages)))
         _table_fits(what, M.known_max_len(kv_sizes) if B else 0, page_table, page_size)
@@ -325,7 +354,8 @@ def _decode_paged(what: str, q: T, q_hidden, B: int, q_lay, q_bound, k_pages: T,
                          scale, causal, window, align, before_device=before_device, kv_8bit=True,
                          kv_names=('k_pages', 'v_pages'))
     t_max = q_bound(False)
-    _at_most_decode(what, t_max)
+    if decode:
+        _at_most_decode(what, t_max)
     s_max, kv_lay = 0, None
     if B and t_max and q.numel():                               # (else: zeros without a launch, as attention_decode)
         s_max = M.max_len(kv_sizes)                             # the ONE [B] read-back, when the host does not know them
@@ -333,6 +363,13 @@ def _decode_paged(what: str, q: T, q_hidden, B: int, q_lay, q_bound, k_pages: T,
         kv_lay = M.lay_cat(kv_sizes, B, M.total_len(kv_sizes))  # it supplies the lengths alone
     plan = O.AttentionPlan(q_lay(), kv_lay, a.heads, a.D, bool(causal), a.scale, t_max, lambda: s_max, a.heads_kv, a.left,
                            a.right, a.align_end)
+    return plan, scales
+
+
+def _decode_paged(what: str, q: T, q_hidden, B: int, q_lay, q_bound, k_pages: T, v_pages: T, page_table: T, kv_sizes: T,
+                  causal, scale, window, align, kv_chunk, k_scale, v_scale):
+    plan, scales = _paged_plan(what, q, q_hidden, B, q_lay, q_bound, k_pages, v_pages, page_table, kv_sizes, causal,
+                               scale, window, align, k_scale, v_scale, True, kv_chunk)
     return O.attention_decode_paged(q, k_pages, v_pages, page_table, plan, kv_chunk, *scales)
 
 
@@ -370,4 +407,42 @@ def segment_attention_decode_paged(q: T, q_sizes: T, k_pages: T, v_pages: T, pag
     return (out, lse) if return_lse else out
 
 
-install(attention=attention, attention_decode=attention_decode, attention_decode_paged=attention_decode_paged)
+def attention_paged(q: Z, k_pages: T, v_pages: T, page_table: T, kv_sizes: T, causal: bool = True, scale=None,
+                    window=None, align: str = 'end', return_lse: bool = False, k_scale=None, v_scale=None):
+    """The forward of `attention` for ANY number of queries per sequence over a PAGED cache — a prompt, or a chunk of
+    one, against the pool `attention_decode_paged` reads, with its arguments: `k_pages` / `v_pages` [num_pages,
+    page_size, heads_kv, D] (q's dtype or float8_e4m3fn), `page_table` int32 [B, max_pages], `kv_sizes` int64 [B].  THE
+    DEFAULTS ARE THE DECODE MASK (`causal=True, align='end'`): the queries are the last T_b positions of a cache that
+    already holds their keys.  The result is `attention` over the rows the table names gathered into a C container."""
+    what = 'attention_paged'
+    if cls_of(q) is None:
+        raise RuaError(f'{what}: `q` is a container (C / L / P / R); got {type(q).__name__}')
+    plan, scales = _paged_plan(what, q.data, hidden_of(q), n_seq(q), lambda: lay_hidden(q)[0],
+                               lambda known_only: _known_bound(q) if known_only else _bound(q), k_pages, v_pages,
+                               page_table, kv_sizes, causal, scale, window, align, k_scale, v_scale, False)
+    out, lse = O.attention_paged(q.data, k_pages, v_pages, page_table, plan, *scales)
+    return (rewrap(q, out), lse) if return_lse else rewrap(q, out)
+
+
+def segment_attention_paged(q: T, q_sizes: T, k_pages: T, v_pages: T, page_table: T, kv_sizes: T, causal: bool = True,
+                            scale=None, window=None, align: str = 'end', return_lse: bool = False, k_scale=None,
+                            v_scale=None):
+    """`attention_paged` of every run of `q_sizes` rows of `q` [N, heads, D]."""
+    what = 'segment_attention_paged'
+    for name, t in (('q', q), ('q_sizes', q_sizes)):
+        if not isinstance(t, torch.Tensor):
+            raise RuaError(f'{what}: `{name}` is a tensor; got {type(t).__name__}')
+
+    def bound(known_only):
+        known = M.known_max_len(q_sizes) if q_sizes.numel() else 0
+        return known if known is not None or known_only else M.max_len(q_sizes)
+
+    plan, scales = _paged_plan(what, q, tuple(q.shape[1:]), int(q_sizes.numel()), lambda: cat_lay(q, q_sizes), bound,
+                               k_pages, v_pages, page_table, kv_sizes, causal, scale, window, align, k_scale, v_scale,
+                               False)
+    out, lse = O.attention_paged(q, k_pages, v_pages, page_table, plan, *scales)
+    return (out, lse) if return_lse else out
+
+
+install(attention=attention, attention_decode=attention_decode, attention_decode_paged=attention_decode_paged,
+        attention_paged=attention_paged)

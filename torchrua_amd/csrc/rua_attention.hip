@@ -421,15 +421,6 @@ __global__ __launch_bounds__(RUA_BLOCK) void seg_attn_dq_kernel(rua_layout LQ, r
 }
 
 // ---------------------------------------------------------------- host side
-// the work items of a launch over blocks of `bound` positions, and its grid; false: too many for 63 bits
-static bool attn_items(int64_t B, int32_t heads, int64_t bound, int64_t& nblk, int64_t& items, unsigned& grid) {
-  nblk = (bound + ATTN_BLOCK_TOK - 1) / ATTN_BLOCK_TOK;
-  if ((double)B * (double)heads * (double)nblk >= 9.0e18) return false;
-  items = B * heads * nblk;
-  grid = (unsigned)(items < ATTN_MAX_GRID ? items : ATTN_MAX_GRID);
-  return true;
-}
-
 // LAUNCH(payload type, D, causal) by (dtype, D, causal)
 #define RUA_ATTN_DISPATCH(dtype, D, causal, LAUNCH)                                                                    \
   do {                                                                                                                 \

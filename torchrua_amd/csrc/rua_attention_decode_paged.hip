@@ -37,30 +37,9 @@
 #include <stdio.h>
 #include <stdint.h>
 #include <math.h>
-#include "rua_attention_decode_dev.h"
+#include "rua_attention_paged_dev.h"
 
 namespace rua {
-
-struct dec_pages {
-  const int32_t* table;   // [B][max_pages]
-  int64_t max_pages, num_pages;
-  int32_t lg;             // log2 page_size, 4 .. 8
-};
-
-// the table entry that serves lane j of the sub-tile [ks, ks + 32) of a sequence of S keys whose table row is `tb`; -1
-// when nothing may be read: the sub-tile is off, the lane's key is past the end, or the column is past the table
-__device__ __forceinline__ int32_t pg_entry(const dec_pages& pt, const int32_t* __restrict__ tb, int64_t S, int64_t ks,
-                                            bool on, int j) {
-  const int64_t pos = ks + j, col = pos >> pt.lg;
-  return (on && pos < S && col < pt.max_pages) ? tb[col] : -1;
-}
-
-// the pool row of key ks + j from its table entry, -1 (zeros) past the end or for a page id outside the pool
-__device__ __forceinline__ int64_t pg_row(const dec_pages& pt, int32_t page, int64_t S, int64_t ks, int j) {
-  const int64_t pos = ks + j;
-  if (pos >= S || page < 0 || (int64_t)page >= pt.num_pages) return -1;
-  return ((int64_t)page << pt.lg) | (pos & (((int64_t)1 << pt.lg) - 1));
-}
 
 // K and V of one key row: lane (j, g) takes the 16 bytes 32 st + 16 g .. + 15 of kv head hk, st = 0 .. NL - 1; row < 0:
 // zeros (for codes 0x00 = +0)
@@ -289,20 +268,6 @@ void seg_attn_decode_paged_kernel(rua_layout LQ, rua_layout LK, dec_pages pt, co
   }
 }
 
-// the checks that are the paged entry's own, in front of dec_prepare's; `lg` is log2 page_size
-static int pg_check(const rua_layout* q, int32_t heads_kv, int32_t D, int kv_es, const void* k_ptr, const void* v_ptr,
-                    const int32_t* page_table, int64_t max_pages, int32_t page_size, int64_t num_pages, int64_t S_max,
-                    int32_t& lg) {
-  for (lg = 4; lg <= 8 && (1 << lg) != page_size; ++lg) {}
-  if (lg > 8 || max_pages < 0 || num_pages < 0 || !q) return RUA_EINVAL;
-  if ((q->B > 0 && max_pages > 0 && !page_table) || (num_pages > 0 && (!k_ptr || !v_ptr))) return RUA_EINVAL;
-  if ((uintptr_t)page_table & 3) return RUA_EALIGN;
-  if (max_pages > 0x7fffffffLL || (double)q->B * (double)max_pages >= 4.0e18) return RUA_ERANGE;
-  if ((double)num_pages * page_size * (double)heads_kv * D * kv_es >= 9.0e18) return RUA_ERANGE;
-  if ((double)S_max > (double)max_pages * page_size) return RUA_EINVAL;   // the longest sequence fits the table
-  return 0;
-}
-
 }  // namespace rua
 
 extern "C" int rua_segment_attention_decode_paged(const rua_layout* q, const rua_layout* kv, const void* q_ptr,
@@ -318,11 +283,8 @@ extern "C" int rua_segment_attention_decode_paged(const rua_layout* q, const rua
   int e;
   dec_launch L;
   dec_pages pt;
-  const bool f8 = kv_dtype == RUA_KV_E4M3;
-  if (kv_dtype != RUA_KV_SAME && !f8) return RUA_EINVAL;
-  if (f8 ? dec8_bad_scale(k_scale_by_value) || dec8_bad_scale(v_scale_by_value)
-         : k_scale || v_scale || k_scale_by_value != 1.0 || v_scale_by_value != 1.0)
-    return RUA_EINVAL;
+  bool f8;
+  if ((e = pg_check_cache(kv_dtype, k_scale, v_scale, k_scale_by_value, v_scale_by_value, f8)) != 0) return e;
   if ((e = pg_check(q, heads_kv, D, f8 ? 1 : 2, k_ptr, v_ptr, page_table, max_pages, page_size, num_pages, S_max,
                     pt.lg)) != 0)
     return e;

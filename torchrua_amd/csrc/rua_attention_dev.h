@@ -1,5 +1,5 @@
 // rua_attention_dev.h — what the attention kernels (rua_attention.hip: the flash-style forward and the backward;
-// rua_attention_decode.hip: the split-KV decode forward) share: the payload types and their matrix instruction, the
+// rua_attention_decode.hip: the split-KV decode forward; rua_attention_paged.hip: the forward over a paged cache) share: the payload types and their matrix instruction, the
 // range-checked row, the LDS tile helpers, the rounding and packing of a tile into the B operand, the store of an O^T
 // accumulator, the padding zeros, the band, and the entry checks of their launchers.  The text was moved here from
 // rua_attention.hip unchanged; the geometry it serves is described there.
@@ -168,6 +168,15 @@ static int attn_check_entry(const rua_layout* lq, const rua_layout* lk, int32_t 
 }
 
 static bool attn_misaligned(const void* p) { return ((uintptr_t)p & 15) != 0; }
+
+// the work items of a launch over blocks of `bound` positions, and its grid; false: too many for 63 bits
+static bool attn_items(int64_t B, int32_t heads, int64_t bound, int64_t& nblk, int64_t& items, unsigned& grid) {
+  nblk = (bound + ATTN_BLOCK_TOK - 1) / ATTN_BLOCK_TOK;
+  if ((double)B * (double)heads * (double)nblk >= 9.0e18) return false;
+  items = B * heads * nblk;
+  grid = (unsigned)(items < ATTN_MAX_GRID ? items : ATTN_MAX_GRID);
+  return true;
+}
 
 // LAUNCH(payload type, D) by (dtype, D): the band instantiations <X, D, false, true>
 #define RUA_ATTN_DISPATCH_BAND(dtype, D, LAUNCH)                                                                       \
